@@ -2,7 +2,7 @@
 """Flagship benchmark: BERT-Large training throughput (samples/s) under the auto-searched
 parallelization strategy, one process per MI355X (torchrun), bf16 compute, synthetic data.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -12,6 +12,12 @@ optimizer pass and the small-GEMM tails). Every timed step is a
 full training iteration (forward, backward, gradient all-reduce, optimizer update). Rank 0 prints
 ONE JSON line; the step time is the MAX over ranks of the time between two barrier+synchronize
 fences around exactly K steps.
+
+A plain run sets up, warms up, times the K steps and prints the line: nothing else is measured.
+--full adds the measurements that take runs of their own (at N > 1 the data-parallel baseline of
+--compare-dp; on one GPU there is none). --dump-outputs DIR writes what the last timed step left
+for its caller as DIR/<name>.npy (see dump_outputs): inputs and initial weights are seeded, so two
+builds run with the same arguments can be compared array for array.
 """
 from __future__ import annotations
 
@@ -52,6 +58,11 @@ def parse():
     ap.add_argument("--zero", action="store_true",
                     help="ZeRO-1 sharded optimizer on data-parallel weights (reduce-scatter + all-gather)")
     ap.add_argument("--compare-dp", action="store_true", help="also time pure data parallel (speedup vs DP)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure that takes runs of its own (implies --compare-dp)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's results (metrics, model output, updated "
+                         "weights; seeded samples of the large ones, <= 64 MB in all) as DIR/<name>.npy")
     ap.add_argument("--verify-steps", type=int, default=4,
                     help="N>1: time the searched strategy and data parallel for this many steps each and keep "
                          "the faster (measurement-verified search; 0 disables)")
@@ -138,6 +149,42 @@ def timed(ff, steps, warmup, world):
     return el
 
 
+DUMP_SEED = 20240607
+DUMP_OUTPUT_ELEMS = 4 << 20   # float32 elements kept of the model output (16 MB)
+DUMP_WEIGHT_ELEMS = 8 << 20   # float32 elements kept of all weights together (32 MB)
+
+
+def _sample(t, cap, rng):
+    """t flattened as float32 on the host; more than cap elements: a seeded sample (sorted flat
+    indices drawn with replacement, the same for equal sizes and draw order) gathered on the device."""
+    flat = t.detach().reshape(-1)
+    if flat.numel() > cap:
+        idx = np.sort(rng.integers(0, flat.numel(), cap, dtype=np.int64))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    return flat.float().cpu().numpy()
+
+
+def dump_outputs(ff, out_dir, rank):
+    """What a caller holds after the last timed train_step(): the metric accumulators behind
+    get_perf_metrics() (metrics.npy, float64; sums over the warm-up and timed steps, whose device
+    reductions may differ in the last bit from run to run), the model output as Tensor.get_tensor()
+    returns it (output.npy) and the updated weights as Parameter.get_weights() returns them, in
+    layer order (weights.npy, one flat array). Every rank takes part (sharded values are gathered),
+    rank 0 writes."""
+    ex = ff.executor
+    rng = np.random.default_rng(DUMP_SEED)
+    arrays = {"metrics": np.asarray(ex.metrics_snapshot(), dtype=np.float64)}
+    arrays["output"] = _sample(ex.get_value(ff.resolve_tensor(ff.output_tensor())), DUMP_OUTPUT_ELEMS, rng)
+    weights = [w for L in ff.layers for w in L.weights if w.guid in ex.weight_layout]
+    cap = max(1024, DUMP_WEIGHT_ELEMS // max(1, len(weights)))
+    parts = [_sample(ex.get_weight(w), cap, rng) for w in weights]
+    arrays["weights"] = np.concatenate(parts) if parts else np.zeros(0, np.float32)
+    if rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        for name, a in arrays.items():
+            np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def sync(world):
     if world > 1:
         dist.barrier()
@@ -149,6 +196,8 @@ def sync(world):
 
 def main():
     args = parse()
+    if args.full:
+        args.compare_dp = True
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     if world != args.gpus and rank == 0:
@@ -178,6 +227,8 @@ def main():
         ff, gb, info = build(args, args.search)
     setup_s = time.perf_counter() - t_start  # build(s) + compile + search + verification
     el = timed(ff, args.steps, args.warmup, world)
+    if args.dump_outputs:
+        dump_outputs(ff, args.dump_outputs, rank)
     ms = el / args.steps * 1e3
     sps = gb * args.steps / el
     res = {

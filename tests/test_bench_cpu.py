@@ -66,6 +66,30 @@ def test_bench_single_process():
     _check(lines[0], 1)
 
 
+def test_bench_dump_outputs_is_reproducible_and_full_is_accepted(tmp_path):
+    """--dump-outputs writes the last timed step's metrics, model output and updated weights as
+    float32 / float64 .npy files; two runs with the same arguments write identical arrays (seeded
+    inputs and weights). --full is accepted on one process and leaves the result line's fields."""
+    import numpy as np
+    argv = ["--steps", "1", "--warmup", "0", "--model", "bert-tiny", "--seq", "32", "--batch-per-gpu", "2"]
+    dumps = []
+    for k, extra in enumerate(([], ["--full"])):
+        d = tmp_path / f"d{k}"
+        out = _bench_main(argv + extra + ["--dump-outputs", str(d)])
+        lines = [ln for ln in out.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        r = json.loads(lines[0])
+        assert REQUIRED <= set(r) and r["steps"] == 1 and r["warmup"] == 0 and r["ms_per_step"] > 0
+        dumps.append({f: np.load(d / f) for f in sorted(os.listdir(d))})
+    assert set(dumps[0]) == {"metrics.npy", "output.npy", "weights.npy"}
+    for f, a in dumps[0].items():
+        assert a.dtype in (np.float32, np.float64) and a.size > 0 and np.isfinite(a).all(), f
+        assert np.array_equal(a, dumps[1][f]), f
+    assert sum(a.nbytes for a in dumps[0].values()) <= 64 << 20
+    # the output is the model's softmax over the vocabulary: rows of probabilities
+    assert abs(float(dumps[0]["output.npy"].sum()) - 2 * 32) < 1e-2 * 2 * 32
+
+
 def test_bench_two_ranks_gloo():
     out = os.path.join(tempfile.mkdtemp(), "b.txt")
     mp.start_processes(_worker, args=(2, _free_port(), out), nprocs=2, join=True, start_method="spawn")

@@ -139,11 +139,14 @@ def test_rules_load_and_match():
     assert len(_core.match_rule(r, g, 8)) == 0
 
 
-def test_reference_rule_file_loads():
-    """The reference's TASO-derived rule collection parses (JSON read with the safe json module)."""
-    path = "/root/reference/substitutions/graph_subst_3_v2.json"
-    if not os.path.exists(path):
-        pytest.skip("reference rules not present")
+def test_reference_rule_file_loads(tmp_path):
+    """The reference's TASO-derived rule collection parses (JSON read with the safe json module).
+    The file is a fixture (tests/golden/substitutions, gzipped: 2 MB as text)."""
+    import gzip
+    path = str(tmp_path / "graph_subst_3_v2.json")
+    with gzip.open(os.path.join(ROOT, "tests", "golden", "substitutions", "graph_subst_3_v2.json.gz"), "rb") as f:
+        with open(path, "wb") as g:
+            g.write(f.read())
     rules = _core.load_rules(path)
     assert len(rules) > 100
     with open(path) as f:

@@ -14,14 +14,14 @@ from flexflow_amd.serving import InferenceServer, InferenceServerClient, InferIn
 from flexflow_amd.serving.client import InferenceServerException
 from flexflow_amd.serving.config import ModelConfig
 
-REPO = "/root/reference/triton/qa/L0_e2e/models"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REPO), reason="reference Triton QA models not mounted")
+# the reference's QA model repository, stored as fixtures
+REPO = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "triton_models")
 
 
 @pytest.fixture(scope="module")
 def server(tmp_path_factory):
     root = tmp_path_factory.mktemp("repo")
-    for m in os.listdir(REPO):  # a private copy (the reference tree is read-only data)
+    for m in os.listdir(REPO):  # a private copy (the fixtures are read-only data)
         shutil.copytree(os.path.join(REPO, m), root / m)
     srv = InferenceServer(str(root), port=0, ff_flags=["--device", "cpu", "--no-hip-graphs"]).start()
     yield srv

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
-REPO = "/root/reference/triton/qa/L0_e2e/models"
+REPO = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "triton_models")
 
 
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
@@ -18,8 +18,7 @@ def test_serve_on_gpu(tmp_path, dtype):
     from test_serving_cpu import _gemm_model, _infer
     assert torch.cuda.is_available()
     w, b = _gemm_model(tmp_path, 8, 100000)
-    if os.path.isdir(REPO):
-        shutil.copytree(os.path.join(REPO, "add"), tmp_path / "add")
+    shutil.copytree(os.path.join(REPO, "add"), tmp_path / "add")
     srv = InferenceServer(str(tmp_path), port=0, ff_flags=["--dtype", dtype]).start()
     try:
         m = srv.repo.get("mlp")
@@ -36,8 +35,7 @@ def test_serve_on_gpu(tmp_path, dtype):
         tol = 1e-4 if dtype == "fp32" else 5e-2
         for x, r in zip(xs, res):
             np.testing.assert_allclose(r, np.maximum(x @ w.T + b, 0), rtol=tol, atol=tol)
-        if os.path.isdir(REPO):
-            a = np.arange(8, dtype=np.float32).reshape(4, 2)
-            np.testing.assert_allclose(_infer(cl, "add", {"input0": a, "input1": a}), a + a)
+        a = np.arange(8, dtype=np.float32).reshape(4, 2)
+        np.testing.assert_allclose(_infer(cl, "add", {"input0": a, "input1": a}), a + a)
     finally:
         srv.stop()

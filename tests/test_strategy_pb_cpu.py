@@ -3,16 +3,15 @@ with --import-strategy: per-table embedding placement + data-parallel MLPs (refe
 generator examples/cpp/DLRM/strategies/dlrm_strategy.py)."""
 import os
 
-import pytest
-
 from flexflow_amd.core import FFConfig, FFModel
 from flexflow_amd.models.recsys import DLRMConfig, build_dlrm
 from flexflow_amd.pcg.search import choose_strategy
 from flexflow_amd.pcg.strategy import load_strategy_pb
 from flexflow_amd.type import OperatorType
 
-PB = "/root/reference/examples/cpp/DLRM/strategies/dlrm_strategy_8embs_8gpus.pb"
-pytestmark = pytest.mark.skipif(not os.path.exists(PB), reason="reference strategy files not mounted")
+# the reference's strategy files, stored as fixtures
+PB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "dlrm_strategies",
+                  "dlrm_strategy_8embs_8gpus.pb")
 
 
 def test_dlrm_pb_strategy_places_tables_and_keeps_mlp_data_parallel():
