@@ -212,6 +212,18 @@ int64_t gemm_pick_splitk(int64_t M, int64_t N, int64_t K, int64_t batch, int64_t
 
 // two tensors whose elements sit at the same offsets of dense memory (both NCHW-contiguous or both
 // channel-last-contiguous): elementwise kernels index them flat
+// the kernels below index their tensors flat in row-major order: a dense but permuted tensor (a
+// transpose, a channel-last activation) would be read or written in the wrong order
+void check_contig(const Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+}
+void check_contig(const optional<Tensor>& t, const char* name) {
+  if (t.has_value() && t->defined()) check_contig(*t, name);
+}
+// float4 / ushort4 accesses of the optimizer kernels
+void check_aligned(const Tensor& t, size_t bytes, const char* name) {
+  TORCH_CHECK(((uintptr_t)t.data_ptr() % bytes) == 0, name, " must be ", bytes, "-byte aligned");
+}
 bool same_dense(const Tensor& a, const Tensor& b) {
   if (a.numel() != b.numel()) return false;
   if (a.is_contiguous() && b.is_contiguous()) return true;
@@ -261,14 +273,18 @@ void binary_bwd(Tensor a, Tensor b, Tensor dc, optional<Tensor> da, optional<Ten
 }
 void cast(Tensor x, Tensor y) {
   TORCH_CHECK(x.numel() == y.numel());
+  check_contig(x, "cast: x"); check_contig(y, "cast: y");
   ffk::cast(dtcode(x), dtcode(y), x.data_ptr(), y.data_ptr(), x.numel(), cur_stream());
 }
 void dropout_fwd(Tensor x, Tensor y, Tensor mask, double rate, int64_t seed, int64_t offset) {
-  TORCH_CHECK(mask.scalar_type() == at::kByte && mask.numel() == x.numel());
+  TORCH_CHECK(mask.scalar_type() == at::kByte && mask.numel() == x.numel() && y.numel() == x.numel());
+  check_contig(x, "dropout_fwd: x"); check_contig(y, "dropout_fwd: y"); check_contig(mask, "dropout_fwd: mask");
   ffk::dropout_fwd(dtcode(x), x.data_ptr(), y.data_ptr(), mask.data_ptr<uint8_t>(), x.numel(), rate, seed, offset,
                    cur_stream());
 }
 void dropout_bwd(Tensor dy, Tensor mask, Tensor dx, double rate, bool acc) {
+  TORCH_CHECK(mask.scalar_type() == at::kByte && mask.numel() == dy.numel() && dx.numel() == dy.numel());
+  check_contig(dy, "dropout_bwd: dy"); check_contig(mask, "dropout_bwd: mask"); check_contig(dx, "dropout_bwd: dx");
   ffk::dropout_bwd(dtcode(dy), dy.data_ptr(), mask.data_ptr<uint8_t>(), dx.data_ptr(), dy.numel(), rate, acc,
                    cur_stream());
 }
@@ -324,34 +340,49 @@ void layernorm_bwd(Tensor dy, Tensor x, optional<Tensor> gamma, Tensor mean, Ten
                      ptr<float>(dsum), ws.data_ptr<float>(), rows, cols, acc, cur_stream(), (int)stage);
 }
 void softmax_fwd(Tensor x, Tensor y, int64_t rows, int64_t cols, double scale) {
-  TORCH_CHECK(x.numel() == rows * cols);
+  TORCH_CHECK(x.numel() == rows * cols && y.numel() == rows * cols);
+  check_contig(x, "softmax_fwd: x"); check_contig(y, "softmax_fwd: y");
   ffk::softmax_fwd(dtcode(x), x.data_ptr(), y.data_ptr(), rows, cols, scale, cur_stream());
 }
 void softmax_bwd(Tensor y, Tensor dy, Tensor dx, int64_t rows, int64_t cols, double scale, bool acc) {
+  TORCH_CHECK(y.numel() == rows * cols && dy.numel() == rows * cols && dx.numel() == rows * cols);
+  check_contig(y, "softmax_bwd: y"); check_contig(dy, "softmax_bwd: dy"); check_contig(dx, "softmax_bwd: dx");
   ffk::softmax_bwd(dtcode(y), y.data_ptr(), dy.data_ptr(), dx.data_ptr(), rows, cols, scale, acc, cur_stream());
 }
 void softmax_xent(Tensor logits, Tensor labels, optional<Tensor> loss, optional<Tensor> dlogits, int64_t rows,
                   int64_t cols, double gscale, optional<Tensor> acc3) {
   TORCH_CHECK(labels.scalar_type() == at::kInt && labels.numel() >= rows);
   TORCH_CHECK(!acc3 || (acc3->scalar_type() == at::kFloat && acc3->numel() >= 3));
+  check_contig(logits, "softmax_xent: logits"); check_contig(labels, "softmax_xent: labels");
+  check_contig(loss, "softmax_xent: loss"); check_contig(dlogits, "softmax_xent: dlogits");
   ffk::softmax_xent_fwd_bwd(dtcode(logits), logits.data_ptr(), labels.data_ptr<int>(), ptr<float>(loss),
                             ptr(dlogits), rows, cols, gscale, ptr<float>(acc3), cur_stream());
 }
 void xent_grad(Tensor probs, optional<Tensor> labels, optional<Tensor> onehot, Tensor dprobs, optional<Tensor> loss,
                int64_t rows, int64_t cols, double gscale, bool sparse) {
+  TORCH_CHECK(probs.numel() == rows * cols && dprobs.numel() == rows * cols);
+  check_contig(probs, "xent_grad: probs"); check_contig(dprobs, "xent_grad: dprobs");
+  check_contig(labels, "xent_grad: labels"); check_contig(onehot, "xent_grad: onehot");
+  check_contig(loss, "xent_grad: loss");
   ffk::xent_grad(dtcode(probs), probs.data_ptr(), ptr<int>(labels), ptr(onehot), dprobs.data_ptr(),
                  ptr<float>(loss), rows, cols, gscale, sparse, cur_stream());
 }
 void mse_grad(Tensor pred, Tensor label, Tensor dpred, optional<Tensor> loss, double gscale) {
-  TORCH_CHECK(pred.numel() == label.numel());
+  TORCH_CHECK(pred.numel() == label.numel() && dpred.numel() == pred.numel());
+  check_contig(pred, "mse_grad: pred"); check_contig(label, "mse_grad: label"); check_contig(dpred, "mse_grad: dpred");
   ffk::mse_grad(dtcode(pred), pred.data_ptr(), label.data_ptr(), dpred.data_ptr(), ptr<float>(loss), pred.numel(),
                 gscale, cur_stream());
 }
 void metrics_classify(Tensor probs, Tensor labels, int64_t rows, int64_t cols, Tensor out) {
+  TORCH_CHECK(probs.numel() == rows * cols && labels.numel() >= rows && out.numel() >= 3);
+  check_contig(probs, "metrics_classify: probs"); check_contig(labels, "metrics_classify: labels");
+  check_contig(out, "metrics_classify: out");
   ffk::metrics_classify(dtcode(probs), probs.data_ptr(), labels.data_ptr<int>(), rows, cols, out.data_ptr<float>(),
                         cur_stream());
 }
 void reduce_rows(Tensor x, Tensor y, int64_t outer, int64_t red, int64_t inner, bool mean) {
+  TORCH_CHECK(x.numel() == outer * red * inner && y.numel() == outer * inner);
+  check_contig(x, "reduce_rows: x"); check_contig(y, "reduce_rows: y");
   ffk::reduce_rows(dtcode(x), x.data_ptr(), y.data_ptr(), outer, red, inner, mean, cur_stream());
 }
 void sgd_sparse_rows(Tensor idx, Tensor mark, Tensor master, Tensor grad, optional<Tensor> lowp, double lr) {
@@ -372,8 +403,17 @@ void sgd_update(Tensor master, Tensor grad, optional<Tensor> mom, optional<Tenso
   TORCH_CHECK(master.scalar_type() == at::kFloat && grad.scalar_type() == at::kFloat);
   TORCH_CHECK(master.numel() == grad.numel());
   if (momentum > 0) TORCH_CHECK(mom.has_value() && mom->numel() == master.numel());
-  if (lowp.has_value() && lowp->defined())
+  check_contig(master, "sgd_update: master"); check_contig(grad, "sgd_update: grad");
+  check_aligned(master, 16, "sgd_update: master"); check_aligned(grad, 16, "sgd_update: grad");
+  if (mom.has_value() && mom->defined()) {
+    check_contig(*mom, "sgd_update: mom");
+    check_aligned(*mom, 16, "sgd_update: mom");
+  }
+  if (lowp.has_value() && lowp->defined()) {
     TORCH_CHECK(lowp->scalar_type() == at::kBFloat16 && lowp->numel() == master.numel());
+    check_contig(*lowp, "sgd_update: lowp");
+    check_aligned(*lowp, 8, "sgd_update: lowp");
+  }
   ffk::sgd_update(master.data_ptr<float>(), grad.data_ptr<float>(), ptr<float>(mom), ptr(lowp), master.numel(), lr,
                   momentum, nesterov, wd, gscale, cur_stream(), (int)max_blocks);
 }
@@ -382,31 +422,48 @@ void adam_update(Tensor master, Tensor grad, Tensor m, Tensor v, optional<Tensor
   if (alpha_dev) TORCH_CHECK(alpha_dev->scalar_type() == at::kFloat && alpha_dev->numel() == 1 && alpha_dev->is_cuda(),
                              "adam_update: alpha_dev must be a one-element fp32 device tensor");
   TORCH_CHECK(master.numel() == grad.numel() && m.numel() == master.numel() && v.numel() == master.numel());
-  if (lowp.has_value() && lowp->defined())
+  check_contig(master, "adam_update: master"); check_contig(grad, "adam_update: grad");
+  check_contig(m, "adam_update: m"); check_contig(v, "adam_update: v");
+  check_aligned(master, 16, "adam_update: master"); check_aligned(grad, 16, "adam_update: grad");
+  check_aligned(m, 16, "adam_update: m"); check_aligned(v, 16, "adam_update: v");
+  if (lowp.has_value() && lowp->defined()) {
     TORCH_CHECK(lowp->scalar_type() == at::kBFloat16 && lowp->numel() == master.numel());
+    check_contig(*lowp, "adam_update: lowp");
+    check_aligned(*lowp, 8, "adam_update: lowp");
+  }
   ffk::adam_update(master.data_ptr<float>(), grad.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
                    ptr(lowp), master.numel(), alpha_t, b1, b2, wd, eps, gscale, cur_stream(), (int)max_blocks,
                    alpha_dev ? alpha_dev->data_ptr<float>() : nullptr);
 }
 void embedding_fwd(Tensor idx, Tensor table, Tensor out, int64_t n_rows, int64_t bag, int64_t dim, bool avg) {
   TORCH_CHECK(idx.numel() == n_rows * bag && out.numel() == n_rows * dim && table.size(-1) == dim);
+  check_contig(idx, "embedding_fwd: idx"); check_contig(table, "embedding_fwd: table");
+  check_contig(out, "embedding_fwd: out");
   const bool i64 = idx.scalar_type() == at::kLong;
   ffk::embedding_fwd(dtcode(table), i64, idx.data_ptr(), table.data_ptr(), out.data_ptr(), n_rows, bag, dim,
                      table.numel() / dim, avg, cur_stream());
 }
 void embedding_bwd(Tensor idx, Tensor dout, Tensor dtable, int64_t n_rows, int64_t bag, int64_t dim, bool avg) {
   TORCH_CHECK(dtable.scalar_type() == at::kFloat && dout.numel() == n_rows * dim);
+  TORCH_CHECK(idx.numel() == n_rows * bag && dtable.size(-1) == dim);
+  check_contig(idx, "embedding_bwd: idx"); check_contig(dout, "embedding_bwd: dout");
+  check_contig(dtable, "embedding_bwd: dtable");
   const bool i64 = idx.scalar_type() == at::kLong;
   ffk::embedding_bwd(dtcode(dout), i64, idx.data_ptr(), dout.data_ptr(), dtable.data_ptr<float>(), n_rows, bag, dim,
                      dtable.numel() / dim, avg, cur_stream());
 }
 void init_uniform(Tensor out, double lo, double hi, int64_t seed, int64_t offset) {
+  check_contig(out, "init_uniform: out");
   ffk::init_uniform(dtcode(out), out.data_ptr(), out.numel(), lo, hi, seed, offset, cur_stream());
 }
 void init_normal(Tensor out, double mean, double stdv, int64_t seed, int64_t offset) {
+  check_contig(out, "init_normal: out");
   ffk::init_normal(dtcode(out), out.data_ptr(), out.numel(), mean, stdv, seed, offset, cur_stream());
 }
-void fill(Tensor out, double v) { ffk::fill(dtcode(out), out.data_ptr(), out.numel(), v, cur_stream()); }
+void fill(Tensor out, double v) {
+  check_contig(out, "fill: out");
+  ffk::fill(dtcode(out), out.data_ptr(), out.numel(), v, cur_stream());
+}
 void slab_sum(Tensor slabs, Tensor out, int64_t S, double beta) {
   TORCH_CHECK(slabs.scalar_type() == at::kFloat && out.scalar_type() == at::kFloat && slabs.is_contiguous() &&
               out.is_contiguous());

@@ -14,11 +14,13 @@ __device__ __forceinline__ float unary_f(int op, float x, float s) {
     case U_RELU: return fmaxf(x, 0.f);
     case U_SIGMOID: return 1.f / (1.f + __expf(-x));
     case U_TANH: return tanhf(x);
-    case U_ELU: return x > 0.f ? x : (__expf(x) - 1.f);
+    case U_ELU: return x > 0.f ? x : expm1f(x);  // not __expf(x) - 1: that cancels for small |x|
     case U_GELU: return 0.5f * x * (1.f + fast_erf(x * 0.70710678118654752f));
     case U_EXP: return __expf(x);
-    case U_SIN: return __sinf(x);
-    case U_COS: return __cosf(x);
+    // sinf / cosf, not the hardware approximations: their ~1e-6 absolute error is a relative
+    // error of 1e-3 and more near the zero crossings
+    case U_SIN: return sinf(x);
+    case U_COS: return cosf(x);
     case U_RSQRT: return rsqrtf(x);
     case U_POW: return powf(x, s);
     case U_IDENTITY: return x;
@@ -46,8 +48,8 @@ __device__ __forceinline__ float unary_df(int op, float x, float y, float s) {
       return cdf + x * 0.3989422804014327f * __expf(-0.5f * x * x);
     }
     case U_EXP: return y;
-    case U_SIN: return __cosf(x);
-    case U_COS: return -__sinf(x);
+    case U_SIN: return cosf(x);
+    case U_COS: return -sinf(x);
     case U_RSQRT: return -0.5f * y * y * y;
     case U_POW: return s * powf(x, s - 1.f);
     case U_IDENTITY: return 1.f;
@@ -65,12 +67,13 @@ __device__ __forceinline__ float unary_df(int op, float x, float y, float s) {
 }
 
 // OP >= 0: the op as a compile-time constant (ReLU, the CNN zoo's), -1: the run-time `op_rt` (a
-// per-element switch over every op otherwise sits in the loop)
-template <typename T, int OP = -1>
+// per-element switch over every op otherwise sits in the loop). VEC = false: no 16-B accesses, every
+// element goes through the scalar loop (a pointer off a 16-B boundary, e.g. a view into a buffer)
+template <typename T, int OP = -1, bool VEC = true>
 __global__ void unary_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t n, int op_rt, float s) {
   const int op = OP >= 0 ? OP : op_rt;
   constexpr int V = 16 / sizeof(T);
-  const int64_t nv = n / V;
+  const int64_t nv = VEC ? n / V : 0;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += stride) {
     float v[V];
@@ -84,13 +87,13 @@ __global__ void unary_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, int
 }
 
 // OP = U_RELU: the gradient needs only y (y > 0 exactly where x > 0), so x is not read — a third
-// less traffic than the generic form
-template <typename T, int OP = -1>
+// less traffic than the generic form. VEC as in unary_fwd_kernel
+template <typename T, int OP = -1, bool VEC = true>
 __global__ void unary_bwd_kernel(const T* __restrict__ x, const T* __restrict__ y, const T* __restrict__ dy,
                                  T* __restrict__ dx, int64_t n, int op_rt, float s, int accumulate) {
   const int op = OP >= 0 ? OP : op_rt;
   constexpr int V = 16 / sizeof(T);
-  const int64_t nv = n / V;
+  const int64_t nv = VEC ? n / V : 0;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += stride) {
     float xv[V], yv[V], g[V], o[V];
@@ -693,9 +696,17 @@ __global__ void bias_act_fwd_kernel(const bf16_t* __restrict__ z, const void* __
     else { using T = float; __VA_ARGS__; }              \
   } while (0)
 
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
 void unary_fwd(int dt, const void* x, void* y, int64_t n, int op, float s, hipStream_t st) {
   if (n == 0) return;
   FFK_DT_DISPATCH(dt, {
+    if (!(aligned16(x) && aligned16(y))) {  // 16-B accesses need 16-B aligned pointers: scalar form
+      const dim3 grid(ew_grid(n, 256));
+      if (op == U_RELU) hipLaunchKernelGGL((unary_fwd_kernel<T, U_RELU, false>), grid, dim3(256), 0, st, (const T*)x, (T*)y, n, op, s);
+      else hipLaunchKernelGGL((unary_fwd_kernel<T, -1, false>), grid, dim3(256), 0, st, (const T*)x, (T*)y, n, op, s);
+      return;
+    }
     const dim3 grid(ew_grid(n / (16 / sizeof(T)) + 1, 256));
     if (op == U_RELU) hipLaunchKernelGGL((unary_fwd_kernel<T, U_RELU>), grid, dim3(256), 0, st, (const T*)x, (T*)y, n, op, s);
     else hipLaunchKernelGGL(unary_fwd_kernel<T>, grid, dim3(256), 0, st, (const T*)x, (T*)y, n, op, s);
@@ -705,6 +716,16 @@ void unary_bwd(int dt, const void* x, const void* y, const void* dy, void* dx, i
                int accumulate, hipStream_t st) {
   if (n == 0) return;
   FFK_DT_DISPATCH(dt, {
+    if (!(aligned16(x) && aligned16(y) && aligned16(dy) && aligned16(dx))) {
+      const dim3 grid(ew_grid(n, 256));
+      if (op == U_RELU)
+        hipLaunchKernelGGL((unary_bwd_kernel<T, U_RELU, false>), grid, dim3(256), 0, st, (const T*)x, (const T*)y,
+                           (const T*)dy, (T*)dx, n, op, s, accumulate);
+      else
+        hipLaunchKernelGGL((unary_bwd_kernel<T, -1, false>), grid, dim3(256), 0, st, (const T*)x, (const T*)y,
+                           (const T*)dy, (T*)dx, n, op, s, accumulate);
+      return;
+    }
     const dim3 grid(ew_grid(n / (16 / sizeof(T)) + 1, 256));
     if (op == U_RELU)
       hipLaunchKernelGGL((unary_bwd_kernel<T, U_RELU>), grid, dim3(256), 0, st, (const T*)x, (const T*)y,

@@ -21,6 +21,7 @@ __device__ __forceinline__ void row_stats(const T* __restrict__ xr, int cols, fl
   s = 0.f;
   for (int c = lane; c < cols; c += 64) {
     const float v = Cvt<T>::to_f(xr[c]) * scale;
+    if (v == -INFINITY) continue;  // exp(-inf) = 0: a masked element leaves (m, s) alone (v - m would be NaN at m = -inf)
     if (v > m) { s = s * __expf(m - v) + 1.f; m = v; }
     else s += __expf(v - m);
   }
@@ -114,6 +115,7 @@ __global__ void __launch_bounds__(256) softmax_xent_kernel(const T* __restrict__
     float m = -INFINITY, s = 0.f;
     int bi = 0x7fffffff;
     row_visit(xr, cols, lane, [&](int c, float v) {
+      if (v == -INFINITY) return;  // as in row_stats: a masked logit contributes 0
       if (v > m) { s = s * __expf(m - v) + 1.f; m = v; bi = c; }
       else s += __expf(v - m);
     });
@@ -207,7 +209,8 @@ __global__ void __launch_bounds__(256) softmax_xent_reg_kernel(const bf16_t* __r
       const int d = tid + i * 256;
       v[i] = d < ndw ? xr[d] : 0u;
     }
-    // pass 1 (registers): max with first-index argmax, then sum of exp
+    // pass 1 (registers): max with first-index argmax, then sum of exp (two sweeps: the sum runs
+    // only once this thread's max is finite, so a -inf logit adds exp(-inf - m) = 0, never NaN)
     float m = -INFINITY;
     int bi = 0x7fffffff;
 #pragma unroll

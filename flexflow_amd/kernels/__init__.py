@@ -1045,6 +1045,7 @@ def layernorm_bwd(dy2d, xs2d, gamma, mean, rstd, dgamma, dbeta, dres=None, dsum=
 # ----------------------------------------------------------------------------- softmax/loss
 def softmax_fwd(x2d):
     if native(x2d):
+        x2d = x2d.contiguous()  # the kernels index rows flat; empty_like would keep a transpose's strides
         y = torch.empty_like(x2d)
         ext().softmax_fwd(x2d, y, x2d.shape[0], x2d.shape[1], 1.0)
         return y
@@ -1053,6 +1054,7 @@ def softmax_fwd(x2d):
 
 def softmax_bwd(y2d, dy2d):
     if native(y2d):
+        y2d, dy2d = y2d.contiguous(), dy2d.contiguous()
         dx = torch.empty_like(dy2d)
         ext().softmax_bwd(y2d, dy2d, dx, y2d.shape[0], y2d.shape[1], 1.0, False)
         return dx
@@ -1065,10 +1067,11 @@ def xent_grad(probs2d, labels, onehot, gscale, sparse):
     """(p - y)*gscale and per-row CE; labels int32 [rows] (sparse) or onehot [rows, C]."""
     rows, cols = probs2d.shape
     if native(probs2d):
+        probs2d = probs2d.contiguous()
         d = torch.empty_like(probs2d)
         loss = torch.empty(rows, device=probs2d.device, dtype=torch.float32)
-        ext().xent_grad(probs2d, labels if sparse else None, None if sparse else onehot, d, loss, rows, cols,
-                        gscale, sparse)
+        ext().xent_grad(probs2d, labels.contiguous() if sparse else None,
+                        None if sparse else onehot.contiguous(), d, loss, rows, cols, gscale, sparse)
         return d, loss
     p = probs2d.float()
     t = F.one_hot(labels.long(), cols).float() if sparse else onehot.float()
@@ -1081,9 +1084,10 @@ def softmax_xent(logits2d, labels, gscale, acc3=None):
     """(dlogits, per-row CE) of softmax + sparse CE; acc3 (fp32 [3]) += {correct, sum CE, rows}."""
     rows, cols = logits2d.shape
     if native(logits2d):
+        logits2d = logits2d.contiguous()
         d = torch.empty_like(logits2d)
         loss = torch.empty(rows, device=logits2d.device, dtype=torch.float32)
-        ext().softmax_xent(logits2d, labels, loss, d, rows, cols, gscale, acc3)
+        ext().softmax_xent(logits2d, labels.contiguous(), loss, d, rows, cols, gscale, acc3)
         return d, loss
     lf = logits2d.float()
     p = torch.softmax(lf, -1)
@@ -1100,9 +1104,10 @@ def softmax_xent(logits2d, labels, gscale, acc3=None):
 
 def mse_grad(pred, label, gscale):
     if native(pred):
+        pred = pred.contiguous()
         d = torch.empty_like(pred)
         loss = torch.zeros(1, device=pred.device, dtype=torch.float32)
-        ext().mse_grad(pred.contiguous(), label.contiguous().to(pred.dtype), d, loss, gscale)
+        ext().mse_grad(pred, label.to(pred.dtype).contiguous(), d, loss, gscale)
         return d, loss
     diff = pred.float() - label.float()
     return (diff * gscale).to(pred.dtype), (diff * diff).sum().reshape(1)
@@ -1294,8 +1299,9 @@ def dropout_fwd(x, rate, seed, offset):
 
 def dropout_bwd(dy, mask, rate):
     if native(dy):
+        dy = dy.contiguous()  # the mask is in row-major order (dropout_fwd)
         dx = torch.empty_like(dy)
-        ext().dropout_bwd(dy.contiguous(), mask, dx, float(rate), False)
+        ext().dropout_bwd(dy, mask, dx, float(rate), False)
         return dx
     return (dy * mask.view(dy.shape).to(dy.dtype) / (1 - rate)).to(dy.dtype)
 
@@ -1309,7 +1315,7 @@ def embedding_fwd(idx, table, bag, avg):
         ii = idx.contiguous()
         if ii.dtype not in (torch.int32, torch.int64):
             ii = ii.to(torch.int64)
-        ext().embedding_fwd(ii, table, out, n, bag, dim, avg)
+        ext().embedding_fwd(ii, table.contiguous(), out, n, bag, dim, avg)
         return out
     ii = idx.long().reshape(n, bag)
     valid = (ii >= 0) & (ii < table.shape[0])  # ids owned by another vocab shard contribute 0
@@ -1476,7 +1482,7 @@ def fill(out, v):
 
 def metrics_classify(probs2d, labels, acc3):
     if native(probs2d):
-        ext().metrics_classify(probs2d, labels, probs2d.shape[0], probs2d.shape[1], acc3)
+        ext().metrics_classify(probs2d.contiguous(), labels.contiguous(), probs2d.shape[0], probs2d.shape[1], acc3)
         return
     p = probs2d.float()
     lab = labels.long()

@@ -1135,7 +1135,9 @@ class Executor:
         for a, b, _, _ in holes:
             if a > lo:
                 optimizer.step_range(ar, lo, a)
-            lo = max(lo, b)
+            # resume at the next entry's offset (WeightArena.add pads every entry to 8 elements): the
+            # update kernels take 16-byte aligned ranges, and the padding holds no weights
+            lo = max(lo, (b + 7) // 8 * 8)
         if lo < ar.size:
             optimizer.step_range(ar, lo, ar.size)
         cleared = []

@@ -1009,27 +1009,28 @@ def test_gemm_f32(ffC, a_k, b_k, M, N, K, batch):
     assert _rel(C2, torch.nn.functional.gelu(z)) < 1e-5
 
 
+@pytest.mark.parametrize("S", [24, 80])  # 80: a causal row spans lanes that see only masked (-inf) scores
 @pytest.mark.parametrize("causal", [False, True])
 @pytest.mark.parametrize("fused", [True, False])
-def test_attention_f32_path(causal, fused):
+def test_attention_f32_path(causal, fused, S):
     """--dtype fp32 attention runs our kernels (f32 MFMA GEMMs + mask + softmax), not einsum: the op's
     forward and input gradients against the fp32 autograd reference."""
     from flexflow_amd.core import DataType, FFConfig, FFModel, SGDOptimizer
     cfg = FFConfig(["--dtype", "fp32", "--no-hip-graphs"])
     cfg.batch_size = 2
     ff = FFModel(cfg)
-    x = ff.create_tensor([2, 24, 64], DataType.DT_FLOAT)
+    x = ff.create_tensor([2, S, 64], DataType.DT_FLOAT)
     if fused:
         y = ff.multihead_attention(x, x, x, 64, 4, causal=causal)
     else:
-        x2 = ff.create_tensor([2, 24, 64], DataType.DT_FLOAT)
+        x2 = ff.create_tensor([2, S, 64], DataType.DT_FLOAT)
         y = ff.multihead_attention(x, x2, x2, 64, 4, causal=causal)
     ff.optimizer = SGDOptimizer(ff, 0.0)
     ff.compile()
     L = [l for l in ff.layers if l.op_type.name == "OP_MULTIHEAD_ATTENTION"][0]
     assert L.attrs["fused_qkv"] == fused
     rng = torch.Generator().manual_seed(0)
-    xv = torch.randn(2, 24, 64, generator=rng)
+    xv = torch.randn(2, S, 64, generator=rng)
     x.set_tensor(ff, xv.numpy())
     if not fused:
         x2.set_tensor(ff, xv.numpy())
@@ -1041,17 +1042,18 @@ def test_attention_f32_path(causal, fused):
     W = {w.short_name: torch.from_numpy(np.asarray(w.get_weights(ff))).double() for w in L.weights}
     xr = xv.double()
     if fused:
-        qkv = xr.reshape(48, 64) @ W["qkv_weight"].reshape(-1, 64).t() + W["qkv_bias"].reshape(-1)
-        qkv = qkv.view(2, 24, 3, 4, 16)
+        qkv = xr.reshape(2 * S, 64) @ W["qkv_weight"].reshape(-1, 64).t() + W["qkv_bias"].reshape(-1)
+        qkv = qkv.view(2, S, 3, 4, 16)
         q, k, v = qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2]
     else:
-        proj = lambda n: (xr.reshape(48, 64) @ W[f"{n}_weight"].reshape(-1, 64).t() + W[f"{n}_bias"].reshape(-1)).view(2, 24, 4, 16)  # noqa: E731
+        proj = lambda n: (xr.reshape(2 * S, 64) @ W[f"{n}_weight"].reshape(-1, 64).t() + W[f"{n}_bias"].reshape(-1)).view(2, S, 4, 16)  # noqa: E731
         q, k, v = proj("q"), proj("k"), proj("v")
     s = torch.einsum("bqhd,bkhd->bhqk", q, k) / math.sqrt(16)
     if causal:
-        s = s.masked_fill(torch.ones(24, 24, dtype=torch.bool).triu(1), float("-inf"))
-    o = torch.einsum("bhqk,bkhd->bqhd", torch.softmax(s, -1), v).reshape(48, 64)
-    ref = (o @ W["o_weight"].reshape(64, 64).t() + W["o_bias"]).view(2, 24, 64)
+        s = s.masked_fill(torch.ones(S, S, dtype=torch.bool).triu(1), float("-inf"))
+    o = torch.einsum("bhqk,bkhd->bqhd", torch.softmax(s, -1), v).reshape(2 * S, 64)
+    ref = (o @ W["o_weight"].reshape(64, 64).t() + W["o_bias"]).view(2, S, 64)
+    assert torch.isfinite(out).all()
     assert _rel(out, ref) < 1e-5
 
 
