@@ -20,6 +20,7 @@
 #include "common.h"
 #include "ops.h"
 #include "attention.h"
+#include <utility>
 
 namespace ffk {
 
@@ -70,6 +71,15 @@ struct TileStage {
       const int id = tid + i * NTH;
       const int row = id / (D / 8), c = id % (D / 8);
       *reinterpret_cast<uint4*>(lds + aoff<D>(row, c * 8)) = r[i];
+    }
+  }
+  template <class F>
+  __device__ __forceinline__ void store(char* lds, int tid, F off) {  // image given by off(row, col)
+#pragma unroll
+    for (int i = 0; i < CH; ++i) {
+      const int id = tid + i * NTH;
+      const int row = id / (D / 8), c = id % (D / 8);
+      *reinterpret_cast<uint4*>(lds + off(row, c * 8)) = r[i];
     }
   }
 };
@@ -547,11 +557,13 @@ __global__ void attn_bwd_pre_kernel(AttnArgs a) {
   }
 }
 
-// dS^T image [key][64 queries] (128-B rows): byte offset of (key row, query q), q % 4 == 0. The
-// 8-B unit index is XORed with f(row) = row[2:0] | (row[1]^row[3])<<3 — found by exhaustive search
-// over linear XOR maps to be conflict-free both for the 8-B writes (16 consecutive key rows per
-// lane group, banks mod 32) and for the ds_read_b64_tr_b16 reads of the dQ stage (banks mod 64);
-// the unswizzled image cost ~57 % extra LDS cycles (SQ_LDS_BANK_CONFLICT, profiles/attn_pmc_r1.txt).
+// dS^T image [key][64 queries] (128-B rows) of attn_bwd_kernel: byte offset of (key row, query q),
+// q % 4 == 0. The 8-B unit index is XORed with f(row) = row[2:0] | (row[1]^row[3])<<3 — found by
+// exhaustive search over linear XOR maps to be conflict-free both for the 8-B writes (16
+// consecutive key rows per lane group, banks mod 32) and for the ds_read_b64_tr_b16 reads of that
+// kernel's 32x32 dQ stage (banks mod 64); the unswizzled image cost ~57 % extra LDS cycles
+// (SQ_LDS_BANK_CONFLICT, profiles/attn_pmc_r1.txt). attn_bwd1b_kernel's 16x16x32 dQ stage reads
+// other rows per instruction and has images of its own (dst1b_off, k1b_off).
 // Workgroup barrier that orders LDS only: __syncthreads() also waits vmcnt(0), which here would
 // stall every q-tile on the dQ partial stores (and on the next tile's prefetch) for a full
 // memory round trip.
@@ -564,6 +576,83 @@ __device__ __forceinline__ void lds_barrier() {
 __device__ __forceinline__ int dst_off(int row, int q) {
   const int f = (row & 7) | ((((row >> 1) ^ (row >> 3)) & 1) << 3);
   return row * 128 + (((q >> 2) ^ f) << 3) + (q & 3) * 2;
+}
+
+// attn_bwd1b_kernel's LDS images. Its dQ stage runs 16x16x32 MFMAs whose ds_read_b64_tr_b16 take,
+// per half-wave, key rows 32 ks + 8 G + qi (+ 4) (G = 0..1 or 2..3, qi = 0..3) at four 8-B units:
+// dst_off's XOR does not separate row bits 1 and 3 of that set, nor does aswz for the K rows, and
+// both reads took 4 LDS array cycles instead of 2 (23 % of the kernel's LDS cycles, measured and
+// modelled: scripts/lds_bank_model.py, docs/PERFORMANCE.md round 7).
+//  * dS^T image: 8-B unit index XOR f(row) = b0 | b2<<1 | b1<<2 | b3<<3 (b_i = row bit i): conflict
+//    free for the 8-B writes of 16 consecutive key rows and for the dQ stage's transposed reads;
+//  * K image (read by the dQ stage and once, as b128 fragments, by the prologue): 16-B chunk index
+//    XOR b1<<1 | b3<<2 | b4.
+__device__ __forceinline__ int dst1b_off(int row, int q) {
+  const int f = (row & 1) | (((row >> 2) & 1) << 1) | (((row >> 1) & 1) << 2) | (((row >> 3) & 1) << 3);
+  return row * 128 + (((q >> 2) ^ f) << 3) + (q & 3) * 2;
+}
+__device__ __forceinline__ int k1b_off(int row, int col) {
+  const int x = (((row >> 1) & 1) << 1) | (((row >> 3) & 1) << 2) | ((row >> 4) & 1);
+  return row * 128 + (((col >> 3) ^ x) << 4) + ((col & 7) << 1);
+}
+
+// LDS reads of attn_bwd1b_kernel's Q / dO tile buffers as inline asm. hipcc puts an s_waitcnt
+// vmcnt(0) in front of any LDS read it sees that may alias an LDS-DMA still in flight, which
+// drained the prefetch of tile t+1 at the top of tile t. It neither sees these reads nor counts
+// them: each destination is named by an lds_wait<N> before its first use, N = the number of these
+// asm reads issued after it (LDS operations return in order; reads hipcc issues in between only
+// make the wait stricter, and its own counted waits stay valid for the same reason).
+// Precondition: between a read and its lds_wait hipcc must not copy or spill the destination (it
+// considers the register written when the asm statement ends). Naming the destination "+v" in the
+// wait pins the order, not the register allocation, and the kernel uses all 256 VGPRs — so after
+// every change to the kernel the device assembly has to show no scratch access and no v_mov of a
+// read's destination ahead of its wait (scripts/lab/asm_spills.py; part of the invariant below).
+template <int OFF>
+__device__ __forceinline__ bf16x8 lds_b128(unsigned a) {
+  bf16x8 r;
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(a), "n"(OFF));
+  return r;
+}
+template <int OFF>
+__device__ __forceinline__ f32x4 lds_f128(unsigned a) {
+  f32x4 r;
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(a), "n"(OFF));
+  return r;
+}
+template <int OFF>
+__device__ __forceinline__ v4s lds_tr(unsigned a) {
+  v4s r;
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(a), "n"(OFF));
+  return r;
+}
+template <int N, class T>
+__device__ __forceinline__ void lds_wait(T& a) {
+  asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(a) : "n"(N));
+}
+template <int N, class T>
+__device__ __forceinline__ void lds_wait(T& a, T& b) {
+  asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N));
+}
+template <int N, class T>
+__device__ __forceinline__ void lds_wait(T& a, T& b, T& c, T& d) {
+  asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(N));
+}
+template <int N, class T, class U>  // `after` is not loaded: naming it orders the wait behind its producers
+__device__ __forceinline__ void lds_wait(T& a, T& b, T& c, T& d, U& after) {
+  asm volatile("s_waitcnt lgkmcnt(%5)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(after) : "n"(N));
+}
+__device__ __forceinline__ bf16x8 join8(v4s lo, v4s hi) {
+  return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+}
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): loop indices as constants, for
+// the immediate offsets of the asm reads
+template <int... I, class F>
+__device__ __forceinline__ void static_for_impl(std::integer_sequence<int, I...>, F&& f) {
+  (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+  static_for_impl(std::make_integer_sequence<int, N>{}, f);
 }
 
 __device__ __forceinline__ unsigned pack_bf2(float x, float y) {
@@ -944,15 +1033,29 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) attn_bwd_kernel(AttnArgs a, i
 // not depend on its S / dP work of the same iteration. dQ^T runs on 16x16x32 MFMAs: 16 (d x query)
 // tiles of 16 x 16, two per wave sharing the K^T operand, each over all KB keys, so no wave hands
 // a partial sum to another (no exchange buffer: the second dS^T image takes its LDS).
+// The DMA of tile t+1, issued at the top of iteration t, stays in flight until finish() at the end
+// of the iteration: the tile buffers are read only through the asm helpers above, and the K block
+// and the dS^T images are arrays of their own, so hipcc has no LDS read to guard with a vmcnt(0)
+// of its own. What this rests on:
+//  * tile t is read only after the finish() of iteration t-1 (its vmcnt(0), then the barrier);
+//  * the DMA for tile t+1 targets the buffer last read in iteration t-1, which that barrier released;
+//  * the lse2 / delta rows are wave 7's DMA, covered by wave 7's own vmcnt(0) before the barrier;
+//  * the dQ global stores stay behind the barrier, and the running-sum loads of prefetch(t) are
+//    first used there (dq_store), ahead of the first store: hipcc's waits for them (vmcnt(1) /
+//    vmcnt(0); one vmcnt(0) in the masked form) sit right behind finish()'s vmcnt(0) and the
+//    barrier, with nothing in flight, so no wait in the iteration covers a DMA or a store early;
+//  * the loop has no scratch access (a reload would bring a vmcnt(0) of its own) and no copy of an
+//    asm read's destination ahead of its lds_wait.
 template <bool MASK, bool CHAIN, bool SB = false>
 __global__ void __launch_bounds__(512, 1) attn_bwd1b_kernel(AttnArgs a, int nkb, int pass) {
   constexpr int D = 64, NW = 8, NT = 64 * NW, QT = 64, KB = 32 * NW, QB = QT * D * 2;
   constexpr int TILE = 2 * QB + 2 * QT * 4;  // Q tile, dO tile, lse2, delta
   constexpr int DS = KB * QT * 2;            // one dS^T image [KB][QT]
   static_assert(2 * TILE >= KB * D * 2, "tile buffers stage the V block and the dV image");
-  __shared__ __attribute__((aligned(16))) char smem[2 * TILE + KB * D * 2 + 2 * DS];
-  char* k_l = smem + 2 * TILE;
-  char* ds0 = k_l + KB * D * 2;
+  // three arrays, so that hipcc knows the K block and dS^T accesses cannot alias the tile DMA
+  __shared__ __attribute__((aligned(16))) char smem[2 * TILE];      // the two tile buffers
+  __shared__ __attribute__((aligned(16))) char k_l[KB * D * 2];     // K block image (k1b_off)
+  __shared__ __attribute__((aligned(16))) char ds0[2 * DS];         // the two dS^T images (dst1b_off)
 
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), h = lane >> 5;
   const bool late = a.stagger && __builtin_amdgcn_readfirstlane(wave) >= NW / 2;
@@ -984,14 +1087,14 @@ __global__ void __launch_bounds__(512, 1) attn_bwd1b_kernel(AttnArgs a, int nkb,
     TileStage<D, KB, NT> sk, sv;
     sk.load(K, a.k_ss, kb0, MASK ? a.Sk : 1 << 30, tid);
     sv.load(V, a.v_ss, kb0, MASK ? a.Sk : 1 << 30, tid);
-    sk.store(k_l, tid);
+    sk.store(k_l, tid, [](int row, int col) { return k1b_off(row, col); });
     sv.store(smem, tid);
   }
   __syncthreads();
 #pragma unroll
   for (int s = 0; s < D / 16; ++s) {
     const int row = wave * 32 + (lane & 31);
-    kf[s] = *reinterpret_cast<const bf16x8*>(k_l + aoff<D>(row, 16 * s + 8 * h));
+    kf[s] = *reinterpret_cast<const bf16x8*>(k_l + k1b_off(row, 16 * s + 8 * h));
     vf[s] = *reinterpret_cast<const bf16x8*>(smem + aoff<D>(row, 16 * s + 8 * h));
   }
   f32x16 dk[D / 32], dv[D / 32];
@@ -1001,6 +1104,23 @@ __global__ void __launch_bounds__(512, 1) attn_bwd1b_kernel(AttnArgs a, int nkb,
   const int qt_begin = (MASK && a.causal) ? kb0 / QT : 0;
   const int nqt = (a.Sq + QT - 1) / QT;
   const int G = lane >> 4, qi = (lane & 15) >> 2, pi = lane & 3, l16 = lane & 15;
+  // LDS byte addresses of this lane's asm reads in the buffer of the tile s_tile runs next (the
+  // 32-row half, Q / dO and the lse2 / delta row are immediate offsets: aswz ignores row bit 5).
+  // Tiles alternate between the buffers from qt_begin on, so s_tile ends by moving these to the
+  // other buffer.
+  unsigned sa[D / 16], va[D / 32][2][2];
+  int tile_step = (qt_begin & 1) ? -TILE : TILE;
+  const unsigned tile0 = (unsigned)(uintptr_t)smem + (qt_begin & 1) * TILE;
+  unsigned la = tile0 + 16 * h;
+#pragma unroll
+  for (int s = 0; s < D / 16; ++s) sa[s] = tile0 + aoff<D>(lane & 31, 16 * s + 8 * h);
+#pragma unroll
+  for (int dt = 0; dt < D / 32; ++dt)
+#pragma unroll
+    for (int s2 = 0; s2 < 2; ++s2)
+#pragma unroll
+      for (int hi = 0; hi < 2; ++hi)
+        va[dt][s2][hi] = tile0 + aoff<D>(16 * s2 + 4 * h + qi + 8 * hi, dt * 32 + 16 * (G & 1) + 4 * pi);
   auto dma_rows = [&](int t) {
     char* tb = smem + (t & 1) * TILE;
     dma_tile<D, NW>(rq, tb, a.q_ss, t * QT, wave, lane);
@@ -1037,35 +1157,39 @@ __global__ void __launch_bounds__(512, 1) attn_bwd1b_kernel(AttnArgs a, int nkb,
   // hook(stage): stage 2 qt after the S / dP MFMAs, 2 qt + 1 after the dV / dK MFMAs of half qt
   auto s_tile = [&](int t, auto hook) {
     const int qbase = t * QT;
-    const char* tb = smem + (t & 1) * TILE;
-    const char* q_l = tb;
-    const char* do_l = tb + QB;
-    const float* lse_l = reinterpret_cast<const float*>(tb + 2 * QB);
-    const float* dl_l = lse_l + QT;
     char* ds_l = ds0 + (t & 1) * DS;
-#pragma unroll
-    for (int qt = 0; qt < 2; ++qt) {
+    static_for<2>([&](auto qt_) {
+      constexpr int qt = decltype(qt_)::value;
+      constexpr int QO = qt * 32 * D * 2;           // the 32-query half inside the Q / dO tile
+      constexpr int LO = 2 * QB + qt * 32 * 4;      // and inside the lse2 row; delta: + QT * 4
       f32x16 sacc = f32x16{}, pacc = f32x16{};
-#pragma unroll
-      for (int s = 0; s < D / 16; ++s) {
-        const int row = 32 * qt + (lane & 31);
-        const bf16x8 qa = *reinterpret_cast<const bf16x8*>(q_l + aoff<D>(row, 16 * s + 8 * h));
-        const bf16x8 da = *reinterpret_cast<const bf16x8*>(do_l + aoff<D>(row, 16 * s + 8 * h));
-        sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qa, kf[s], sacc, 0, 0, 0);
-        pacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da, vf[s], pacc, 0, 0, 0);
-      }
+      bf16x8 qa[D / 16], da[D / 16];
+      f32x4 L4[4], D4[4];
+      static_for<D / 16>([&](auto s_) {
+        constexpr int s = decltype(s_)::value;
+        qa[s] = lds_b128<QO>(sa[s]);
+        da[s] = lds_b128<QO + QB>(sa[s]);
+      });
+      static_for<D / 16>([&](auto s_) {
+        constexpr int s = decltype(s_)::value;
+        lds_wait<2 * (D / 16 - 1 - s)>(qa[s], da[s]);
+        sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qa[s], kf[s], sacc, 0, 0, 0);
+        pacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da[s], vf[s], pacc, 0, 0, 0);
+      });
+      static_for<4>([&](auto g_) { L4[decltype(g_)::value] = lds_f128<LO + 32 * decltype(g_)::value>(la); });
       // stagger (a.stagger): waves w and w + 4 share a SIMD and would otherwise reach the
       // softmax VALU together; waves 4-7 run the dQ chunk after it instead, so one wave of each
       // pair issues MFMAs while its partner runs the exp / dS arithmetic (MI355X_MICROARCH.md,
       // 'Two waves per SIMD', item 9)
       if (!late) hook(2 * qt);
+      // delta is read under the exponentials: its wait also names sacc, which keeps it behind them
+      static_for<4>([&](auto g_) { D4[decltype(g_)::value] = lds_f128<LO + QT * 4 + 32 * decltype(g_)::value>(la); });
+      lds_wait<4>(L4[0], L4[1], L4[2], L4[3]);
 #pragma unroll
-      for (int g4 = 0; g4 < 4; ++g4) {
-        const float4 L4 = *reinterpret_cast<const float4*>(lse_l + 32 * qt + 8 * g4 + 4 * h);
-        const float lv[4] = {L4.x, L4.y, L4.z, L4.w};
+      for (int g4 = 0; g4 < 4; ++g4)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) sacc[4 * g4 + j] = fast_exp2(sacc[4 * g4 + j] * sl2 - lv[j]);
-      }
+        for (int j = 0; j < 4; ++j) sacc[4 * g4 + j] = fast_exp2(sacc[4 * g4 + j] * sl2 - L4[g4][j]);
+      lds_wait<0>(D4[0], D4[1], D4[2], D4[3], sacc);
       if (MASK) {
         const bool need = (kb0 + wave * 32 + 31 >= a.Sk) || (a.causal && kb0 + wave * 32 + 31 > qbase + 32 * qt);
         if (need) {
@@ -1077,34 +1201,50 @@ __global__ void __launch_bounds__(512, 1) attn_bwd1b_kernel(AttnArgs a, int nkb,
         }
       }
 #pragma unroll
-      for (int g4 = 0; g4 < 4; ++g4) {
-        const float4 D4 = *reinterpret_cast<const float4*>(dl_l + 32 * qt + 8 * g4 + 4 * h);
-        const float dv4[4] = {D4.x, D4.y, D4.z, D4.w};
+      for (int g4 = 0; g4 < 4; ++g4)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) pacc[4 * g4 + j] = sacc[4 * g4 + j] * (pacc[4 * g4 + j] - dv4[j]);
-      }
+        for (int j = 0; j < 4; ++j) pacc[4 * g4 + j] = sacc[4 * g4 + j] * (pacc[4 * g4 + j] - D4[g4][j]);
       const bf16x8 pb0 = pack8(sacc, 0), pb1 = pack8(sacc, 8);
       const bf16x8 sb0 = pack8(pacc, 0), sb1 = pack8(pacc, 8);
       if (late) hook(2 * qt);
-#pragma unroll
-      for (int dt = 0; dt < D / 32; ++dt) {
-        const int col = dt * 32 + 16 * (G & 1) + 4 * pi;
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-          const int r0 = 32 * qt + 16 * s2 + 4 * h + qi;
-          const bf16x8 ao = cat8(tr_read(do_l, aoff<D>(r0, col)), tr_read(do_l, aoff<D>(r0 + 8, col)));
-          const bf16x8 aq = cat8(tr_read(q_l, aoff<D>(r0, col)), tr_read(q_l, aoff<D>(r0 + 8, col)));
-          dv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ao, s2 ? pb1 : pb0, dv[dt], 0, 0, 0);
-          dk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aq, s2 ? sb1 : sb0, dk[dt], 0, 0, 0);
-        }
-      }
+      // dV / dK: group g = (dt, s2) is four transposed reads (dO and Q rows r0, r0 + 8); group g + 2
+      // is issued behind the MFMAs of group g, so one group is in flight under every MFMA pair
+      v4s ro[4][2], rq[4][2];
+      auto issue = [&](auto g_) {
+        constexpr int g = decltype(g_)::value, dt = g >> 1, s2 = g & 1;
+        ro[g][0] = lds_tr<QO + QB>(va[dt][s2][0]);
+        ro[g][1] = lds_tr<QO + QB>(va[dt][s2][1]);
+        rq[g][0] = lds_tr<QO>(va[dt][s2][0]);
+        rq[g][1] = lds_tr<QO>(va[dt][s2][1]);
+      };
+      issue(std::integral_constant<int, 0>{});
+      issue(std::integral_constant<int, 1>{});
+      static_for<4>([&](auto g_) {
+        constexpr int g = decltype(g_)::value, dt = g >> 1, s2 = g & 1;
+        lds_wait<(g < 3 ? 4 : 0)>(ro[g][0], ro[g][1], rq[g][0], rq[g][1]);  // one younger group in flight
+        const bf16x8 ao = join8(ro[g][0], ro[g][1]), aq = join8(rq[g][0], rq[g][1]);
+        dv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ao, s2 ? pb1 : pb0, dv[dt], 0, 0, 0);
+        dk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aq, s2 ? sb1 : sb0, dk[dt], 0, 0, 0);
+        if constexpr (g + 2 < 4) issue(std::integral_constant<int, g + 2>{});
+      });
       hook(2 * qt + 1);
       const int krow = wave * 32 + (lane & 31);
       const bf16x4 parts[4] = {sb0.lo, sb0.hi, sb1.lo, sb1.hi};
 #pragma unroll
       for (int g = 0; g < 4; ++g)
-        *reinterpret_cast<bf16x4*>(ds_l + dst_off(krow, 32 * qt + 8 * g + 4 * h)) = parts[g];
-    }
+        *reinterpret_cast<bf16x4*>(ds_l + dst1b_off(krow, 32 * qt + 8 * g + 4 * h)) = parts[g];
+    });
+    // the next tile is in the other buffer
+    la += tile_step;
+#pragma unroll
+    for (int s = 0; s < D / 16; ++s) sa[s] += tile_step;
+#pragma unroll
+    for (int dt = 0; dt < D / 32; ++dt)
+#pragma unroll
+      for (int s2 = 0; s2 < 2; ++s2)
+#pragma unroll
+        for (int hi = 0; hi < 2; ++hi) va[dt][s2][hi] += tile_step;
+    tile_step = -tile_step;
   };
   // dQ^T (16 d x 16 queries, two tiles) = K^T . dS^T of tile t-1 over key slices [32 k0, 32 k1)
   auto dq_chunk = [&](int t, int k0, int k1) {
@@ -1113,11 +1253,11 @@ __global__ void __launch_bounds__(512, 1) attn_bwd1b_kernel(AttnArgs a, int nkb,
 #pragma unroll
     for (int ks = k0; ks < k1; ++ks) {
       const int kr = 32 * ks + 8 * G + qi;
-      const bf16x8 ka = cat8(tr_read(k_l, aoff<D>(kr, dq_d0 + 4 * pi)), tr_read(k_l, aoff<D>(kr + 4, dq_d0 + 4 * pi)));
+      const bf16x8 ka = cat8(tr_read(k_l, k1b_off(kr, dq_d0 + 4 * pi)), tr_read(k_l, k1b_off(kr + 4, dq_d0 + 4 * pi)));
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const int cq = dq_q0 + 16 * j + 4 * pi;
-        const bf16x8 sbq = cat8(tr_read(dsl, dst_off(kr, cq)), tr_read(dsl, dst_off(kr + 4, cq)));
+        const bf16x8 sbq = cat8(tr_read(dsl, dst1b_off(kr, cq)), tr_read(dsl, dst1b_off(kr + 4, cq)));
         dqa[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ka, sbq, dqa[j], 0, 0, 0);
       }
     }
@@ -1128,18 +1268,27 @@ __global__ void __launch_bounds__(512, 1) attn_bwd1b_kernel(AttnArgs a, int nkb,
   // [nkb][B*H][D] (dK, dV) that attn_bias_fold adds into the bias gradient
   const bool bsum = a.dbp != nullptr;
   float dqs[4] = {0.f, 0.f, 0.f, 0.f};
-  auto dq_store = [&](int t) {  // after the barrier: vmcnt counts stores, the next wait is a tile away
+  // after the barrier: vmcnt counts stores, the next wait is a tile away. Both running sums are
+  // added before the first store: hipcc waits for each prevq[j] at its first use, and a wait placed
+  // behind the j = 0 store would also wait for that store's acknowledgement, once per tile.
+  auto dq_store = [&](int t) {
     const int pq = (t - 1) * QT;
     int last = nkb - 1;
     if (MASK && a.causal) last = min(last, (pq + QT - 1) / KB);
+    f32x4 accs[2] = {dqa[0], dqa[1]};
+    if (chain && kblk > 0) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        if (!MASK || pq + dq_q0 + 16 * j + l16 < a.Sq) {
+          accs[j][0] += prevq[j].x; accs[j][1] += prevq[j].y; accs[j][2] += prevq[j].z; accs[j][3] += prevq[j].w;
+        }
+      }
+    }
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int q = pq + dq_q0 + 16 * j + l16;
       if (!MASK || q < a.Sq) {
-        f32x4 acc = dqa[j];
-        if (chain && kblk > 0) {
-          acc[0] += prevq[j].x; acc[1] += prevq[j].y; acc[2] += prevq[j].z; acc[3] += prevq[j].w;
-        }
+        const f32x4 acc = accs[j];
         if (chain && kblk == last) {
           const unsigned w0 = pack_bf2(acc[0] * a.scale, acc[1] * a.scale), w1 = pack_bf2(acc[2] * a.scale, acc[3] * a.scale);
           *reinterpret_cast<uint2*>(dQb + (int64_t)q * a.dq_ss + dq_d0 + 4 * G) = make_uint2(w0, w1);
