@@ -29,6 +29,11 @@ struct AttnArgs {
   int causal = 0;
   float rescale_thr = 8.f;  // forward: deferred-max threshold, log2 units (attn_set_rescale_thr)
   int stagger = 0;  // backward (attn_bwd1b_kernel): waves 4-7 run each dQ chunk after the softmax
+  // per-sample key lengths [B] (device int32) of a right-padded batch, or null: key j of sample b
+  // takes part iff j < clamp(key_lens[b], 0, Sk). Read on the device only; selects the MASK = true
+  // instantiations, which bound their mask tests and tile / key-block loops by it (memory bounds
+  // stay on Sk). A sample of length 0 gives o = 0, lse = +inf and zero gradients.
+  const int* key_lens = nullptr;
 };
 
 void attn_fwd(AttnArgs a, hipStream_t st);

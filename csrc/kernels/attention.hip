@@ -120,8 +120,18 @@ __device__ __forceinline__ bf16x8 pack8(const f32x16& a, int base) {
   return o;
 }
 
+// Keys of sample b that take part: clamp(key_lens[b], 0, Sk), or Sk without lengths. One scalar
+// load per workgroup (b is wave-uniform); only the MASK = true instantiations look at it.
+template <bool MASK>
+__device__ __forceinline__ int key_limit(const AttnArgs& a, int b) {
+  if constexpr (MASK) {
+    if (a.key_lens) return __builtin_amdgcn_readfirstlane(min(max(a.key_lens[b], 0), a.Sk));
+  }
+  return a.Sk;
+}
+
 // ------------------------------------------------------------------------------------ forward
-// MASK = false (no ragged key tile, not causal) compiles the mask test out. 1-D grid through
+// MASK = false (no ragged key tile, not causal, no key lengths) compiles the mask test out. 1-D grid through
 // xcd_remap: the query blocks of one (batch, head) share an XCD and its L2 copy of K / V. The O
 // tile leaves through LDS as whole rows (16 B per lane). Together -5 % at B32 H16 S512 D64
 // (scripts/lab/attn_fwd_lab.hip, profiles/attn_fwd_lab_r2.txt).
@@ -174,7 +184,10 @@ __global__ void __launch_bounds__(256, DMA ? 4 : 2) attn_fwd_kernel(AttnArgs a) 
         asm volatile("" : "+v"(vo[dt][s2][hi]));
       }
 
-  int nkv = (a.Sk + KV - 1) / KV;
+  // tiles past the sample's key length are never fetched; no live key at all (nkv == 0) leaves
+  // lsum == 0 for the epilogue: o = 0, lse = +inf
+  const int klim = key_limit<MASK>(a, b);
+  int nkv = (klim + KV - 1) / KV;
   if (a.causal) nkv = min(nkv, (min(qblk0 + 128, a.Sq) + KV - 1) / KV);
 
   TileStage<D, KV, 256> sk, sv;
@@ -226,14 +239,14 @@ __global__ void __launch_bounds__(256, DMA ? 4 : 2) attn_fwd_kernel(AttnArgs a) 
     // test), online softmax on the raw scores (lane-local + xor-32 partner), scale folded into
     // one FMA per element: p = exp2(s * sl2 - m * sl2)
     const int kbase = t * KV;
-    const bool need_mask = MASK && ((kbase + KV > a.Sk) || (a.causal && kbase + KV - 1 > q0));
+    const bool need_mask = MASK && ((kbase + KV > klim) || (a.causal && kbase + KV - 1 > q0));
     if (need_mask) {
 #pragma unroll
       for (int kt = 0; kt < 2; ++kt) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int key = kbase + 32 * kt + (r & 3) + 8 * (r >> 2) + 4 * h;
-          if (key >= a.Sk || (a.causal && key > qrow)) sacc[kt][r] = -INFINITY;
+          if (key >= klim || (a.causal && key > qrow)) sacc[kt][r] = -INFINITY;
         }
       }
     }
@@ -394,7 +407,8 @@ __global__ void __launch_bounds__(256, 2) attn_fwd2_kernel(AttnArgs a) {
         asm volatile("" : "+v"(vo[dt][s2][hi]));
       }
 
-  int nkv = (a.Sk + KV - 1) / KV;
+  const int klim = key_limit<MASK>(a, b);
+  int nkv = (klim + KV - 1) / KV;
   if (a.causal) nkv = min(nkv, (min(qblk0 + ROWS, a.Sq) + KV - 1) / KV);
   const int kb = (int)min((int64_t)0x7fffffff, ((int64_t)(a.Sk - 1) * a.k_ss + D) * 2);
   const int vb = (int)min((int64_t)0x7fffffff, ((int64_t)(a.Sk - 1) * a.v_ss + D) * 2);
@@ -433,14 +447,14 @@ __global__ void __launch_bounds__(256, 2) attn_fwd2_kernel(AttnArgs a) {
 #pragma unroll
     for (int qb = 0; qb < QB; ++qb) {
       const int qrow = q0 + 32 * qb + (lane & 31);
-      const bool need_mask = MASK && ((kbase + KV > a.Sk) || (a.causal && kbase + KV - 1 > q0 + 32 * qb));
+      const bool need_mask = MASK && ((kbase + KV > klim) || (a.causal && kbase + KV - 1 > q0 + 32 * qb));
       if (need_mask) {
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const int key = kbase + 32 * kt + (r & 3) + 8 * (r >> 2) + 4 * h;
-            if (key >= a.Sk || (a.causal && key > qrow)) sacc[qb][kt][r] = -INFINITY;
+            if (key >= klim || (a.causal && key > qrow)) sacc[qb][kt][r] = -INFINITY;
           }
       }
       float mx = -INFINITY;
@@ -661,7 +675,7 @@ __device__ __forceinline__ unsigned pack_bf2(float x, float y) {
 
 // NW waves x 32 keys per workgroup (NW = 8 at D = 64: 256 keys; 4 at D = 128), loop over 64-query
 // tiles. Shaped by measurements (scripts/lab/attn_bwd_lab.hip, profiles/attn_bwd_lab_r2.txt):
-//  * MASK = false (no ragged blocks, not causal) drops every bounds / mask test; with MASK the
+//  * MASK = false (no ragged blocks, not causal, no key lengths) drops every bounds / mask test; with MASK the
 //    key / causal mask runs only on 32x32 blocks that cross the sequence end or the diagonal (a
 //    per-element select on every block cost the kernel ~30 %).
 //  * Prologue: the K and V blocks go row-coalesced into LDS (K stays there for dQ; V is staged in
@@ -729,6 +743,14 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) attn_bwd_kernel(AttnArgs a, i
   float* dq_part = a.dq_acc + (int64_t)(chain ? 0 : kblk) * a.B * a.H * a.Sq * D + (int64_t)bh * a.Sq * D;
   bf16_t* dQb = a.dq + (int64_t)b * a.dq_sb + (int64_t)hh * a.dq_sh;
 
+  // per-sample key length (AttnArgs.key_lens): the sample's last live key block kb_last (not
+  // nkb - 1) ends the dQ chain, and a block past it has no query tile to run (qt_begin = nqt below):
+  // it leaves the chained dQ alone and, through the ordinary epilogue, writes zero dK / dV rows (a
+  // zero dQ slab in the slab form). Block 0 always runs, so a sample of length 0 still gets its dQ
+  // written: every P is masked to 0 there, which makes all of its gradients exact zeros.
+  const int klim = key_limit<MASK>(a, b);
+  auto kb_last = [&]() { return MASK ? min(nkb - 1, max((klim + KB - 1) / KB - 1, 0)) : nkb - 1; };
+
   // K block -> LDS (kept for dQ), V block -> tile buffers; K^T / V^T fragments (B operands, key on
   // the lane) from the LDS images
   bf16x8 kf[D / 16], vf[D / 16];
@@ -749,8 +771,8 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) attn_bwd_kernel(AttnArgs a, i
   f32x16 dk[D / 32], dv[D / 32];
 #pragma unroll
   for (int i = 0; i < D / 32; ++i) { dk[i] = f32x16{}; dv[i] = f32x16{}; }
-  const int qt_begin = (MASK && a.causal) ? kb0 / QT : 0;
   const int nqt = (a.Sq + QT - 1) / QT;
+  const int qt_begin = !MASK ? 0 : kblk > kb_last() ? nqt : a.causal ? kb0 / QT : 0;
   const int G = lane >> 4, qi = (lane & 15) >> 2, pi = lane & 3;
 
   TileStage<D, QT, NT> sq, sd;
@@ -846,12 +868,12 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) attn_bwd_kernel(AttnArgs a, i
         for (int j = 0; j < 4; ++j) sacc[4 * g4 + j] = fast_exp2(sacc[4 * g4 + j] * sl2 - lv[j]);
       }
       if (MASK) {
-        const bool need = (kb0 + wave * 32 + 31 >= a.Sk) || (a.causal && kb0 + wave * 32 + 31 > qbase + 32 * qt);
+        const bool need = (kb0 + wave * 32 + 31 >= klim) || (a.causal && kb0 + wave * 32 + 31 > qbase + 32 * qt);
         if (need) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const int q = qbase + 32 * qt + (r & 3) + 8 * (r >> 2) + 4 * h;
-            if (key >= a.Sk || (a.causal && key > q)) sacc[r] = 0.f;
+            if (key >= klim || (a.causal && key > q)) sacc[r] = 0.f;
           }
         }
       }
@@ -905,7 +927,7 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) attn_bwd_kernel(AttnArgs a, i
           }
         }
         // last key block contributing to this query tile: the last one, or (causal) the diagonal's
-        int last = nkb - 1;
+        int last = kb_last();
         if (MASK && a.causal) last = min(last, (qbase + QT - 1) / KB);
         if (chain && kblk == last) {
           bf16_t* drow = dQb + (int64_t)q * a.dq_ss + 32 * dt + 4 * h;
@@ -987,8 +1009,9 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) attn_bwd_kernel(AttnArgs a, i
       lds_barrier();           // tile t+1 visible; dS^T reads of tile t done before it is rewritten
     }
   }
-  // slabs, causal: query tiles before qt_begin get nothing from this key block; zero its rows
-  if (MASK && a.causal && !chain) {
+  // slabs: query tiles before qt_begin (causal; all of them in a block past the key length) get
+  // nothing from this key block; zero its rows
+  if (MASK && !chain) {
     for (int64_t i = tid; i < (int64_t)min(qt_begin * QT, a.Sq) * D; i += NT) dq_part[i] = 0.f;
   }
   // dK (K block image) and dV (tile buffers) through LDS, 16-B chunks XOR-swizzled by row & 7;
@@ -1082,6 +1105,11 @@ __global__ void __launch_bounds__(512, 1) attn_bwd1b_kernel(AttnArgs a, int nkb,
   float* dq_part = a.dq_acc + (int64_t)(chain ? 0 : kblk) * a.B * a.H * a.Sq * D + (int64_t)bh * a.Sq * D;
   bf16_t* dQb = a.dq + (int64_t)b * a.dq_sb + (int64_t)hh * a.dq_sh;
 
+  // per-sample key length, as in attn_bwd_kernel: the dQ chain ends at block kb_last; a block past
+  // it runs no query tile and writes zero dK / dV rows and zero bias partials; block 0 always runs
+  const int klim = key_limit<MASK>(a, b);
+  auto kb_last = [&]() { return MASK ? min(nkb - 1, max((klim + KB - 1) / KB - 1, 0)) : nkb - 1; };
+
   bf16x8 kf[D / 16], vf[D / 16];
   {
     TileStage<D, KB, NT> sk, sv;
@@ -1101,8 +1129,8 @@ __global__ void __launch_bounds__(512, 1) attn_bwd1b_kernel(AttnArgs a, int nkb,
 #pragma unroll
   for (int i = 0; i < D / 32; ++i) { dk[i] = f32x16{}; dv[i] = f32x16{}; }
 
-  const int qt_begin = (MASK && a.causal) ? kb0 / QT : 0;
   const int nqt = (a.Sq + QT - 1) / QT;
+  const int qt_begin = !MASK ? 0 : kblk > kb_last() ? nqt : a.causal ? kb0 / QT : 0;
   const int G = lane >> 4, qi = (lane & 15) >> 2, pi = lane & 3, l16 = lane & 15;
   // LDS byte addresses of this lane's asm reads in the buffer of the tile s_tile runs next (the
   // 32-row half, Q / dO and the lse2 / delta row are immediate offsets: aswz ignores row bit 5).
@@ -1191,12 +1219,12 @@ __global__ void __launch_bounds__(512, 1) attn_bwd1b_kernel(AttnArgs a, int nkb,
         for (int j = 0; j < 4; ++j) sacc[4 * g4 + j] = fast_exp2(sacc[4 * g4 + j] * sl2 - L4[g4][j]);
       lds_wait<0>(D4[0], D4[1], D4[2], D4[3], sacc);
       if (MASK) {
-        const bool need = (kb0 + wave * 32 + 31 >= a.Sk) || (a.causal && kb0 + wave * 32 + 31 > qbase + 32 * qt);
+        const bool need = (kb0 + wave * 32 + 31 >= klim) || (a.causal && kb0 + wave * 32 + 31 > qbase + 32 * qt);
         if (need) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const int q = qbase + 32 * qt + (r & 3) + 8 * (r >> 2) + 4 * h;
-            if (key >= a.Sk || (a.causal && key > q)) sacc[r] = 0.f;
+            if (key >= klim || (a.causal && key > q)) sacc[r] = 0.f;
           }
         }
       }
@@ -1273,7 +1301,7 @@ __global__ void __launch_bounds__(512, 1) attn_bwd1b_kernel(AttnArgs a, int nkb,
   // behind the j = 0 store would also wait for that store's acknowledgement, once per tile.
   auto dq_store = [&](int t) {
     const int pq = (t - 1) * QT;
-    int last = nkb - 1;
+    int last = kb_last();
     if (MASK && a.causal) last = min(last, (pq + QT - 1) / KB);
     f32x4 accs[2] = {dqa[0], dqa[1]};
     if (chain && kblk > 0) {
@@ -1327,10 +1355,10 @@ __global__ void __launch_bounds__(512, 1) attn_bwd1b_kernel(AttnArgs a, int nkb,
     finish();
     dq_store(nqt);
   }
-  if (MASK && a.causal && !chain) {
+  if (MASK && !chain) {
     for (int64_t i = tid; i < (int64_t)min(qt_begin * QT, a.Sq) * D; i += NT) dq_part[i] = 0.f;
   }
-  if (bsum && kblk == nkb - 1) {  // dQ column sums: over the 16 query lanes of each d quad
+  if (bsum && kblk == kb_last()) {  // dQ column sums: over the 16 query lanes of each d quad
 #pragma unroll
     for (int off = 1; off < 16; off <<= 1)
 #pragma unroll
@@ -1536,7 +1564,7 @@ void attn_set_stagger(int v) { g_stagger = v != 0; }
 
 void attn_fwd(AttnArgs a, hipStream_t st) {
   const dim3 grid((unsigned)((a.Sq + 127) / 128 * a.B * a.H));
-  const bool mask = a.causal || a.Sk % 64 != 0;
+  const bool mask = a.causal || a.Sk % 64 != 0 || a.key_lens != nullptr;
   a.rescale_thr = attn_rescale_thr();
   // the DMA path needs 16-B aligned K / V rows and buffer offsets below 2 GiB
   const bool dma_ok = ((uintptr_t)a.k & 15) == 0 && ((uintptr_t)a.v & 15) == 0 && a.k_ss % 8 == 0 &&
@@ -1567,7 +1595,7 @@ void attn_fwd(AttnArgs a, hipStream_t st) {
 
 template <int D, int NW, bool DMA = false>
 static void launch_bwd_main(AttnArgs a, int nkb, bool chain, hipStream_t st) {
-  const bool mask = a.causal || a.Sk % (32 * NW) != 0 || a.Sq % 64 != 0;
+  const bool mask = a.causal || a.Sk % (32 * NW) != 0 || a.Sq % 64 != 0 || a.key_lens != nullptr;
   const int bh = a.B * a.H;
   if (chain) {
     for (int p = 0; p < nkb; ++p) {
@@ -1601,7 +1629,7 @@ bool attn_bwd(AttnArgs a, hipStream_t st) {
   if (a.D == 64) {
     hipLaunchKernelGGL(attn_bwd_pre_kernel<64>, gpre, dim3(256), 0, st, a);
     if (chain && dma_ok) {
-      const bool m = a.causal || a.Sk % 256 != 0 || a.Sq % 64 != 0;
+      const bool m = a.causal || a.Sk % 256 != 0 || a.Sq % 64 != 0 || a.key_lens != nullptr;
       const int bh = a.B * a.H;
       // fused bias-gradient sums: non-causal (every query tile's last key block is the last launch)
       if (a.causal) a.dbp = nullptr;

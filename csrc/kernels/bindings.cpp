@@ -504,6 +504,15 @@ void gemm_f32(Tensor A, Tensor B, Tensor C, optional<Tensor> bias, optional<Tens
   ffk::gemm_f32(p, cur_stream());
 }
 
+void key_len_mask_f32(Tensor s, Tensor key_lens, int64_t b, int64_t Sk, double value) {
+  check_dev(s, "s");
+  TORCH_CHECK(s.scalar_type() == at::kFloat && s.is_contiguous() && s.numel() % Sk == 0);
+  TORCH_CHECK(key_lens.scalar_type() == at::kInt && key_lens.is_contiguous() && b >= 0 && b < key_lens.numel() &&
+              key_lens.device() == s.device(), "key_len_mask_f32: key_lens int32 [B] on the scores' device");
+  ffk::key_len_mask_f32(s.data_ptr<float>(), s.numel() / Sk, (int)Sk, key_lens.data_ptr<int>() + b, (float)value,
+                        cur_stream());
+}
+
 void causal_mask_f32(Tensor s, int64_t Sq, int64_t Sk) {
   TORCH_CHECK(s.scalar_type() == at::kFloat && s.is_contiguous() && s.numel() % Sk == 0);
   ffk::causal_mask_f32(s.data_ptr<float>(), s.numel() / Sk, (int)Sq, (int)Sk, cur_stream());
@@ -604,10 +613,19 @@ void aggregate_bwd(Tensor dout, optional<Tensor> gate, std::vector<optional<Tens
                      cur_stream());
 }
 
+// per-sample key lengths of a padded batch: int32 [B] on the activations' device, read there only
+const int* attn_key_lens(const optional<Tensor>& key_lens, const Tensor& q, int64_t B) {
+  if (!key_lens.has_value() || !key_lens->defined()) return nullptr;
+  TORCH_CHECK(key_lens->scalar_type() == at::kInt && key_lens->is_contiguous() && key_lens->numel() == B,
+              "attn: key_lens must be a contiguous int32 tensor of B elements");
+  TORCH_CHECK(key_lens->device() == q.device(), "attn: key_lens must be on the device of q");
+  return key_lens->data_ptr<int>();
+}
+
 // q/k/v/o given with explicit [b,h,s] element strides (d contiguous)
 void attn_fwd(Tensor q, std::vector<int64_t> qs, Tensor k, std::vector<int64_t> ks, Tensor v,
               std::vector<int64_t> vs, Tensor o, std::vector<int64_t> os, Tensor lse, int64_t B, int64_t H,
-              int64_t Sq, int64_t Sk, int64_t D, double scale, bool causal) {
+              int64_t Sq, int64_t Sk, int64_t D, double scale, bool causal, optional<Tensor> key_lens) {
   TORCH_CHECK(D == 64 || D == 128, "flash attention supports head_dim 64/128");
   TORCH_CHECK(q.scalar_type() == at::kBFloat16 && o.scalar_type() == at::kBFloat16);
   TORCH_CHECK(lse.numel() >= B * H * Sq && lse.scalar_type() == at::kFloat);
@@ -619,6 +637,7 @@ void attn_fwd(Tensor q, std::vector<int64_t> qs, Tensor k, std::vector<int64_t> 
   a.o = (uint16_t*)o.data_ptr(); a.o_sb = os[0]; a.o_sh = os[1]; a.o_ss = os[2];
   a.lse = lse.data_ptr<float>();
   a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.D = D; a.scale = scale; a.causal = causal;
+  a.key_lens = attn_key_lens(key_lens, q, B);
   ffk::attn_fwd(a, cur_stream());
 }
 int64_t attn_bwd_ws(int64_t B, int64_t H, int64_t Sq, int64_t Sk, int64_t D) {
@@ -628,7 +647,7 @@ bool attn_bwd(Tensor q, std::vector<int64_t> qs, Tensor k, std::vector<int64_t> 
               std::vector<int64_t> vs, Tensor o, std::vector<int64_t> os, Tensor dout, std::vector<int64_t> dos,
               Tensor lse, Tensor dq, std::vector<int64_t> dqs, Tensor dk, std::vector<int64_t> dks, Tensor dv,
               std::vector<int64_t> dvs, Tensor ws, int64_t B, int64_t H, int64_t Sq, int64_t Sk, int64_t D,
-              double scale, bool causal, optional<Tensor> dbias) {
+              double scale, bool causal, optional<Tensor> dbias, optional<Tensor> key_lens) {
   TORCH_CHECK(D == 64 || D == 128, "flash attention supports head_dim 64/128");
   TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.numel() >= ffk::attn_bwd_workspace_floats(B, H, Sq, Sk, D),
               "attn_bwd: workspace too small");
@@ -653,6 +672,7 @@ bool attn_bwd(Tensor q, std::vector<int64_t> qs, Tensor k, std::vector<int64_t> 
     a.dbias = dbias->data_ptr<float>();
   }
   a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.D = D; a.scale = scale; a.causal = causal;
+  a.key_lens = attn_key_lens(key_lens, q, B);
   return ffk::attn_bwd(a, cur_stream());
 }
 
@@ -957,6 +977,7 @@ PYBIND11_MODULE(_C, m) {
   m.def("transpose2d_batch", &transpose2d_batch);
   m.def("gemm_f32", &gemm_f32);
   m.def("causal_mask_f32", &causal_mask_f32);
+  m.def("key_len_mask_f32", &key_len_mask_f32);
   m.def("topk_fwd", &topk_fwd);
   m.def("topk_bwd", &topk_bwd);
   m.def("moe_route_ws_ints", &moe_route_ws_ints);
@@ -965,12 +986,14 @@ PYBIND11_MODULE(_C, m) {
   m.def("groupby_bwd", &groupby_bwd);
   m.def("aggregate_fwd", &aggregate_fwd);
   m.def("aggregate_bwd", &aggregate_bwd);
-  m.def("attn_fwd", &attn_fwd);
+  m.def("attn_fwd", &attn_fwd, py::arg("q"), py::arg("qs"), py::arg("k"), py::arg("ks"), py::arg("v"), py::arg("vs"),
+        py::arg("o"), py::arg("os"), py::arg("lse"), py::arg("B"), py::arg("H"), py::arg("Sq"), py::arg("Sk"),
+        py::arg("D"), py::arg("scale"), py::arg("causal"), py::arg("key_lens") = py::none());
   m.def("attn_bwd", &attn_bwd, py::arg("q"), py::arg("qs"), py::arg("k"), py::arg("ks"), py::arg("v"), py::arg("vs"),
         py::arg("o"), py::arg("os"), py::arg("dout"), py::arg("dos"), py::arg("lse"), py::arg("dq"), py::arg("dqs"),
         py::arg("dk"), py::arg("dks"), py::arg("dv"), py::arg("dvs"), py::arg("ws"), py::arg("B"), py::arg("H"),
         py::arg("Sq"), py::arg("Sk"), py::arg("D"), py::arg("scale"), py::arg("causal"),
-        py::arg("dbias") = py::none());
+        py::arg("dbias") = py::none(), py::arg("key_lens") = py::none());
   m.def("attn_bwd_ws", &attn_bwd_ws);
   m.def("attn_set_bwd_variant", [](int v) { ffk::attn_set_bwd_variant(v); });
   m.def("attn_fwd_variant", []() { return ffk::attn_fwd_variant(); });

@@ -54,6 +54,7 @@ int gemm256_bn(int M, int N, int batch, int splitk);
 void gemm_f32(const GemmArgs& p, hipStream_t stream);
 // fp32 attention path: -inf above the causal diagonal of [rows][Sk] scores (rows = batch * Sq)
 void causal_mask_f32(float* s, int64_t rows, int Sq, int Sk, hipStream_t st);
+void key_len_mask_f32(float* s, int64_t rows, int Sk, const int* key_len, float value, hipStream_t st);
 // dgrad GEMM of a consumer Linear fused with the producer Linear's activation backward:
 // C[M,N] bf16 = (A.B) * act'(zin), colpart as above. False when the shape / alignment does not
 // fit the 256-row kernel's coalesced epilogue (the caller then runs GEMM + bias_act_bwd).

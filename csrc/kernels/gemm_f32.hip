@@ -180,4 +180,22 @@ void causal_mask_f32(float* s, int64_t rows, int Sq, int Sk, hipStream_t st) {
   hipLaunchKernelGGL(causal_mask_kernel, dim3(ew_grid(rows * Sk, 256)), dim3(256), 0, st, s, rows, Sq, Sk);
 }
 
+// s[row][j] = value for j >= clamp(*key_len, 0, Sk): the key-length mask of one sample of the fp32
+// attention path. On the scores before the softmax with value = -inf; on the probabilities after it
+// with value = 0, which only matters for a length of 0 (the row softmax of an all -inf row is NaN,
+// as torch's is; the sample's probabilities are defined as 0). The length stays on the device: one
+// int32, read by every thread.
+__global__ void key_len_mask_kernel(float* __restrict__ s, int64_t rows, int Sk, const int* __restrict__ key_len,
+                                    float value) {
+  const int L = min(max(*key_len, 0), Sk);
+  const int64_t n = rows * Sk;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
+    if ((int)(e % Sk) >= L) s[e] = value;
+  }
+}
+void key_len_mask_f32(float* s, int64_t rows, int Sk, const int* key_len, float value, hipStream_t st) {
+  if (rows <= 0) return;
+  hipLaunchKernelGGL(key_len_mask_kernel, dim3(ew_grid(rows * Sk, 256)), dim3(256), 0, st, s, rows, Sk, key_len, value);
+}
+
 }  // namespace ffk

@@ -1,0 +1,57 @@
+"""bert-tiny on right-padded variable-length batches: every sample carries its number of real
+tokens, the data loader feeds those lengths next to the token ids, and every attention layer
+leaves the pad positions out as keys (`key_lengths`, read on the device: the step still captures
+into a graph). Synthetic data; the labels of pad positions are not masked out of the loss.
+
+    python examples/python/native/bert_varlen.py -b 8 --seq-length 64 --iterations 20
+"""
+import argparse
+import sys
+
+import _args  # noqa: F401  (puts the repo root on sys.path)
+import numpy as np
+
+from flexflow_amd.core import *  # noqa: F401,F403
+from flexflow_amd.models.bert import BertConfig, build_bert
+
+
+def top_level_task(argv=None):
+    ap = argparse.ArgumentParser(add_help=False)
+    ap.add_argument("--seq-length", type=int, default=64)
+    ap.add_argument("--iterations", type=int, default=20)
+    ap.add_argument("--min-length", type=int, default=8)
+    args, rest = ap.parse_known_args(sys.argv[1:] if argv is None else argv)
+    ffconfig = FFConfig(rest)
+    ffmodel = FFModel(ffconfig)
+    b, s = ffconfig.batch_size, args.seq_length
+    bc = BertConfig.tiny(s)
+    lengths = ffmodel.create_tensor([b], DataType.DT_INT32, name="key_lengths")
+    ids, pos, _ = build_bert(ffmodel, b, bc, key_lengths=lengths)
+    ffmodel.optimizer = AdamOptimizer(ffmodel, 1e-3)
+    ffmodel.compile(loss_type=LossType.LOSS_SPARSE_CATEGORICAL_CROSSENTROPY, metrics=[MetricsType.METRICS_ACCURACY])
+    # a synthetic corpus: n sentences of min-length .. s tokens, right-padded with token 0
+    rng = np.random.default_rng(0)
+    n = b * args.iterations
+    lens = rng.integers(min(args.min_length, s), s + 1, n).astype(np.int32)
+    tok = rng.integers(1, bc.vocab, (n, s)).astype(np.int32)
+    tok[np.arange(s)[None, :] >= lens[:, None]] = 0
+    labels = ((tok + 1) % bc.vocab)[..., None].astype(np.int32)  # learnable: the next id of each token
+    loaders = [ffmodel.create_data_loader(ids, tok),
+               ffmodel.create_data_loader(pos, np.tile(np.arange(s, dtype=np.int32), (n, 1))),
+               ffmodel.create_data_loader(lengths, lens),
+               ffmodel.create_data_loader(ffmodel.label_tensor, labels)]
+    ffmodel.init_layers()
+    ts = ffconfig.get_current_time()
+    for _ in range(args.iterations):
+        for dl in loaders:
+            dl.next_batch(ffmodel)
+        ffmodel.train_step()
+    pm = ffmodel.get_perf_metrics()
+    run_time = 1e-6 * (ffconfig.get_current_time() - ts)
+    print("bert-tiny varlen: %d iterations, mean length %.1f of %d, %.4fs, THROUGHPUT = %.2f samples/s, loss %.4f" %
+          (args.iterations, lens.mean(), s, run_time, b * args.iterations / run_time, pm.get_loss()))
+    return pm
+
+
+if __name__ == "__main__":
+    top_level_task()

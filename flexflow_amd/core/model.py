@@ -285,8 +285,12 @@ class FFModel:
         return L.outputs[0]
 
     def multihead_attention(self, query, key, value, embed_dim, num_heads, kdim=0, vdim=0, dropout=0.0, bias=True,
-                            add_bias_kv=False, add_zero_attn=False, kernel_initializer=None, causal=False, name=None):
-        return self._add(OperatorType.OP_MULTIHEAD_ATTENTION, [query, key, value], name, embed_dim=int(embed_dim),
+                            add_bias_kv=False, add_zero_attn=False, kernel_initializer=None, causal=False, name=None,
+                            key_lengths=None):
+        """key_lengths: optional int32 tensor [batch] (or [batch, 1]) of a right-padded batch: sample b
+        attends to its first key_lengths[b] keys only (ops/attention.py)."""
+        ins = [query, key, value] + ([key_lengths] if key_lengths is not None else [])
+        return self._add(OperatorType.OP_MULTIHEAD_ATTENTION, ins, name, embed_dim=int(embed_dim),
                          num_heads=int(num_heads), kdim=int(kdim), vdim=int(vdim), dropout=float(dropout), bias=bias,
                          add_bias_kv=add_bias_kv, add_zero_attn=add_zero_attn, kernel_init=kernel_initializer,
                          causal=causal, self_attn=(query is key and key is value)).outputs[0]

@@ -960,15 +960,33 @@ def attn_padded_dim(x, kd, vd):
     return 64 if kd <= 64 else 128
 
 
-def flash_attn_fwd(q, qs, k, ks, v, vs, o, os_, B, H, Sq, Sk, D, scale, causal):
+def attn_key_lens(key_lens, B, device):
+    """The per-sample key lengths of a right-padded batch as the kernels take them: contiguous int32
+    [B] ([B, 1] is flattened) on `device`, or None. Values are clamped to [0, Sk] where they are
+    read, on the device; nothing here looks at them."""
+    if key_lens is None:
+        return None
+    kl = key_lens.reshape(-1)
+    if kl.numel() != B:
+        raise ValueError(f"key_lengths: expected {B} entries (one per sample), got {tuple(key_lens.shape)}")
+    if kl.dtype != torch.int32 or kl.device != device or not kl.is_contiguous():
+        kl = kl.to(device=device, dtype=torch.int32).contiguous()
+    return kl
+
+
+def flash_attn_fwd(q, qs, k, ks, v, vs, o, os_, B, H, Sq, Sk, D, scale, causal, key_lens=None):
+    """key_lens: optional int32 [B] device tensor; key j of sample b is attended iff j < key_lens[b]
+    (a length of 0: o = 0, lse = +inf)."""
     lse = torch.empty(B * H * Sq, device=q.device, dtype=torch.float32)
-    ext().attn_fwd(q, qs, k, ks, v, vs, o, os_, lse, B, H, Sq, Sk, D, scale, causal)
+    ext().attn_fwd(q, qs, k, ks, v, vs, o, os_, lse, B, H, Sq, Sk, D, scale, causal,
+                   attn_key_lens(key_lens, B, q.device))
     return lse
 
 
 def flash_attn_bwd(q, qs, k, ks, v, vs, o, os_, do, dos, lse, dq, dqs, dk, dks, dv, dvs, B, H, Sq, Sk, D, scale,
-                   causal, dbias=None):
-    """dbias: optional contiguous fp32 [3*H*D] bias gradient of a fused [B,S,3,H,D] QKV projection
+                   causal, dbias=None, key_lens=None):
+    """key_lens: as in flash_attn_fwd; dk / dv rows at or past a sample's length are written as zeros.
+    dbias: optional contiguous fp32 [3*H*D] bias gradient of a fused [B,S,3,H,D] QKV projection
     (dq/dk/dv inside one dqkv buffer). Returns True when the kernel added the column sums of dq / dk /
     dv into it (attn_bwd1b_kernel, non-causal); False: the caller still owes that bias gradient."""
     X = ext()
@@ -976,7 +994,7 @@ def flash_attn_bwd(q, qs, k, ks, v, vs, o, os_, do, dos, lse, dq, dqs, dk, dks, 
     # dQ partial slabs + delta: one arena buffer shared (stream-ordered) by every attention layer
     ws = DeviceContext.get(q.device).workspace("attn_bwd", X.attn_bwd_ws(B, H, Sq, Sk, D))
     return bool(X.attn_bwd(q, qs, k, ks, v, vs, o, os_, do, dos, lse, dq, dqs, dk, dks, dv, dvs, ws, B, H, Sq, Sk, D,
-                           scale, causal, dbias))
+                           scale, causal, dbias, attn_key_lens(key_lens, B, q.device)))
 
 
 # ---------------------------------------------------------------------------- layer norm
@@ -1970,11 +1988,14 @@ def attn_f32_supported(x) -> bool:
     return native(x) and x.dtype == torch.float32
 
 
-def attn_f32_fwd(q, qs, k, ks, v, vs, o, os_, B, H, Sq, Sk, kd, vd, scale, causal):
+def attn_f32_fwd(q, qs, k, ks, v, vs, o, os_, B, H, Sq, Sk, kd, vd, scale, causal, key_lens=None):
     """fp32 attention on our kernels, per sample: S = Q.K^T (f32 MFMA GEMM, heads as the batch),
-    causal mask, row softmax(scale * S) (softmax.hip), O = P.V. q/k/v/o are flat views with [b, h,
-    row] element strides (qs, ks, vs, os_) and contiguous head dims. Returns P [B, H, Sq, Sk]."""
+    causal mask, key-length mask (key_lens: int32 [B] on the device, columns >= key_lens[b] set to
+    -inf there), row softmax(scale * S) (softmax.hip), the same columns of P set to 0 (a sample of
+    length 0 has P = 0, not the softmax's NaN), O = P.V. q/k/v/o are flat views with [b, h, row] element strides (qs, ks, vs, os_) and contiguous head dims.
+    Returns P [B, H, Sq, Sk]."""
     X = ext()
+    key_lens = attn_key_lens(key_lens, B, q.device)
     q, k, v, o = q.reshape(-1), k.reshape(-1), v.reshape(-1), o.reshape(-1)
     P = torch.empty(B, H, Sq, Sk, device=q.device, dtype=torch.float32)
     S = torch.empty(H, Sq, Sk, device=q.device, dtype=torch.float32)
@@ -1983,15 +2004,21 @@ def attn_f32_fwd(q, qs, k, ks, v, vs, o, os_, B, H, Sq, Sk, kd, vd, scale, causa
                    H, True, True, 1.0, 0.0, ACT_NONE)
         if causal:
             X.causal_mask_f32(S, Sq, Sk)
+        if key_lens is not None:
+            X.key_len_mask_f32(S, key_lens, b, Sk, float("-inf"))
         X.softmax_fwd(S, P[b], H * Sq, Sk, scale)
+        if key_lens is not None:  # a sample without keys: its all -inf rows came out NaN, P is 0 there
+            X.key_len_mask_f32(P[b], key_lens, b, Sk, 0.0)
         X.gemm_f32(P[b], v[b * vs[0]:], o[b * os_[0]:], None, None, Sq, vd, Sk, Sk, vs[2], os_[2], Sq * Sk, vs[1],
                    os_[1], H, True, False, 1.0, 0.0, ACT_NONE)
     return P
 
 
-def attn_f32_bwd(q, qs, k, ks, v, vs, do, dos, P, dq, dk, dv, B, H, Sq, Sk, kd, vd, scale):
+def attn_f32_bwd(q, qs, k, ks, v, vs, do, dos, P, dq, dk, dv, B, H, Sq, Sk, kd, vd, scale, key_lens=None):
     """Backward of attn_f32_fwd: dP = dO.V^T, dS = scale * P * (dP - rowsum(dP * P)), dQ = dS.K,
-    dK = dS^T.Q, dV = P^T.dO (dq / dk / dv share q / k / v's strides)."""
+    dK = dS^T.Q, dV = P^T.dO (dq / dk / dv share q / k / v's strides). key_lens needs no work here:
+    the forward left P = 0 in the masked columns, so dS is 0 there and the dK / dV rows at or past a
+    sample's length come out as zeros (all of a length-0 sample's gradients do)."""
     X = ext()
     q, k, v, do = q.reshape(-1), k.reshape(-1), v.reshape(-1), do.reshape(-1)
     dq, dk, dv = dq.reshape(-1), dk.reshape(-1), dv.reshape(-1)

@@ -10,6 +10,14 @@ GPU path (bf16): for self-attention ONE fused QKV GEMM ([T,E] x [3*H*D,E]^T) who
 in place by the flash-attention kernel through strides (no permute copies), then the output
 projection GEMM; the backward mirrors it (flash bwd writes dQ/dK/dV straight into the fused
 [T, 3, H, D] gradient buffer that feeds one dgrad and one split-K wgrad GEMM).
+
+Optional 4th input `key_lengths` (int32 [B] or [B, 1], on the activations' device): sample b of a
+right-padded batch has L_b = clamp(key_lengths[b], 0, Sk) real keys; key j takes part in the softmax
+iff j < L_b (and j <= q with `causal`). Every query row is still computed (as with torch's
+key_padding_mask); L_b = 0 gives zero output rows and zero gradients. The lengths are read on the
+device only, by every path (flash, zero-padded head dims, fp32 device, reference, CPU), so a step
+that takes them still captures into a graph. Not covered: arbitrary masks, query-side skipping or
+packing, loss masking.
 """
 from __future__ import annotations
 
@@ -30,12 +38,23 @@ def _pad_heads(t, st, B, S, H, d, Dp):
     return out
 
 
-def _attn_ref(q, k, v, scale, causal):
+def _attn_ref(q, k, v, scale, causal, key_lens=None):
     s = torch.einsum("bhqd,bhkd->bhqk", q, k) * scale
+    Sq, Sk = s.shape[-2:]
     if causal:
-        Sq, Sk = s.shape[-2:]
         s = s.masked_fill(torch.ones(Sq, Sk, dtype=torch.bool, device=s.device).triu(1), float("-inf"))
-    return torch.einsum("bhqk,bhkd->bhqd", torch.softmax(s, -1), v)
+    if key_lens is None:
+        return torch.einsum("bhqk,bhkd->bhqd", torch.softmax(s, -1), v)
+    # keys at or past the sample's length leave the softmax; a sample without keys gets P = 0 (its
+    # scores are made finite first, so neither the softmax nor its gradient sees a NaN). All on the
+    # tensor's device: the lengths are never read on the host.
+    L = key_lens.reshape(-1).to(s.device).clamp(0, Sk)
+    pad = torch.arange(Sk, device=s.device)[None, :] >= L[:, None]
+    empty = (L == 0)[:, None, None, None]
+    s = s.masked_fill(pad[:, None, None, :], float("-inf"))
+    s = torch.where(empty, torch.zeros_like(s), s)
+    p = torch.where(empty, torch.zeros_like(s), torch.softmax(s, -1))
+    return torch.einsum("bhqk,bhkd->bhqd", p, v)
 
 
 @register(OperatorType.OP_MULTIHEAD_ATTENTION)
@@ -44,7 +63,13 @@ class MultiHeadAttention(OpImpl):
 
     @classmethod
     def infer(cls, attrs, in_dims, in_dtypes):
-        q, k, v = in_dims
+        if len(in_dims) not in (3, 4):
+            raise ValueError(f"multihead_attention takes query, key, value[, key_lengths]; got {len(in_dims)} inputs")
+        q, k, v = in_dims[:3]
+        if len(in_dims) == 4:
+            kl = tuple(in_dims[3])
+            if kl not in ((q[0],), (q[0], 1)):
+                raise ValueError(f"key_lengths must have shape [{q[0]}] or [{q[0]}, 1], got {list(kl)}")
         H = attrs["num_heads"]
         E = attrs["embed_dim"]
         kd = attrs.get("kdim") or E // H
@@ -85,7 +110,13 @@ class MultiHeadAttention(OpImpl):
         return axis in (0, 3)
 
     def input_maps(self):
-        return [(0, 1, None), (0, None, None), (0, None, None)]
+        maps = [(0, 1, None), (0, None, None), (0, None, None)]
+        if len(self.layer.inputs) > 3:  # key lengths: sharded with the batch, replicated over the heads axis
+            maps.append((0,) + (None,) * (len(self.layer.inputs[3].dims) - 1))
+        return maps
+
+    def needs_input_grad(self, i):
+        return i < 3
 
     def weight_maps(self):
         out = []
@@ -109,9 +140,10 @@ class MultiHeadAttention(OpImpl):
         return {w.short_name: t for w, t in zip(self.layer.weights, ws)}
 
     def forward(self, ctx, xs, ws):
-        q_in, k_in, v_in = xs
+        q_in, k_in, v_in = xs[:3]
         W = self._w(ws)
         B, Sq, _ = q_in.shape
+        kl = K.attn_key_lens(xs[3], B, q_in.device) if len(xs) > 3 else None
         Sk = k_in.shape[1]
         kd, vd = self.attrs["kdim"], self.attrs["vdim"]
         Hl = W["o_weight"].shape[1]
@@ -151,7 +183,7 @@ class MultiHeadAttention(OpImpl):
         o = torch.empty(B, Sq, Hl, vd, device=q_in.device, dtype=q_in.dtype)
         os_ = [Sq * Hl * vd, vd, Hl * vd]
         if K.attn_supported(q_in, kd) and kd == vd:
-            lse = K.flash_attn_fwd(qv, qs, kv, ks, vv, vs, o, os_, B, Hl, Sq, Sk, kd, scale, causal)
+            lse = K.flash_attn_fwd(qv, qs, kv, ks, vv, vs, o, os_, B, Hl, Sq, Sk, kd, scale, causal, key_lens=kl)
             s["lse"] = lse
         elif K.attn_padded_dim(q_in, kd, vd):
             # head dims the MFMA kernels have no instance for (e.g. 16, 32, 80, 96): zero-pad Q, K,
@@ -164,12 +196,13 @@ class MultiHeadAttention(OpImpl):
             po = torch.empty(B, Sq, Hl, Dp, device=q_in.device, dtype=q_in.dtype)
             pst = [Sq * Hl * Dp, Dp, Hl * Dp]
             kst = [Sk * Hl * Dp, Dp, Hl * Dp]
-            lse = K.flash_attn_fwd(pq, pst, pk, kst, pv, kst, po, pst, B, Hl, Sq, Sk, Dp, scale, causal)
+            lse = K.flash_attn_fwd(pq, pst, pk, kst, pv, kst, po, pst, B, Hl, Sq, Sk, Dp, scale, causal, key_lens=kl)
             o.copy_(po[..., :vd])
             s.update(lse=lse, pad=(Dp, pq, pk, pv, po))
         elif K.attn_f32_supported(q_in) and os.environ.get("FF_ATTN_REF_FALLBACK") != "1":
             # --dtype fp32 on the device: f32 MFMA GEMMs + causal mask + row softmax, our kernels
-            s["P"] = K.attn_f32_fwd(qv, qs, kv, ks, vv, vs, o.view(-1), os_, B, Hl, Sq, Sk, kd, vd, scale, causal)
+            s["P"] = K.attn_f32_fwd(qv, qs, kv, ks, vv, vs, o.view(-1), os_, B, Hl, Sq, Sk, kd, vd, scale, causal,
+                                    key_lens=kl)
         else:
             if K.native(q_in) and q_in.dtype == torch.bfloat16 and os.environ.get("FF_ATTN_REF_FALLBACK") != "1":
                 raise NotImplementedError(
@@ -178,7 +211,7 @@ class MultiHeadAttention(OpImpl):
             q4 = qv.as_strided((B, Hl, Sq, kd), (qs[0], qs[1], qs[2], 1)).float()
             k4 = kv.as_strided((B, Hl, Sk, kd), (ks[0], ks[1], ks[2], 1)).float()
             v4 = vv.as_strided((B, Hl, Sk, vd), (vs[0], vs[1], vs[2], 1)).float()
-            o.copy_(_attn_ref(q4, k4, v4, scale, causal).permute(0, 2, 1, 3))
+            o.copy_(_attn_ref(q4, k4, v4, scale, causal, kl).permute(0, 2, 1, 3))
         o2 = o.view(B * Sq, Hl * vd)
         wo = W["o_weight"].reshape(E, Hl * vd)
         if ctx.training:
@@ -186,7 +219,7 @@ class MultiHeadAttention(OpImpl):
         y, _ = K.linear_fwd(o2, wo, bo, K.ACT_NONE, False)
         if ctx.training:
             s.update(o=o, wo=wo, has_bo=bo is not None, shape=(B, Sq, Sk, Hl, kd, vd, E), fused=fused,
-                     qs=qs, ks=ks, vs=vs, os=os_, scale=scale, causal=causal)
+                     qs=qs, ks=ks, vs=vs, os=os_, scale=scale, causal=causal, key_lens=kl)
         return [y.view(B, Sq, E)]
 
     def overwrites_wgrad(self, i):
@@ -212,6 +245,8 @@ class MultiHeadAttention(OpImpl):
         scale, causal = s["scale"], s["causal"]
         qs, ks, vs, os_ = s["qs"], s["ks"], s["vs"], s["os"]
         fused = s["fused"]
+        kl = s["key_lens"]
+        no_kl_grad = [None] * (len(self.layer.inputs) - 3)  # the lengths take no gradient
         bias_done = False
         if fused:
             qkv = s["qkv"]
@@ -229,7 +264,7 @@ class MultiHeadAttention(OpImpl):
             pst = [Sq * Hl * Dp, Dp, Hl * Dp]
             kst = [Sk * Hl * Dp, Dp, Hl * Dp]
             K.flash_attn_bwd(pq, pst, pk, kst, pv, kst, po, pst, pdo, pst, s["lse"], pdq, pst, pdk, kst, pdv, kst,
-                             B, Hl, Sq, Sk, Dp, scale, causal)
+                             B, Hl, Sq, Sk, Dp, scale, causal, key_lens=kl)
             for g, st, pg, S_, d in ((dq, qs, pdq, Sq, kd), (dk, ks, pdk, Sk, kd), (dv, vs, pdv, Sk, vd)):
                 g.as_strided((B, Hl, S_, d), (st[0], st[1], st[2], 1)).copy_(pg[..., :d].permute(0, 2, 1, 3))
         elif "lse" in s:
@@ -238,19 +273,19 @@ class MultiHeadAttention(OpImpl):
             dbq = gw("qkv_bias") if (fused and os.environ.get("FF_ATTN_BIAS_FUSION", "1") == "1") else None
             if dbq is not None and dbq.dtype == torch.float32 and dbq.is_contiguous():
                 bias_done = K.flash_attn_bwd(qv, qs, kv, ks, vv, vs, o, os_, do, os_, s["lse"], dq, qs, dk, ks, dv, vs,
-                                             B, Hl, Sq, Sk, kd, scale, causal, dbias=dbq.view(-1))
+                                             B, Hl, Sq, Sk, kd, scale, causal, dbias=dbq.view(-1), key_lens=kl)
             else:
                 K.flash_attn_bwd(qv, qs, kv, ks, vv, vs, o, os_, do, os_, s["lse"], dq, qs, dk, ks, dv, vs,
-                                 B, Hl, Sq, Sk, kd, scale, causal)
+                                 B, Hl, Sq, Sk, kd, scale, causal, key_lens=kl)
         elif "P" in s:
             K.attn_f32_bwd(qv, qs, kv, ks, vv, vs, do.contiguous().view(-1), os_, s["P"], dq.view(-1), dk.view(-1),
-                           dv.view(-1), B, Hl, Sq, Sk, kd, vd, scale)
+                           dv.view(-1), B, Hl, Sq, Sk, kd, vd, scale, key_lens=kl)
         else:
             q4 = qv.as_strided((B, Hl, Sq, kd), (qs[0], qs[1], qs[2], 1)).detach().float().requires_grad_()
             k4 = kv.as_strided((B, Hl, Sk, kd), (ks[0], ks[1], ks[2], 1)).detach().float().requires_grad_()
             v4 = vv.as_strided((B, Hl, Sk, vd), (vs[0], vs[1], vs[2], 1)).detach().float().requires_grad_()
             with torch.enable_grad():
-                out = _attn_ref(q4, k4, v4, scale, causal)
+                out = _attn_ref(q4, k4, v4, scale, causal, kl)
             g4 = do.permute(0, 2, 1, 3).float()
             gq, gk, gv = torch.autograd.grad(out, (q4, k4, v4), g4)
             dq.as_strided((B, Hl, Sq, kd), (qs[0], qs[1], qs[2], 1)).copy_(gq)
@@ -266,7 +301,7 @@ class MultiHeadAttention(OpImpl):
                                dx_out=acc.view(B * Sq, -1) if acc is not None else None, wt=s.get("wqkv_t"))
             dx = acc if acc is not None else dx2.view(B, Sq, -1)
             ctx.saved.clear()
-            return [dx, None, None]  # all three inputs are the same tensor: gradient once
+            return [dx, None, None] + no_kl_grad  # all three inputs are the same tensor: gradient once
         grads = []
         accs = ctx.extra.get("dx_accum") or {}
         for slot, (name, g, d, S_) in enumerate((("q", dq, kd, Sq), ("k", dk, kd, Sk), ("v", dv, vd, Sk))):
@@ -280,7 +315,7 @@ class MultiHeadAttention(OpImpl):
                                dx_out=acc.view(B * S_, -1) if acc is not None else None)
             grads.append(acc if acc is not None else dx2.view(B, S_, -1))
         ctx.saved.clear()
-        return grads
+        return grads + no_kl_grad
 
     def accumulates_dx(self):
         return True

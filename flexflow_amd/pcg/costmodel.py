@@ -197,9 +197,24 @@ def cost_key(layer, cfg: OpConfig, compute_dtype: DataType) -> tuple:
     lo = op_layouts(layer, cfg)
     need_dx0 = bool(layer.inputs) and layer.inputs[0].owner_layer is not None and \
         layer.inputs[0].owner_layer.op_type != OperatorType.OP_INPUT
-    return (layer.op_type, cost_params_key(layer), tuple(l.local_shape(0) for l in lo.inputs),
+    # an attention layer's key lengths are timed as a dense batch (fabricate_int_input), so they
+    # are left out of the key: the layer shares the measured entry of the same layer without them
+    n_in = 3 if layer.op_type == OperatorType.OP_MULTIHEAD_ATTENTION else len(lo.inputs)
+    return (layer.op_type, cost_params_key(layer), tuple(l.local_shape(0) for l in lo.inputs[:n_in]),
             tuple(l.local_shape(0) for l in lo.weights), cfg.degrees, compute_dtype, need_dx0,
-            tuple(_hot_inputs(layer)), (dact_fusion_partner(layer) or (None,))[0])
+            tuple(_hot_inputs(layer)[:n_in]), (dact_fusion_partner(layer) or (None,))[0])
+
+
+def fabricate_int_input(layer, i: int, shp, cfg: OpConfig, device) -> torch.Tensor:
+    """A stand-in for integer input i of `layer` when its cost is measured: embedding indices over
+    the local table, an attention layer's key lengths all equal to Sk (a dense batch: random small
+    lengths would time a nearly empty attention), otherwise 0 / 1."""
+    if layer.op_type == OperatorType.OP_MULTIHEAD_ATTENTION and i == 3:
+        return torch.full(tuple(shp), int(layer.inputs[1].dims[1]), device=device, dtype=torch.int32)
+    hi = 2
+    if layer.op_type == OperatorType.OP_EMBEDDING:
+        hi = layer.attrs["num_entries"] // max(1, cfg.degrees[-1])
+    return torch.randint(0, max(1, hi), tuple(shp), device=device, dtype=torch.int32)
 
 
 def measure_cost(layer, cfg: OpConfig, compute_dtype: DataType, device, reps: int = 8) -> Tuple[float, float]:
@@ -237,10 +252,7 @@ def measure_cost(layer, cfg: OpConfig, compute_dtype: DataType, device, reps: in
                 xs.append(shared[i])
                 continue
             if t.data_type in (DataType.DT_INT32, DataType.DT_INT64):
-                hi = 2
-                if layer.op_type == OperatorType.OP_EMBEDDING:
-                    hi = layer.attrs["num_entries"] // max(1, cfg.degrees[-1])
-                xs.append(torch.randint(0, max(1, hi), shp, device=device, dtype=torch.int32))
+                xs.append(fabricate_int_input(layer, i, shp, cfg, device))
             else:
                 xs.append(_step_layout(torch.randn(shp, device=device, dtype=ct)))
             if hot[i]:
