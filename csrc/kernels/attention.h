@@ -34,7 +34,27 @@ struct AttnArgs {
   // instantiations, which bound their mask tests and tile / key-block loops by it (memory bounds
   // stay on Sk). A sample of length 0 gives o = 0, lse = +inf and zero gradients.
   const int* key_lens = nullptr;
+  // attention dropout (attn_dropout.h): drop_thr = round(256 p) > 0 selects the DROP = true
+  // instantiations of attn_fwd_kernel / attn_bwd_kernel (always MASK = true; attn_fwd2_kernel and
+  // attn_bwd1b_kernel have none, so attn_bwd then leaves the fused bias gradient to the caller).
+  // rng_step is a one-element device counter read by the kernels (one scalar load per workgroup), so
+  // a captured step draws a new mask at every replay; rng_seed has seed and layer id folded in;
+  // drop_scale = 1 / (1 - drop_thr / 256); b0 / h0 are the shard's first global batch / head index
+  // and H_total the global head count. lse is that of the undropped softmax.
+  const int64_t* rng_step = nullptr;
+  uint64_t rng_seed = 0;
+  uint32_t drop_thr = 0;
+  float drop_scale = 1.f;
+  int b0 = 0, h0 = 0, H_total = 0;
 };
+
+// out[h][q][k] = keep(b, h0 + h, q, k) ? x[h][q][k] * drop_scale : 0 over an fp32 [H][Sq][Sk] slab of
+// global sample b (the fp32 device path: P[b] after the softmax, dP in the backward); out may be x
+void attn_dropout_f32(const float* x, float* out, int H, int Sq, int Sk, int b, int h0, int H_total,
+                      const int64_t* rng_step, uint64_t rng_seed, uint32_t drop_thr, float drop_scale, hipStream_t st);
+// the keep-mask itself as bytes [B][H][Sq][Sk] (tests, debugging)
+void attn_dropout_mask(uint8_t* out, int B, int H, int Sq, int Sk, int b0, int h0, int H_total,
+                       const int64_t* rng_step, uint64_t rng_seed, uint32_t drop_thr, hipStream_t st);
 
 void attn_fwd(AttnArgs a, hipStream_t st);
 bool attn_bwd(AttnArgs a, hipStream_t st);

@@ -20,6 +20,7 @@
 #include "common.h"
 #include "ops.h"
 #include "attention.h"
+#include "attn_dropout.h"
 #include <utility>
 
 namespace ffk {
@@ -135,8 +136,13 @@ __device__ __forceinline__ int key_limit(const AttnArgs& a, int b) {
 // xcd_remap: the query blocks of one (batch, head) share an XCD and its L2 copy of K / V. The O
 // tile leaves through LDS as whole rows (16 B per lane). Together -5 % at B32 H16 S512 D64
 // (scripts/lab/attn_fwd_lab.hip, profiles/attn_fwd_lab_r2.txt).
-template <int D, bool MASK, bool DMA>
-__global__ void __launch_bounds__(256, DMA ? 4 : 2) attn_fwd_kernel(AttnArgs a) {
+// DROP (attention dropout, attn_dropout.h): m, lsum and lse come from the undropped P; the bf16 P
+// operand of the PV MFMA is keep ? p : 0 and 1 / (1 - p_eff) is folded into the epilogue's inv. The
+// lane's row key is derived once, outside the tile loop; a tile costs one 32-bit hash per register
+// quad (4 consecutive keys). The DMA form sits exactly at the 128 registers of 4 workgroups per CU
+// and spilled 3 of them with DROP, so its DROP instantiation is bounded for 3.
+template <int D, bool MASK, bool DMA, bool DROP = false>
+__global__ void __launch_bounds__(256, DMA ? (DROP ? 3 : 4) : 2) attn_fwd_kernel(AttnArgs a) {
   constexpr int KV = 64;
   constexpr int TB = KV * D * 2;  // bytes of one K or V tile
   __shared__ __attribute__((aligned(16))) char smem[4 * TB];
@@ -162,6 +168,11 @@ __global__ void __launch_bounds__(256, DMA ? 4 : 2) attn_fwd_kernel(AttnArgs a) 
   for (int i = 0; i < D / 32; ++i) oacc[i] = f32x16{};
   float m = -INFINITY, lsum = 0.f;
   const float sl2 = a.scale * LOG2E;
+  uint32_t rkey = 0;
+  if constexpr (DROP) {
+    const int64_t step = a.rng_step ? *a.rng_step : 0;  // uniform: one scalar load per workgroup
+    rkey = attn_dropout_row_key(attn_dropout_head_key(a.rng_seed, step, (int64_t)(a.b0 + b) * a.H_total + a.h0 + hh), qrow);
+  }
 
   // This lane's fragment byte offsets inside a K / V tile image, computed once: the 32-row key
   // half (kt), the V tile and the double-buffer slot are additive (ds_read immediates; the swizzle
@@ -285,6 +296,17 @@ __global__ void __launch_bounds__(256, DMA ? 4 : 2) attn_fwd_kernel(AttnArgs a) 
     float rs = rs0 + rs1;
     rs += __shfl_xor(rs, 32, 64);
     lsum += rs;
+    if constexpr (DROP) {  // after the row sum: keys 4g..4g+3 of register quad g share one hash
+#pragma unroll
+      for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const uint32_t w = attn_dropout_word(rkey, (uint32_t)((kbase >> 2) + 8 * kt + 2 * g + h) * ADROP_KMUL);
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (((w >> (8 * j)) & 255u) < a.drop_thr) sacc[kt][4 * g + j] = 0.f;
+        }
+    }
     // O^T[d][q] += V^T[d][key] . P^T[key][q]
     bf16x8 pf[2][2];
 #pragma unroll
@@ -318,7 +340,8 @@ __global__ void __launch_bounds__(256, DMA ? 4 : 2) attn_fwd_kernel(AttnArgs a) 
   // image (16-B chunks XOR-swizzled by row & 7) -> whole-row 16-B stores
   __syncthreads();  // the last tile's V reads are done: the K/V buffers are free
   {
-    const float inv = lsum > 0.f ? 1.f / lsum : 0.f;
+    float inv = lsum > 0.f ? 1.f / lsum : 0.f;
+    if constexpr (DROP) inv *= a.drop_scale;
     const int row = wave * 32 + (lane & 31);
 #pragma unroll
     for (int dt = 0; dt < D / 32; ++dt)
@@ -695,7 +718,12 @@ __device__ __forceinline__ unsigned pack_bf2(float x, float y) {
 //  * DMA: the next Q / dO tile and its lse2 / delta rows go global -> LDS by buffer_load ... lds
 //    (no staging registers, no ds_write of the tile); vmcnt also counts stores, so the dQ tile's
 //    global stores are issued after the end-of-tile barrier, behind the wait for the DMA.
-template <int D, int NW, bool MASK, bool CHAIN, bool DMA = false>
+//  * DROP (attention dropout, attn_dropout.h): the 64 row keys of a query tile sit in the tile buffer
+//    behind lse2 / delta (computed by 64 lanes while the tile is fetched), the lane's key enters as
+//    one premultiplied constant, so an element costs one 32-bit hash. dV takes keep ? P : 0 (its
+//    1 / (1 - p_eff) in the epilogue), dP = keep ? dP_raw / (1 - p_eff) : 0, dS = P (dP - delta)
+//    with the undropped P; delta = rowsum(dO . O) holds because O carries the dropout.
+template <int D, int NW, bool MASK, bool CHAIN, bool DMA = false, bool DROP = false>
 __global__ void __launch_bounds__(64 * NW, 8 / NW) attn_bwd_kernel(AttnArgs a, int nkb, int pass) {
   constexpr int NT = 64 * NW;
   constexpr int QT = 64;       // queries per loop step
@@ -703,7 +731,7 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) attn_bwd_kernel(AttnArgs a, i
   constexpr int QB = QT * D * 2;
   // LDS: 2 x {Q tile, dO tile, lse, delta} (double-buffered: tile t+1 is fetched into registers
   // while tile t is computed), K block image, dS^T image [KB][QT]
-  constexpr int TILE = 2 * QB + 2 * QT * 4;
+  constexpr int TILE = 2 * QB + (DROP ? 3 : 2) * QT * 4;
   static_assert(2 * TILE >= KB * D * 2, "tile buffers stage the V block and the dV image");
   // dQ stage: NTILE (d x query) 32x32 tiles per q-tile; with more waves than tiles, KSPLIT waves
   // share a tile's key range and the upper parts hand their fp32 partial to part 0 through LDS
@@ -729,6 +757,15 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) attn_bwd_kernel(AttnArgs a, i
   const float* LSE = a.lse + (int64_t)bh * a.Sq;
   const float* DL = a.delta + (int64_t)bh * a.Sq;
   const float sl2 = a.scale * LOG2E;
+  uint64_t hkey = 0;  // DROP: this (batch, head)'s stream (wave-uniform)
+  uint32_t kmul = 0;  // DROP: the lane's key quad, premultiplied
+  int kshift = 0;     // DROP: the lane's byte of the quad's word
+  if constexpr (DROP) {
+    const int64_t step = a.rng_step ? *a.rng_step : 0;  // uniform: one scalar load per workgroup
+    hkey = attn_dropout_head_key(a.rng_seed, step, (int64_t)(a.b0 + b) * a.H_total + a.h0 + hh);
+    kmul = (uint32_t)(key >> 2) * ADROP_KMUL;
+    kshift = 8 * (key & 3);
+  }
   static_assert(!DMA || NW >= 2 * (D / 32), "DMA defers one dQ tile per wave past the barrier");
   // DMA: buffer resources over this (batch, head)'s Q / dO rows and lse2 / delta entries
   const int qbytes = (int)min((int64_t)0x7fffffff, ((int64_t)(a.Sq - 1) * a.q_ss + D) * 2);
@@ -794,6 +831,7 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) attn_bwd_kernel(AttnArgs a, i
     if (tid < QT) {
       reinterpret_cast<float*>(tb + 2 * QB)[tid] = lse_r;
       reinterpret_cast<float*>(tb + 2 * QB)[QT + tid] = dl_r;
+      if constexpr (DROP) reinterpret_cast<uint32_t*>(tb + 2 * QB)[2 * QT + tid] = attn_dropout_row_key(hkey, t * QT + tid);
     }
   };
   // DMA: tile t's Q / dO image (the TileStage layout) and lse2 / delta rows into buffer t & 1;
@@ -805,6 +843,9 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) attn_bwd_kernel(AttnArgs a, i
     if (wave == NW - 1) {
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rl, (lds_ptr_t)(tb + 2 * QB), 4, (t * QT + lane) * 4, 0, 0, 0);
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rdl, (lds_ptr_t)(tb + 2 * QB + QT * 4), 4, (t * QT + lane) * 4, 0, 0, 0);
+      // the tile's row keys: a plain LDS write by the same wave, ordered by the same barriers
+      if constexpr (DROP)
+        reinterpret_cast<uint32_t*>(tb + 2 * QB)[2 * QT + lane] = attn_dropout_row_key(hkey, t * QT + lane);
     }
   };
   if constexpr (DMA) {
@@ -837,7 +878,7 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) attn_bwd_kernel(AttnArgs a, i
     // now so its HBM round trip runs under the tile's MFMAs (read at its use below, the load sat on
     // the workgroup's critical path once per query tile)
     float4 prev[4];
-    if constexpr (NW >= 2 * (D / 32)) {
+    if constexpr (NW >= 2 * (D / 32) && !DROP) {  // DROP: these 16 registers made the chained forms spill
       const int tile = wave % (2 * (D / 32));
       const int q = qbase + 32 * (tile / (D / 32)) + (lane & 31);
       if (chain && kblk > 0 && wave < 2 * (D / 32) && (!MASK || q < a.Sq)) {
@@ -877,12 +918,32 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) attn_bwd_kernel(AttnArgs a, i
           }
         }
       }
+      unsigned keepm = 0;  // DROP: bit r = element r is kept
+      if constexpr (DROP) {
+        const uint32_t* rk_l = reinterpret_cast<const uint32_t*>(dl_l + QT);
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4) {
+          const uint4 R4 = *reinterpret_cast<const uint4*>(rk_l + 32 * qt + 8 * g4 + 4 * h);
+          const uint32_t rv[4] = {R4.x, R4.y, R4.z, R4.w};
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (((attn_dropout_word(rv[j], kmul) >> kshift) & 255u) >= a.drop_thr) keepm |= 1u << (4 * g4 + j);
+        }
+      }
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4) {
         const float4 D4 = *reinterpret_cast<const float4*>(dl_l + 32 * qt + 8 * g4 + 4 * h);
         const float dv4[4] = {D4.x, D4.y, D4.z, D4.w};
 #pragma unroll
-        for (int j = 0; j < 4; ++j) pacc[4 * g4 + j] = sacc[4 * g4 + j] * (pacc[4 * g4 + j] - dv4[j]);
+        for (int j = 0; j < 4; ++j) {
+          if constexpr (DROP) {
+            const bool kp = (keepm >> (4 * g4 + j)) & 1u;
+            pacc[4 * g4 + j] = sacc[4 * g4 + j] * ((kp ? pacc[4 * g4 + j] * a.drop_scale : 0.f) - dv4[j]);
+            if (!kp) sacc[4 * g4 + j] = 0.f;  // dV takes the dropped P
+          } else {
+            pacc[4 * g4 + j] = sacc[4 * g4 + j] * (pacc[4 * g4 + j] - dv4[j]);
+          }
+        }
       }
       const bf16x8 pb0 = pack8(sacc, 0), pb1 = pack8(sacc, 8);
       const bf16x8 sb0 = pack8(pacc, 0), sb1 = pack8(pacc, 8);
@@ -921,7 +982,7 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) attn_bwd_kernel(AttnArgs a, i
 #pragma unroll
           for (int g = 0; g < 4; ++g) {
             float4 pv;
-            if constexpr (NW >= 2 * (D / 32)) pv = prev[g];  // prefetched at the top of the tile
+            if constexpr (NW >= 2 * (D / 32) && !DROP) pv = prev[g];  // prefetched at the top of the tile
             else pv = *reinterpret_cast<const float4*>(prow + 8 * g);
             acc[4 * g] += pv.x; acc[4 * g + 1] += pv.y; acc[4 * g + 2] += pv.z; acc[4 * g + 3] += pv.w;
           }
@@ -1028,6 +1089,10 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) attn_bwd_kernel(AttnArgs a, i
         const int off = row * (D * 2) + ((c ^ (row & 7)) << 4) + 8 * h;
         *reinterpret_cast<uint2*>(k_l + off) = make_uint2(pack_bf2(dk[dt][4 * g] * a.scale, dk[dt][4 * g + 1] * a.scale),
                                                           pack_bf2(dk[dt][4 * g + 2] * a.scale, dk[dt][4 * g + 3] * a.scale));
+        if constexpr (DROP) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) dv[dt][4 * g + j] *= a.drop_scale;
+        }
         *reinterpret_cast<uint2*>(dv_l + off) = make_uint2(pack_bf2(dv[dt][4 * g], dv[dt][4 * g + 1]),
                                                            pack_bf2(dv[dt][4 * g + 2], dv[dt][4 * g + 3]));
       }
@@ -1562,6 +1627,48 @@ int attn_stagger() {
 }
 void attn_set_stagger(int v) { g_stagger = v != 0; }
 
+// ------------------------------------------------------- attention dropout outside the flash kernels
+__global__ void attn_dropout_f32_kernel(const float* __restrict__ x, float* __restrict__ out, int H, int Sq, int Sk,
+                                        int b, int h0, int H_total, const int64_t* __restrict__ rng_step,
+                                        uint64_t rng_seed, uint32_t thr, float scale) {
+  const int64_t n = (int64_t)H * Sq * Sk;
+  const int64_t step = rng_step ? *rng_step : 0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int k = (int)(i % Sk), q = (int)((i / Sk) % Sq), h = (int)(i / ((int64_t)Sk * Sq));
+    const bool keep = attn_dropout_keep(rng_seed, step, (int64_t)b * H_total + h0 + h, q, k, thr);
+    out[i] = keep ? x[i] * scale : 0.f;
+  }
+}
+
+void attn_dropout_f32(const float* x, float* out, int H, int Sq, int Sk, int b, int h0, int H_total,
+                      const int64_t* rng_step, uint64_t rng_seed, uint32_t drop_thr, float drop_scale, hipStream_t st) {
+  const int64_t n = (int64_t)H * Sq * Sk;
+  if (n <= 0) return;
+  hipLaunchKernelGGL(attn_dropout_f32_kernel, dim3(ew_grid(n, 256)), dim3(256), 0, st, x, out, H, Sq, Sk, b, h0,
+                     H_total, rng_step, rng_seed, drop_thr, drop_scale);
+}
+
+__global__ void attn_dropout_mask_kernel(uint8_t* __restrict__ out, int B, int H, int Sq, int Sk, int b0, int h0,
+                                         int H_total, const int64_t* __restrict__ rng_step, uint64_t rng_seed,
+                                         uint32_t thr) {
+  const int64_t n = (int64_t)B * H * Sq * Sk;
+  const int64_t step = rng_step ? *rng_step : 0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int k = (int)(i % Sk), q = (int)((i / Sk) % Sq);
+    const int64_t bh = i / ((int64_t)Sk * Sq);
+    const int h = (int)(bh % H), b = (int)(bh / H);
+    out[i] = attn_dropout_keep(rng_seed, step, (int64_t)(b0 + b) * H_total + h0 + h, q, k, thr) ? 1 : 0;
+  }
+}
+
+void attn_dropout_mask(uint8_t* out, int B, int H, int Sq, int Sk, int b0, int h0, int H_total,
+                       const int64_t* rng_step, uint64_t rng_seed, uint32_t drop_thr, hipStream_t st) {
+  const int64_t n = (int64_t)B * H * Sq * Sk;
+  if (n <= 0) return;
+  hipLaunchKernelGGL(attn_dropout_mask_kernel, dim3(ew_grid(n, 256)), dim3(256), 0, st, out, B, H, Sq, Sk, b0, h0,
+                     H_total, rng_step, rng_seed, drop_thr);
+}
+
 void attn_fwd(AttnArgs a, hipStream_t st) {
   const dim3 grid((unsigned)((a.Sq + 127) / 128 * a.B * a.H));
   const bool mask = a.causal || a.Sk % 64 != 0 || a.key_lens != nullptr;
@@ -1571,6 +1678,19 @@ void attn_fwd(AttnArgs a, hipStream_t st) {
                       a.v_ss % 8 == 0 && (int64_t)(a.Sk + 64) * a.k_ss * 2 < 0x7fffffffLL &&
                       (int64_t)(a.Sk + 64) * a.v_ss * 2 < 0x7fffffffLL;
   const bool dma = attn_fwd_variant() >= 1 && dma_ok;
+  if (a.drop_thr > 0) {
+    // attention dropout: the DROP instantiations of the 4-wave kernel (always MASK = true);
+    // attn_fwd2_kernel's DROP form (230 VGPRs, no scratch) measured slower than this kernel's: 60.1
+    // against 57.8 us at B32 H16 S512 (docs/PERFORMANCE.md, 'Attention dropout'), so it has none
+    if (a.H_total <= 0) a.H_total = a.H;
+    if (a.D == 64) {
+      if (dma) hipLaunchKernelGGL((attn_fwd_kernel<64, true, true, true>), grid, dim3(256), 0, st, a);
+      else hipLaunchKernelGGL((attn_fwd_kernel<64, true, false, true>), grid, dim3(256), 0, st, a);
+    } else if (a.D == 128) {
+      hipLaunchKernelGGL((attn_fwd_kernel<128, true, false, true>), grid, dim3(256), 0, st, a);
+    }
+    return;
+  }
   // 64 query rows per wave (attn_fwd2_kernel): 2-6 % faster from S = 512 up, slower at S = 256
   // (half the workgroups), profiles/attn_fwd_variants_r4.txt
   if (attn_fwd_variant() == 3 && dma_ok && a.D == 64 && a.Sq >= 512) {
@@ -1593,6 +1713,18 @@ void attn_fwd(AttnArgs a, hipStream_t st) {
   }
 }
 
+// attention dropout: the DROP instantiations of attn_bwd_kernel (always MASK = true)
+template <int D, int NW, bool DMA = false>
+static void launch_bwd_drop(AttnArgs a, int nkb, bool chain, hipStream_t st) {
+  const int bh = a.B * a.H;
+  if (chain) {
+    for (int p = 0; p < nkb; ++p)
+      hipLaunchKernelGGL((attn_bwd_kernel<D, NW, true, true, DMA, true>), dim3(bh), dim3(64 * NW), 0, st, a, nkb, p);
+  } else {
+    hipLaunchKernelGGL((attn_bwd_kernel<D, NW, true, false, DMA, true>), dim3(bh * nkb), dim3(64 * NW), 0, st, a, nkb, 0);
+  }
+}
+
 template <int D, int NW, bool DMA = false>
 static void launch_bwd_main(AttnArgs a, int nkb, bool chain, hipStream_t st) {
   const bool mask = a.causal || a.Sk % (32 * NW) != 0 || a.Sq % 64 != 0 || a.key_lens != nullptr;
@@ -1610,6 +1742,8 @@ static void launch_bwd_main(AttnArgs a, int nkb, bool chain, hipStream_t st) {
 
 bool attn_bwd(AttnArgs a, hipStream_t st) {
   bool bias_done = false;
+  const bool drop = a.drop_thr > 0;
+  if (drop && a.H_total <= 0) a.H_total = a.H;
   a.stagger = attn_stagger();
   const int v = attn_bwd_variant();
   const int nkb = (a.Sk + bwd_keys(a.D) - 1) / bwd_keys(a.D);
@@ -1628,7 +1762,12 @@ bool attn_bwd(AttnArgs a, hipStream_t st) {
                       (int64_t)(a.Sq + 64) * a.do_ss * 2 < 0x7fffffffLL;
   if (a.D == 64) {
     hipLaunchKernelGGL(attn_bwd_pre_kernel<64>, gpre, dim3(256), 0, st, a);
-    if (chain && dma_ok) {
+    if (drop) {
+      // attn_bwd1b_kernel has no DROP instantiation (it uses every VGPR already): the generic kernel
+      // runs the chained form too, and the fused bias gradient is left to the caller (returns false)
+      if (dma_ok) launch_bwd_drop<64, 8, true>(a, nkb, chain, st);
+      else launch_bwd_drop<64, 8>(a, nkb, chain, st);
+    } else if (chain && dma_ok) {
       const bool m = a.causal || a.Sk % 256 != 0 || a.Sq % 64 != 0 || a.key_lens != nullptr;
       const int bh = a.B * a.H;
       // fused bias-gradient sums: non-causal (every query tile's last key block is the last launch)
@@ -1646,7 +1785,8 @@ bool attn_bwd(AttnArgs a, hipStream_t st) {
     if (finish) hipLaunchKernelGGL(attn_dq_finish_kernel<64>, gfin, dim3(256), 0, st, a, nkb);
   } else if (a.D == 128) {
     hipLaunchKernelGGL(attn_bwd_pre_kernel<128>, gpre, dim3(256), 0, st, a);
-    launch_bwd_main<128, 4>(a, nkb, chain, st);
+    if (drop) launch_bwd_drop<128, 4>(a, nkb, chain, st);
+    else launch_bwd_main<128, 4>(a, nkb, chain, st);
     if (finish) hipLaunchKernelGGL(attn_dq_finish_kernel<128>, gfin, dim3(256), 0, st, a, nkb);
   }
   if (bias_done)

@@ -622,10 +622,30 @@ const int* attn_key_lens(const optional<Tensor>& key_lens, const Tensor& q, int6
   return key_lens->data_ptr<int>();
 }
 
+// attention dropout (attn_dropout.h): drop_thr = round(256 p) (0: none), rng_step a one-element int64
+// counter on q's device (read there only; null: step 0), rng_seed with seed and layer id folded in
+// (passed as int64 bits), b0 / h0 / H_total the shard's place among the global batch / heads
+void attn_drop_args(ffk::AttnArgs& a, const Tensor& q, int64_t drop_thr, const optional<Tensor>& rng_step,
+                    int64_t rng_seed, int64_t b0, int64_t h0, int64_t H_total, int64_t H) {
+  TORCH_CHECK(drop_thr >= 0 && drop_thr < 256, "attn: drop_thr must be round(256 p) in [0, 255]");
+  if (drop_thr == 0) return;
+  if (rng_step.has_value() && rng_step->defined()) {
+    TORCH_CHECK(rng_step->scalar_type() == at::kLong && rng_step->numel() == 1 && rng_step->device() == q.device(),
+                "attn: rng_step must be a one-element int64 tensor on the device of q");
+    a.rng_step = rng_step->data_ptr<int64_t>();
+  }
+  a.rng_seed = (uint64_t)rng_seed;
+  a.drop_thr = (uint32_t)drop_thr;
+  a.drop_scale = 256.f / (float)(256 - drop_thr);
+  a.b0 = (int)b0; a.h0 = (int)h0; a.H_total = (int)(H_total > 0 ? H_total : H);
+  TORCH_CHECK(b0 >= 0 && h0 >= 0 && h0 + H <= a.H_total, "attn: head shard outside H_total");
+}
+
 // q/k/v/o given with explicit [b,h,s] element strides (d contiguous)
 void attn_fwd(Tensor q, std::vector<int64_t> qs, Tensor k, std::vector<int64_t> ks, Tensor v,
               std::vector<int64_t> vs, Tensor o, std::vector<int64_t> os, Tensor lse, int64_t B, int64_t H,
-              int64_t Sq, int64_t Sk, int64_t D, double scale, bool causal, optional<Tensor> key_lens) {
+              int64_t Sq, int64_t Sk, int64_t D, double scale, bool causal, optional<Tensor> key_lens,
+              int64_t drop_thr, optional<Tensor> rng_step, int64_t rng_seed, int64_t b0, int64_t h0, int64_t H_total) {
   TORCH_CHECK(D == 64 || D == 128, "flash attention supports head_dim 64/128");
   TORCH_CHECK(q.scalar_type() == at::kBFloat16 && o.scalar_type() == at::kBFloat16);
   TORCH_CHECK(lse.numel() >= B * H * Sq && lse.scalar_type() == at::kFloat);
@@ -638,6 +658,7 @@ void attn_fwd(Tensor q, std::vector<int64_t> qs, Tensor k, std::vector<int64_t> 
   a.lse = lse.data_ptr<float>();
   a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.D = D; a.scale = scale; a.causal = causal;
   a.key_lens = attn_key_lens(key_lens, q, B);
+  attn_drop_args(a, q, drop_thr, rng_step, rng_seed, b0, h0, H_total, H);
   ffk::attn_fwd(a, cur_stream());
 }
 int64_t attn_bwd_ws(int64_t B, int64_t H, int64_t Sq, int64_t Sk, int64_t D) {
@@ -647,7 +668,8 @@ bool attn_bwd(Tensor q, std::vector<int64_t> qs, Tensor k, std::vector<int64_t> 
               std::vector<int64_t> vs, Tensor o, std::vector<int64_t> os, Tensor dout, std::vector<int64_t> dos,
               Tensor lse, Tensor dq, std::vector<int64_t> dqs, Tensor dk, std::vector<int64_t> dks, Tensor dv,
               std::vector<int64_t> dvs, Tensor ws, int64_t B, int64_t H, int64_t Sq, int64_t Sk, int64_t D,
-              double scale, bool causal, optional<Tensor> dbias, optional<Tensor> key_lens) {
+              double scale, bool causal, optional<Tensor> dbias, optional<Tensor> key_lens, int64_t drop_thr,
+              optional<Tensor> rng_step, int64_t rng_seed, int64_t b0, int64_t h0, int64_t H_total) {
   TORCH_CHECK(D == 64 || D == 128, "flash attention supports head_dim 64/128");
   TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.numel() >= ffk::attn_bwd_workspace_floats(B, H, Sq, Sk, D),
               "attn_bwd: workspace too small");
@@ -673,7 +695,40 @@ bool attn_bwd(Tensor q, std::vector<int64_t> qs, Tensor k, std::vector<int64_t> 
   }
   a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.D = D; a.scale = scale; a.causal = causal;
   a.key_lens = attn_key_lens(key_lens, q, B);
+  attn_drop_args(a, q, drop_thr, rng_step, rng_seed, b0, h0, H_total, H);
   return ffk::attn_bwd(a, cur_stream());
+}
+
+// out = keep ? x * 1 / (1 - p_eff) : 0 over the fp32 [H, Sq, Sk] slab of global sample b (out may be x)
+void attn_dropout_f32(Tensor x, Tensor out, int64_t H, int64_t Sq, int64_t Sk, int64_t b, int64_t h0, int64_t H_total,
+                      int64_t drop_thr, optional<Tensor> rng_step, int64_t rng_seed) {
+  check_dev(x, "x");
+  TORCH_CHECK(x.scalar_type() == at::kFloat && out.scalar_type() == at::kFloat && x.is_contiguous() &&
+              out.is_contiguous() && x.numel() == H * Sq * Sk && out.numel() == x.numel() && out.device() == x.device());
+  TORCH_CHECK(drop_thr > 0 && drop_thr < 256 && b >= 0 && h0 >= 0 && h0 + H <= H_total);
+  const int64_t* step = nullptr;
+  if (rng_step.has_value() && rng_step->defined()) {
+    TORCH_CHECK(rng_step->scalar_type() == at::kLong && rng_step->numel() == 1 && rng_step->device() == x.device());
+    step = rng_step->data_ptr<int64_t>();
+  }
+  ffk::attn_dropout_f32(x.data_ptr<float>(), out.data_ptr<float>(), (int)H, (int)Sq, (int)Sk, (int)b, (int)h0,
+                        (int)H_total, step, (uint64_t)rng_seed, (uint32_t)drop_thr, 256.f / (float)(256 - drop_thr),
+                        cur_stream());
+}
+
+// the keep-mask the kernels draw, as uint8 [B, H, Sq, Sk]
+void attn_dropout_mask(Tensor out, int64_t B, int64_t H, int64_t Sq, int64_t Sk, int64_t b0, int64_t h0,
+                       int64_t H_total, int64_t drop_thr, optional<Tensor> rng_step, int64_t rng_seed) {
+  check_dev(out, "out");
+  TORCH_CHECK(out.scalar_type() == at::kByte && out.is_contiguous() && out.numel() == B * H * Sq * Sk);
+  TORCH_CHECK(drop_thr > 0 && drop_thr < 256 && b0 >= 0 && h0 >= 0 && h0 + H <= H_total);
+  const int64_t* step = nullptr;
+  if (rng_step.has_value() && rng_step->defined()) {
+    TORCH_CHECK(rng_step->scalar_type() == at::kLong && rng_step->numel() == 1 && rng_step->device() == out.device());
+    step = rng_step->data_ptr<int64_t>();
+  }
+  ffk::attn_dropout_mask(out.data_ptr<uint8_t>(), (int)B, (int)H, (int)Sq, (int)Sk, (int)b0, (int)h0, (int)H_total,
+                         step, (uint64_t)rng_seed, (uint32_t)drop_thr, cur_stream());
 }
 
 
@@ -988,12 +1043,18 @@ PYBIND11_MODULE(_C, m) {
   m.def("aggregate_bwd", &aggregate_bwd);
   m.def("attn_fwd", &attn_fwd, py::arg("q"), py::arg("qs"), py::arg("k"), py::arg("ks"), py::arg("v"), py::arg("vs"),
         py::arg("o"), py::arg("os"), py::arg("lse"), py::arg("B"), py::arg("H"), py::arg("Sq"), py::arg("Sk"),
-        py::arg("D"), py::arg("scale"), py::arg("causal"), py::arg("key_lens") = py::none());
+        py::arg("D"), py::arg("scale"), py::arg("causal"), py::arg("key_lens") = py::none(),
+        py::arg("drop_thr") = 0, py::arg("rng_step") = py::none(), py::arg("rng_seed") = 0, py::arg("b0") = 0,
+        py::arg("h0") = 0, py::arg("H_total") = 0);
   m.def("attn_bwd", &attn_bwd, py::arg("q"), py::arg("qs"), py::arg("k"), py::arg("ks"), py::arg("v"), py::arg("vs"),
         py::arg("o"), py::arg("os"), py::arg("dout"), py::arg("dos"), py::arg("lse"), py::arg("dq"), py::arg("dqs"),
         py::arg("dk"), py::arg("dks"), py::arg("dv"), py::arg("dvs"), py::arg("ws"), py::arg("B"), py::arg("H"),
         py::arg("Sq"), py::arg("Sk"), py::arg("D"), py::arg("scale"), py::arg("causal"),
-        py::arg("dbias") = py::none(), py::arg("key_lens") = py::none());
+        py::arg("dbias") = py::none(), py::arg("key_lens") = py::none(), py::arg("drop_thr") = 0,
+        py::arg("rng_step") = py::none(), py::arg("rng_seed") = 0, py::arg("b0") = 0, py::arg("h0") = 0,
+        py::arg("H_total") = 0);
+  m.def("attn_dropout_f32", &attn_dropout_f32);
+  m.def("attn_dropout_mask", &attn_dropout_mask);
   m.def("attn_bwd_ws", &attn_bwd_ws);
   m.def("attn_set_bwd_variant", [](int v) { ffk::attn_set_bwd_variant(v); });
   m.def("attn_fwd_variant", []() { return ffk::attn_fwd_variant(); });

@@ -288,7 +288,11 @@ class FFModel:
                             add_bias_kv=False, add_zero_attn=False, kernel_initializer=None, causal=False, name=None,
                             key_lengths=None):
         """key_lengths: optional int32 tensor [batch] (or [batch, 1]) of a right-padded batch: sample b
-        attends to its first key_lengths[b] keys only (ops/attention.py)."""
+        attends to its first key_lengths[b] keys only (ops/attention.py).
+        dropout: attention-probability dropout rate in [0, 1), torch's dropout_p semantics; applied in
+        training forwards only, at the effective rate round(256 p) / 256 (ops/attention.py)."""
+        if not 0.0 <= float(dropout) < 1.0:
+            raise ValueError(f"multihead_attention: dropout must be in [0, 1), got {dropout}")
         ins = [query, key, value] + ([key_lengths] if key_lengths is not None else [])
         return self._add(OperatorType.OP_MULTIHEAD_ATTENTION, ins, name, embed_dim=int(embed_dim),
                          num_heads=int(num_heads), kdim=int(kdim), vdim=int(vdim), dropout=float(dropout), bias=bias,

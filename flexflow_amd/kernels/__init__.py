@@ -974,18 +974,95 @@ def attn_key_lens(key_lens, B, device):
     return kl
 
 
-def flash_attn_fwd(q, qs, k, ks, v, vs, o, os_, B, H, Sq, Sk, D, scale, causal, key_lens=None):
+# ---- attention dropout: csrc/kernels/attn_dropout.h is the device definition, this is its mirror
+_ADROP_GOLD = 0x9E3779B97F4A7C15
+_ADROP_STEP = 0xD1B54A32D192ED03
+_ADROP_KMUL = 0x9E3779B1
+
+
+def attn_dropout_thr(p) -> int:
+    """8-bit drop threshold round(256 p) of an attention dropout rate p in [0, 1): an element is
+    dropped iff its hash byte is below it, so the effective rate is p_eff = thr / 256 (and the
+    kept elements are scaled by 256 / (256 - thr)). 0 means no dropout."""
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"attention dropout rate must be in [0, 1), got {p}")
+    return min(int(256.0 * p + 0.5), 255)
+
+
+def attn_dropout_seed(seed, layer_id) -> int:
+    """seed and layer id folded into the 64-bit stream key the kernels take (unsigned)."""
+    M = (1 << 64) - 1
+    return _mix64((int(seed) * _ADROP_GOLD + int(layer_id)) & M)
+
+
+def _xshift(z, s):  # logical right shift of a wrapped (signed) int64 tensor
+    return (z >> s) & ((1 << (64 - s)) - 1)
+
+
+def _mix64_t(z):
+    z = (z ^ _xshift(z, 30)) * _to_signed(0xBF58476D1CE4E5B9)
+    z = (z ^ _xshift(z, 27)) * _to_signed(0x94D049BB133111EB)
+    return z ^ _xshift(z, 31)
+
+
+def attn_dropout_keep_ref(seed, layer_id, step, B, H, Sq, Sk, p, b0=0, h0=0, H_total=None, device="cpu"):
+    """The attention dropout keep-mask as bool [B, H, Sq, Sk]: element [b, h, q, k] is that of
+    global sample b0 + b and global head h0 + h (of H_total heads; default H) of layer `layer_id`
+    in training step `step` (an int, or a one-element int64 tensor that is read on its device only).
+    A pure function of (seed, layer_id, step, b, h, q, k), evaluated with wrapped int64 torch ops
+    exactly as attn_dropout.h evaluates it on the device."""
+    thr = attn_dropout_thr(p)
+    H_total = H if H_total is None else int(H_total)
+    dev = torch.device(device)
+    i64 = dict(dtype=torch.int64, device=dev)
+    step_t = step.to(**i64).reshape(()) if isinstance(step, torch.Tensor) else torch.tensor(int(step), **i64)
+    s = _mix64_t(step_t * _to_signed(_ADROP_STEP) + _to_signed(attn_dropout_seed(seed, layer_id)))
+    bh = ((torch.arange(B, **i64) + int(b0))[:, None] * H_total + (torch.arange(H, **i64) + int(h0))[None, :])
+    hk = _mix64_t(s + bh * _to_signed(_ADROP_GOLD))  # [B, H]
+    rk = _xshift(_mix64_t(hk[:, :, None] + torch.arange(Sq, **i64) * _to_signed(_ADROP_GOLD)), 32)  # [B, H, Sq]
+    m32 = 0xFFFFFFFF
+    kq = torch.arange((Sk + 3) // 4, **i64)
+    x = (rk[..., None] + kq * _ADROP_KMUL) & m32  # [B, H, Sq, Sk/4]
+    x = ((x ^ (x >> 16)) * 0x85EBCA6B) & m32
+    x = ((x ^ (x >> 13)) * 0xC2B2AE35) & m32
+    x = x ^ (x >> 16)
+    byts = (x[..., None] >> (8 * torch.arange(4, **i64))) & 255  # [B, H, Sq, Sk/4, 4]
+    return (byts >= thr).reshape(B, H, Sq, -1)[..., :Sk]
+
+
+def attn_dropout_mask(B, H, Sq, Sk, thr, rng_step, rng_seed, b0=0, h0=0, H_total=None, device=None):
+    """The keep-mask as the device function draws it (attn_dropout_mask_kernel): bool [B, H, Sq, Sk]."""
+    out = torch.empty(B, H, Sq, Sk, dtype=torch.uint8, device=device if device is not None else rng_step.device)
+    ext().attn_dropout_mask(out, B, H, Sq, Sk, b0, h0, H if H_total is None else H_total, thr, rng_step,
+                            _to_signed(rng_seed))
+    return out.bool()
+
+
+def _drop_kw(drop):
+    """drop: None or (thr, rng_step, rng_seed, b0, h0, H_total) -> the bindings' keyword arguments."""
+    if not drop or not drop[0]:
+        return {}
+    thr, step, seed, b0, h0, H_total = drop
+    return dict(drop_thr=int(thr), rng_step=step, rng_seed=_to_signed(int(seed)), b0=int(b0), h0=int(h0),
+                H_total=int(H_total))
+
+
+def flash_attn_fwd(q, qs, k, ks, v, vs, o, os_, B, H, Sq, Sk, D, scale, causal, key_lens=None, drop=None):
     """key_lens: optional int32 [B] device tensor; key j of sample b is attended iff j < key_lens[b]
-    (a length of 0: o = 0, lse = +inf)."""
+    (a length of 0: o = 0, lse = +inf). drop: optional attention dropout (thr, rng_step, rng_seed, b0,
+    h0, H_total), see _drop_kw / attn_dropout_keep_ref; lse is that of the undropped softmax."""
     lse = torch.empty(B * H * Sq, device=q.device, dtype=torch.float32)
     ext().attn_fwd(q, qs, k, ks, v, vs, o, os_, lse, B, H, Sq, Sk, D, scale, causal,
-                   attn_key_lens(key_lens, B, q.device))
+                   attn_key_lens(key_lens, B, q.device), **_drop_kw(drop))
     return lse
 
 
 def flash_attn_bwd(q, qs, k, ks, v, vs, o, os_, do, dos, lse, dq, dqs, dk, dks, dv, dvs, B, H, Sq, Sk, D, scale,
-                   causal, dbias=None, key_lens=None):
+                   causal, dbias=None, key_lens=None, drop=None):
     """key_lens: as in flash_attn_fwd; dk / dv rows at or past a sample's length are written as zeros.
+    drop: as in flash_attn_fwd, with the counter value the forward saw; the dropout kernels never fuse
+    the bias gradient (returns False).
     dbias: optional contiguous fp32 [3*H*D] bias gradient of a fused [B,S,3,H,D] QKV projection
     (dq/dk/dv inside one dqkv buffer). Returns True when the kernel added the column sums of dq / dk /
     dv into it (attn_bwd1b_kernel, non-causal); False: the caller still owes that bias gradient."""
@@ -994,7 +1071,7 @@ def flash_attn_bwd(q, qs, k, ks, v, vs, o, os_, do, dos, lse, dq, dqs, dk, dks, 
     # dQ partial slabs + delta: one arena buffer shared (stream-ordered) by every attention layer
     ws = DeviceContext.get(q.device).workspace("attn_bwd", X.attn_bwd_ws(B, H, Sq, Sk, D))
     return bool(X.attn_bwd(q, qs, k, ks, v, vs, o, os_, do, dos, lse, dq, dqs, dk, dks, dv, dvs, ws, B, H, Sq, Sk, D,
-                           scale, causal, dbias, attn_key_lens(key_lens, B, q.device)))
+                           scale, causal, dbias, attn_key_lens(key_lens, B, q.device), **_drop_kw(drop)))
 
 
 # ---------------------------------------------------------------------------- layer norm
@@ -1988,13 +2065,17 @@ def attn_f32_supported(x) -> bool:
     return native(x) and x.dtype == torch.float32
 
 
-def attn_f32_fwd(q, qs, k, ks, v, vs, o, os_, B, H, Sq, Sk, kd, vd, scale, causal, key_lens=None):
+def attn_f32_fwd(q, qs, k, ks, v, vs, o, os_, B, H, Sq, Sk, kd, vd, scale, causal, key_lens=None, drop=None):
     """fp32 attention on our kernels, per sample: S = Q.K^T (f32 MFMA GEMM, heads as the batch),
     causal mask, key-length mask (key_lens: int32 [B] on the device, columns >= key_lens[b] set to
     -inf there), row softmax(scale * S) (softmax.hip), the same columns of P set to 0 (a sample of
     length 0 has P = 0, not the softmax's NaN), O = P.V. q/k/v/o are flat views with [b, h, row] element strides (qs, ks, vs, os_) and contiguous head dims.
+    drop (as in flash_attn_fwd): the PV GEMM takes keep ? P / (1 - p_eff) : 0 (attn_dropout_f32 on P[b]);
+    the P returned is the undropped one, for softmax_bwd.
     Returns P [B, H, Sq, Sk]."""
     X = ext()
+    dkw = _drop_kw(drop)
+    Pd = torch.empty(H, Sq, Sk, device=q.device, dtype=torch.float32) if dkw else None
     key_lens = attn_key_lens(key_lens, B, q.device)
     q, k, v, o = q.reshape(-1), k.reshape(-1), v.reshape(-1), o.reshape(-1)
     P = torch.empty(B, H, Sq, Sk, device=q.device, dtype=torch.float32)
@@ -2009,17 +2090,25 @@ def attn_f32_fwd(q, qs, k, ks, v, vs, o, os_, B, H, Sq, Sk, kd, vd, scale, causa
         X.softmax_fwd(S, P[b], H * Sq, Sk, scale)
         if key_lens is not None:  # a sample without keys: its all -inf rows came out NaN, P is 0 there
             X.key_len_mask_f32(P[b], key_lens, b, Sk, 0.0)
-        X.gemm_f32(P[b], v[b * vs[0]:], o[b * os_[0]:], None, None, Sq, vd, Sk, Sk, vs[2], os_[2], Sq * Sk, vs[1],
+        Pb = P[b]
+        if dkw:
+            X.attn_dropout_f32(P[b], Pd, H, Sq, Sk, dkw["b0"] + b, dkw["h0"], dkw["H_total"], dkw["drop_thr"],
+                               dkw["rng_step"], dkw["rng_seed"])
+            Pb = Pd
+        X.gemm_f32(Pb, v[b * vs[0]:], o[b * os_[0]:], None, None, Sq, vd, Sk, Sk, vs[2], os_[2], Sq * Sk, vs[1],
                    os_[1], H, True, False, 1.0, 0.0, ACT_NONE)
     return P
 
 
-def attn_f32_bwd(q, qs, k, ks, v, vs, do, dos, P, dq, dk, dv, B, H, Sq, Sk, kd, vd, scale, key_lens=None):
+def attn_f32_bwd(q, qs, k, ks, v, vs, do, dos, P, dq, dk, dv, B, H, Sq, Sk, kd, vd, scale, key_lens=None, drop=None):
     """Backward of attn_f32_fwd: dP = dO.V^T, dS = scale * P * (dP - rowsum(dP * P)), dQ = dS.K,
     dK = dS^T.Q, dV = P^T.dO (dq / dk / dv share q / k / v's strides). key_lens needs no work here:
     the forward left P = 0 in the masked columns, so dS is 0 there and the dK / dV rows at or past a
-    sample's length come out as zeros (all of a length-0 sample's gradients do)."""
+    sample's length come out as zeros (all of a length-0 sample's gradients do). drop (with the
+    counter value of the forward): dP and the P of the dV GEMM go through attn_dropout_f32."""
     X = ext()
+    dkw = _drop_kw(drop)
+    Pd = torch.empty(H, Sq, Sk, device=q.device, dtype=torch.float32) if dkw else None
     q, k, v, do = q.reshape(-1), k.reshape(-1), v.reshape(-1), do.reshape(-1)
     dq, dk, dv = dq.reshape(-1), dk.reshape(-1), dv.reshape(-1)
     dP = torch.empty(H, Sq, Sk, device=q.device, dtype=torch.float32)
@@ -2027,10 +2116,16 @@ def attn_f32_bwd(q, qs, k, ks, v, vs, do, dos, P, dq, dk, dv, B, H, Sq, Sk, kd, 
     for b in range(B):
         X.gemm_f32(do[b * dos[0]:], v[b * vs[0]:], dP, None, None, Sq, Sk, vd, dos[2], vs[2], Sk, dos[1], vs[1],
                    Sq * Sk, H, True, True, 1.0, 0.0, ACT_NONE)
+        Pb = P[b]
+        if dkw:
+            da = (H, Sq, Sk, dkw["b0"] + b, dkw["h0"], dkw["H_total"], dkw["drop_thr"], dkw["rng_step"], dkw["rng_seed"])
+            X.attn_dropout_f32(dP, dP, *da)
+            X.attn_dropout_f32(P[b], Pd, *da)
+            Pb = Pd
         X.softmax_bwd(P[b], dP, dS, H * Sq, Sk, scale, False)
         X.gemm_f32(dS, k[b * ks[0]:], dq[b * qs[0]:], None, None, Sq, kd, Sk, Sk, ks[2], qs[2], Sq * Sk, ks[1],
                    qs[1], H, True, False, 1.0, 0.0, ACT_NONE)
         X.gemm_f32(dS, q[b * qs[0]:], dk[b * ks[0]:], None, None, Sk, kd, Sq, Sk, qs[2], ks[2], Sq * Sk, qs[1],
                    ks[1], H, False, False, 1.0, 0.0, ACT_NONE)
-        X.gemm_f32(P[b], do[b * dos[0]:], dv[b * vs[0]:], None, None, Sk, vd, Sq, Sk, dos[2], vs[2], Sq * Sk,
+        X.gemm_f32(Pb, do[b * dos[0]:], dv[b * vs[0]:], None, None, Sk, vd, Sq, Sk, dos[2], vs[2], Sq * Sk,
                    dos[1], vs[1], H, False, False, 1.0, 0.0, ACT_NONE)

@@ -26,6 +26,9 @@ class BertConfig:
     max_pos: int = 512
     seq: int = 512
     dropout: float = 0.0
+    # attention-probability dropout of every layer (ops/attention.py); `dropout` above only drives
+    # the hidden-state dropout layers
+    attn_dropout: float = 0.0
     mlm_head: bool = True
 
     @staticmethod
@@ -71,7 +74,8 @@ def build_bert(ff, batch: int, cfg: BertConfig, key_lengths=None):
     x = ff.add(x, p, name="emb_add")
     x = ff.layer_norm(x, [-1], name="emb_ln")
     for l in range(cfg.layers):
-        a = ff.multihead_attention(x, x, x, H, cfg.heads, name=f"l{l}_attn", key_lengths=key_lengths)
+        a = ff.multihead_attention(x, x, x, H, cfg.heads, dropout=cfg.attn_dropout, name=f"l{l}_attn",
+                                   key_lengths=key_lengths)
         if cfg.dropout > 0:
             a = ff.dropout(a, cfg.dropout, l, name=f"l{l}_attn_drop")
         x = ff.layer_norm(ff.add(a, x, name=f"l{l}_res1"), [-1], name=f"l{l}_ln1")

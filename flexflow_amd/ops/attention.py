@@ -18,11 +18,24 @@ key_padding_mask); L_b = 0 gives zero output rows and zero gradients. The length
 device only, by every path (flash, zero-padded head dims, fp32 device, reference, CPU), so a step
 that takes them still captures into a graph. Not covered: arbitrary masks, query-side skipping or
 packing, loss masking.
+
+Attention dropout (`dropout` = p in [0, 1), torch's `dropout_p`): in a training forward every
+attention probability is dropped with the effective rate p_eff = round(256 p) / 256 and the kept ones
+are scaled by 1 / (1 - p_eff); evaluation forwards apply nothing, and p_eff = 0 runs exactly the
+kernels of a layer without dropout. Whether element (b, h, q, k) is kept is a pure function of
+(seed, layer id, step, b, h, q, k) with GLOBAL batch and head indices (csrc/kernels/attn_dropout.h,
+mirrored by kernels.attn_dropout_keep_ref), so every path (flash kernels, zero-padded head dims,
+fp32 device, reference, CPU) and every shard draws the mask a 1-GPU run draws. The layer id is the
+CRC-32 of the layer name; the step is the executor's device-side counter (`ctx.rng_step`, read by
+the kernels on the device, so a captured step draws a new mask at every replay; step 0 without an
+executor). The flash kernels generate the mask themselves, forward and backward, from the same
+counters: P is never materialised.
 """
 from __future__ import annotations
 
 import math
 import os
+import zlib
 
 import torch
 
@@ -38,13 +51,18 @@ def _pad_heads(t, st, B, S, H, d, Dp):
     return out
 
 
-def _attn_ref(q, k, v, scale, causal, key_lens=None):
+def _attn_ref(q, k, v, scale, causal, key_lens=None, keep=None, keep_scale=1.0):
+    """keep: optional bool [B, H, Sq, Sk] attention dropout mask (kernels.attn_dropout_keep_ref), the
+    kept probabilities scaled by keep_scale = 1 / (1 - p_eff)."""
+    def drop(p):
+        return p if keep is None else torch.where(keep, p * keep_scale, torch.zeros_like(p))
+
     s = torch.einsum("bhqd,bhkd->bhqk", q, k) * scale
     Sq, Sk = s.shape[-2:]
     if causal:
         s = s.masked_fill(torch.ones(Sq, Sk, dtype=torch.bool, device=s.device).triu(1), float("-inf"))
     if key_lens is None:
-        return torch.einsum("bhqk,bhkd->bhqd", torch.softmax(s, -1), v)
+        return torch.einsum("bhqk,bhkd->bhqd", drop(torch.softmax(s, -1)), v)
     # keys at or past the sample's length leave the softmax; a sample without keys gets P = 0 (its
     # scores are made finite first, so neither the softmax nor its gradient sees a NaN). All on the
     # tensor's device: the lengths are never read on the host.
@@ -54,7 +72,7 @@ def _attn_ref(q, k, v, scale, causal, key_lens=None):
     s = s.masked_fill(pad[:, None, None, :], float("-inf"))
     s = torch.where(empty, torch.zeros_like(s), s)
     p = torch.where(empty, torch.zeros_like(s), torch.softmax(s, -1))
-    return torch.einsum("bhqk,bhkd->bhqd", p, v)
+    return torch.einsum("bhqk,bhkd->bhqd", drop(p), v)
 
 
 @register(OperatorType.OP_MULTIHEAD_ATTENTION)
@@ -70,6 +88,7 @@ class MultiHeadAttention(OpImpl):
             kl = tuple(in_dims[3])
             if kl not in ((q[0],), (q[0], 1)):
                 raise ValueError(f"key_lengths must have shape [{q[0]}] or [{q[0]}, 1], got {list(kl)}")
+        K.attn_dropout_thr(attrs.get("dropout", 0.0))  # ValueError outside [0, 1)
         H = attrs["num_heads"]
         E = attrs["embed_dim"]
         kd = attrs.get("kdim") or E // H
@@ -139,6 +158,31 @@ class MultiHeadAttention(OpImpl):
     def _w(self, ws):
         return {w.short_name: t for w, t in zip(self.layer.weights, ws)}
 
+    def drops_attention(self) -> bool:
+        """Whether training forwards of this layer drop attention probabilities (p_eff > 0): the
+        executor then keeps a device-side step counter (ctx.rng_step)."""
+        return K.attn_dropout_thr(self.attrs.get("dropout", 0.0)) > 0
+
+    def _drop(self, ctx, B, Hl, device):
+        """Attention dropout of this training forward as the kernels take it: (thr, rng_step, rng_seed,
+        b0, h0, H_total) with the shard's first global batch / head index, or None."""
+        thr = K.attn_dropout_thr(self.attrs.get("dropout", 0.0))
+        if not (ctx.training and thr):
+            return None
+        step = ctx.rng_step
+        if step is None or step.device != device:  # no executor (cost model, op-level tests): step 0
+            step = ctx.extra.get("rng_step0")
+            if step is None or step.device != device:
+                step = ctx.extra["rng_step0"] = torch.zeros(1, dtype=torch.int64, device=device)
+        seed = K.attn_dropout_seed(ctx.seed, zlib.crc32(self.layer.name.encode()))
+        return (thr, step, seed, ctx.coord(0) * B, ctx.coord(self.H_AXIS) * Hl, int(self.attrs["num_heads"]))
+
+    def _keep_ref(self, ctx, drop, B, Hl, Sq, Sk, device):
+        """The mirror's mask for the reference / CPU path (the same one the kernels draw)."""
+        thr, step, _, b0, h0, H_total = drop
+        return K.attn_dropout_keep_ref(ctx.seed, zlib.crc32(self.layer.name.encode()), step, B, Hl, Sq, Sk,
+                                       thr / 256.0, b0=b0, h0=h0, H_total=H_total, device=device)
+
     def forward(self, ctx, xs, ws):
         q_in, k_in, v_in = xs[:3]
         W = self._w(ws)
@@ -155,6 +199,7 @@ class MultiHeadAttention(OpImpl):
             bo = None
         fused = self.attrs["fused_qkv"] and (q_in is k_in is v_in or (q_in.data_ptr() == k_in.data_ptr() == v_in.data_ptr()))
         s = ctx.saved if ctx.training else {}
+        drop = self._drop(ctx, B, Hl, q_in.device)
         if fused:
             x2 = q_in.reshape(B * Sq, -1)
             wq = W["qkv_weight"].reshape(3 * Hl * kd, -1)
@@ -183,7 +228,8 @@ class MultiHeadAttention(OpImpl):
         o = torch.empty(B, Sq, Hl, vd, device=q_in.device, dtype=q_in.dtype)
         os_ = [Sq * Hl * vd, vd, Hl * vd]
         if K.attn_supported(q_in, kd) and kd == vd:
-            lse = K.flash_attn_fwd(qv, qs, kv, ks, vv, vs, o, os_, B, Hl, Sq, Sk, kd, scale, causal, key_lens=kl)
+            lse = K.flash_attn_fwd(qv, qs, kv, ks, vv, vs, o, os_, B, Hl, Sq, Sk, kd, scale, causal, key_lens=kl,
+                                   drop=drop)
             s["lse"] = lse
         elif K.attn_padded_dim(q_in, kd, vd):
             # head dims the MFMA kernels have no instance for (e.g. 16, 32, 80, 96): zero-pad Q, K,
@@ -196,13 +242,14 @@ class MultiHeadAttention(OpImpl):
             po = torch.empty(B, Sq, Hl, Dp, device=q_in.device, dtype=q_in.dtype)
             pst = [Sq * Hl * Dp, Dp, Hl * Dp]
             kst = [Sk * Hl * Dp, Dp, Hl * Dp]
-            lse = K.flash_attn_fwd(pq, pst, pk, kst, pv, kst, po, pst, B, Hl, Sq, Sk, Dp, scale, causal, key_lens=kl)
+            lse = K.flash_attn_fwd(pq, pst, pk, kst, pv, kst, po, pst, B, Hl, Sq, Sk, Dp, scale, causal, key_lens=kl,
+                                   drop=drop)
             o.copy_(po[..., :vd])
             s.update(lse=lse, pad=(Dp, pq, pk, pv, po))
         elif K.attn_f32_supported(q_in) and os.environ.get("FF_ATTN_REF_FALLBACK") != "1":
             # --dtype fp32 on the device: f32 MFMA GEMMs + causal mask + row softmax, our kernels
             s["P"] = K.attn_f32_fwd(qv, qs, kv, ks, vv, vs, o.view(-1), os_, B, Hl, Sq, Sk, kd, vd, scale, causal,
-                                    key_lens=kl)
+                                    key_lens=kl, drop=drop)
         else:
             if K.native(q_in) and q_in.dtype == torch.bfloat16 and os.environ.get("FF_ATTN_REF_FALLBACK") != "1":
                 raise NotImplementedError(
@@ -211,7 +258,11 @@ class MultiHeadAttention(OpImpl):
             q4 = qv.as_strided((B, Hl, Sq, kd), (qs[0], qs[1], qs[2], 1)).float()
             k4 = kv.as_strided((B, Hl, Sk, kd), (ks[0], ks[1], ks[2], 1)).float()
             v4 = vv.as_strided((B, Hl, Sk, vd), (vs[0], vs[1], vs[2], 1)).float()
-            o.copy_(_attn_ref(q4, k4, v4, scale, causal, kl).permute(0, 2, 1, 3))
+            keep = self._keep_ref(ctx, drop, B, Hl, Sq, Sk, q_in.device) if drop else None
+            if keep is not None:
+                s["keep"] = keep
+            o.copy_(_attn_ref(q4, k4, v4, scale, causal, kl, keep, 256.0 / (256 - drop[0]) if drop else 1.0)
+                    .permute(0, 2, 1, 3))
         o2 = o.view(B * Sq, Hl * vd)
         wo = W["o_weight"].reshape(E, Hl * vd)
         if ctx.training:
@@ -219,7 +270,7 @@ class MultiHeadAttention(OpImpl):
         y, _ = K.linear_fwd(o2, wo, bo, K.ACT_NONE, False)
         if ctx.training:
             s.update(o=o, wo=wo, has_bo=bo is not None, shape=(B, Sq, Sk, Hl, kd, vd, E), fused=fused,
-                     qs=qs, ks=ks, vs=vs, os=os_, scale=scale, causal=causal, key_lens=kl)
+                     qs=qs, ks=ks, vs=vs, os=os_, scale=scale, causal=causal, key_lens=kl, drop=drop)
         return [y.view(B, Sq, E)]
 
     def overwrites_wgrad(self, i):
@@ -246,6 +297,7 @@ class MultiHeadAttention(OpImpl):
         qs, ks, vs, os_ = s["qs"], s["ks"], s["vs"], s["os"]
         fused = s["fused"]
         kl = s["key_lens"]
+        drop = s["drop"]  # the counter is read on the device again: the next forward advances it, not this backward
         no_kl_grad = [None] * (len(self.layer.inputs) - 3)  # the lengths take no gradient
         bias_done = False
         if fused:
@@ -264,7 +316,7 @@ class MultiHeadAttention(OpImpl):
             pst = [Sq * Hl * Dp, Dp, Hl * Dp]
             kst = [Sk * Hl * Dp, Dp, Hl * Dp]
             K.flash_attn_bwd(pq, pst, pk, kst, pv, kst, po, pst, pdo, pst, s["lse"], pdq, pst, pdk, kst, pdv, kst,
-                             B, Hl, Sq, Sk, Dp, scale, causal, key_lens=kl)
+                             B, Hl, Sq, Sk, Dp, scale, causal, key_lens=kl, drop=drop)
             for g, st, pg, S_, d in ((dq, qs, pdq, Sq, kd), (dk, ks, pdk, Sk, kd), (dv, vs, pdv, Sk, vd)):
                 g.as_strided((B, Hl, S_, d), (st[0], st[1], st[2], 1)).copy_(pg[..., :d].permute(0, 2, 1, 3))
         elif "lse" in s:
@@ -273,19 +325,20 @@ class MultiHeadAttention(OpImpl):
             dbq = gw("qkv_bias") if (fused and os.environ.get("FF_ATTN_BIAS_FUSION", "1") == "1") else None
             if dbq is not None and dbq.dtype == torch.float32 and dbq.is_contiguous():
                 bias_done = K.flash_attn_bwd(qv, qs, kv, ks, vv, vs, o, os_, do, os_, s["lse"], dq, qs, dk, ks, dv, vs,
-                                             B, Hl, Sq, Sk, kd, scale, causal, dbias=dbq.view(-1), key_lens=kl)
+                                             B, Hl, Sq, Sk, kd, scale, causal, dbias=dbq.view(-1), key_lens=kl,
+                                             drop=drop)
             else:
                 K.flash_attn_bwd(qv, qs, kv, ks, vv, vs, o, os_, do, os_, s["lse"], dq, qs, dk, ks, dv, vs,
-                                 B, Hl, Sq, Sk, kd, scale, causal, key_lens=kl)
+                                 B, Hl, Sq, Sk, kd, scale, causal, key_lens=kl, drop=drop)
         elif "P" in s:
             K.attn_f32_bwd(qv, qs, kv, ks, vv, vs, do.contiguous().view(-1), os_, s["P"], dq.view(-1), dk.view(-1),
-                           dv.view(-1), B, Hl, Sq, Sk, kd, vd, scale, key_lens=kl)
+                           dv.view(-1), B, Hl, Sq, Sk, kd, vd, scale, key_lens=kl, drop=drop)
         else:
             q4 = qv.as_strided((B, Hl, Sq, kd), (qs[0], qs[1], qs[2], 1)).detach().float().requires_grad_()
             k4 = kv.as_strided((B, Hl, Sk, kd), (ks[0], ks[1], ks[2], 1)).detach().float().requires_grad_()
             v4 = vv.as_strided((B, Hl, Sk, vd), (vs[0], vs[1], vs[2], 1)).detach().float().requires_grad_()
             with torch.enable_grad():
-                out = _attn_ref(q4, k4, v4, scale, causal, kl)
+                out = _attn_ref(q4, k4, v4, scale, causal, kl, s.get("keep"), 256.0 / (256 - drop[0]) if drop else 1.0)
             g4 = do.permute(0, 2, 1, 3).float()
             gq, gk, gv = torch.autograd.grad(out, (q4, k4, v4), g4)
             dq.as_strided((B, Hl, Sq, kd), (qs[0], qs[1], qs[2], 1)).copy_(gq)

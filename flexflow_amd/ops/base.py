@@ -63,6 +63,10 @@ class OpCtx:
     wgrads: List[Optional[torch.Tensor]] = field(default_factory=list)   # fp32 accumulators (+=)
     step: int = 0
     seed: int = 0
+    # one-element int64 device tensor: the executor's training-step counter as the device sees it
+    # (advanced by a kernel at the start of every training forward, so a captured step reads a new
+    # value at every replay); None where an op runs without an executor, which means step 0
+    rng_step: Optional[torch.Tensor] = None
     extra: Dict[str, Any] = field(default_factory=dict)
 
     def coord(self, axis: int) -> int:

@@ -67,6 +67,8 @@ def save_checkpoint(model, path: str):
     if cfg.rank == 0:
         meta = {
             "step": int(ex.step_idx),
+            # the device-side step counter of attention dropout (Executor.rng_step), when the model has one
+            "rng_step": int(ex.rng_step.item()) if getattr(ex, "rng_step", None) is not None else None,
             "world_size": int(cfg.world_size),
             # informational: the state above is gathered, so resuming under another sharding is fine
             "zero": bool(getattr(ex, "zero", False)),
@@ -154,4 +156,7 @@ def load_checkpoint(model, path: str, strict: bool = True):
             setattr(opt, k, v)
     ex._master_stale = False  # every rank now holds the full master
     ex.step_idx = int(meta["step"])
+    if getattr(ex, "rng_step", None) is not None:  # the resumed run draws the masks the unbroken run draws
+        rs = meta.get("rng_step")
+        ex.rng_step.fill_(int(meta["step"] if rs is None else rs))
     return meta["step"]

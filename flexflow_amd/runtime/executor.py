@@ -105,6 +105,16 @@ class Executor:
             if mine:
                 self.ctx[L.name] = OpCtx(layer=L, part_coords=scfg.coords(mine[0]), degrees=scfg.degrees,
                                          compute_dtype=self.cdt, training=training, seed=cfg.seed)
+        # training-step counter on the device for attention dropout (ops/attention.py): one int64,
+        # advanced by a kernel at the start of every training forward and read by the attention
+        # kernels, so eager steps, graph replays and trace bodies all draw a new mask per step with no
+        # host write. Only a model with an attention layer that drops gets one (and the extra
+        # launch): every other model's launch sequence is what it was.
+        self.rng_step = None
+        if any(getattr(L.impl, "drops_attention", lambda: False)() for L in self.layers):
+            self.rng_step = torch.zeros(1, dtype=torch.int64, device=self.device)
+            for c in self.ctx.values():
+                c.rng_step = self.rng_step
         self.producer_layout: Dict[int, Layout] = {}
         for L in self.layers:
             for o, lo in zip(L.outputs, self.lay[L.name].outputs):
@@ -459,6 +469,8 @@ class Executor:
             stores = [st for c in self.ctx.values() for k, st in c.extra.items() if k.startswith("wt_store")]
             K.wt_refresh_all(stores, self.__dict__.setdefault("_wt_batch", {}))
         K.wt_forward(batched)
+        if tr and self.rng_step is not None:
+            self.rng_step.add_(1)  # forward and backward of this step read the same value
         try:
             return self._forward(tr)
         finally:

@@ -106,7 +106,7 @@ def _enc_module(m, node) -> (OpType, List[str]):
     if isinstance(m, nn.MultiheadAttention):
         if not m.batch_first:
             raise NotImplementedError("MultiheadAttention(batch_first=False)")
-        return OpType.MULTIHEAD_ATTENTION, [m.embed_dim, m.num_heads, int(m.in_proj_bias is not None)]
+        return OpType.MULTIHEAD_ATTENTION, [m.embed_dim, m.num_heads, int(m.in_proj_bias is not None), float(m.dropout)]
     simple = {nn.ReLU: OpType.RELU, nn.GELU: OpType.GELU, nn.Sigmoid: OpType.SIGMOID, nn.Tanh: OpType.TANH,
               nn.ELU: OpType.ELU, nn.Identity: OpType.IDENTITY}
     for cls, op in simple.items():
@@ -253,7 +253,8 @@ def _build(ff, node: IRNode, ins: list, name: str):
         E, H, bias = int(a[0]), int(a[1]), bool(int(a[2]))
         q, k, v = (ins + [ins[0]] * 3)[:3]
         # torch returns (attn_output, attn_weights); the weights are not materialised
-        return (ff.multihead_attention(q, k, v, E, H, E // H, E // H, 0.0, bias, name=name), None)
+        drop = float(a[3]) if len(a) > 3 else 0.0  # .ff files written before the field: no dropout
+        return (ff.multihead_attention(q, k, v, E, H, E // H, E // H, drop, bias, name=name), None)
     unary = {OpType.RELU: ff.relu, OpType.GELU: ff.gelu, OpType.SIGMOID: ff.sigmoid, OpType.TANH: ff.tanh,
              OpType.ELU: ff.elu, OpType.EXP: ff.exp, OpType.RSQRT: ff.rsqrt, OpType.SIN: ff.sin, OpType.COS: ff.cos}
     if op in unary:
