@@ -349,23 +349,48 @@ void softmax_bwd(Tensor y, Tensor dy, Tensor dx, int64_t rows, int64_t cols, dou
   check_contig(y, "softmax_bwd: y"); check_contig(dy, "softmax_bwd: dy"); check_contig(dx, "softmax_bwd: dx");
   ffk::softmax_bwd(dtcode(y), y.data_ptr(), dy.data_ptr(), dx.data_ptr(), rows, cols, scale, acc, cur_stream());
 }
+// ignore_index / valid_count of the loss bindings: a device-side fp32 [1] count needs an ignore_index
+static const float* valid_count_ptr(const optional<int64_t>& ignore_index, const optional<Tensor>& valid_count,
+                                    const Tensor& like, const char* what) {
+  if (!valid_count) return nullptr;
+  TORCH_CHECK(ignore_index.has_value(), what, ": valid_count needs ignore_index");
+  TORCH_CHECK(valid_count->scalar_type() == at::kFloat && valid_count->numel() >= 1 &&
+              valid_count->device() == like.device(), what, ": valid_count must be fp32 [1] on the inputs' device");
+  check_contig(*valid_count, what);
+  return valid_count->data_ptr<float>();
+}
 void softmax_xent(Tensor logits, Tensor labels, optional<Tensor> loss, optional<Tensor> dlogits, int64_t rows,
-                  int64_t cols, double gscale, optional<Tensor> acc3) {
+                  int64_t cols, double gscale, optional<Tensor> acc3, optional<int64_t> ignore_index,
+                  optional<Tensor> valid_count) {
   TORCH_CHECK(labels.scalar_type() == at::kInt && labels.numel() >= rows);
   TORCH_CHECK(!acc3 || (acc3->scalar_type() == at::kFloat && acc3->numel() >= 3));
   check_contig(logits, "softmax_xent: logits"); check_contig(labels, "softmax_xent: labels");
   check_contig(loss, "softmax_xent: loss"); check_contig(dlogits, "softmax_xent: dlogits");
+  const float* vc = valid_count_ptr(ignore_index, valid_count, logits, "softmax_xent");
   ffk::softmax_xent_fwd_bwd(dtcode(logits), logits.data_ptr(), labels.data_ptr<int>(), ptr<float>(loss),
-                            ptr(dlogits), rows, cols, gscale, ptr<float>(acc3), cur_stream());
+                            ptr(dlogits), rows, cols, gscale, ptr<float>(acc3), cur_stream(),
+                            ignore_index.has_value(), (int)ignore_index.value_or(0), vc);
 }
 void xent_grad(Tensor probs, optional<Tensor> labels, optional<Tensor> onehot, Tensor dprobs, optional<Tensor> loss,
-               int64_t rows, int64_t cols, double gscale, bool sparse) {
+               int64_t rows, int64_t cols, double gscale, bool sparse, optional<int64_t> ignore_index,
+               optional<Tensor> valid_count) {
   TORCH_CHECK(probs.numel() == rows * cols && dprobs.numel() == rows * cols);
+  TORCH_CHECK(!ignore_index || sparse, "xent_grad: ignore_index needs sparse labels");
   check_contig(probs, "xent_grad: probs"); check_contig(dprobs, "xent_grad: dprobs");
   check_contig(labels, "xent_grad: labels"); check_contig(onehot, "xent_grad: onehot");
   check_contig(loss, "xent_grad: loss");
+  const float* vc = valid_count_ptr(ignore_index, valid_count, probs, "xent_grad");
   ffk::xent_grad(dtcode(probs), probs.data_ptr(), ptr<int>(labels), ptr(onehot), dprobs.data_ptr(),
-                 ptr<float>(loss), rows, cols, gscale, sparse, cur_stream());
+                 ptr<float>(loss), rows, cols, gscale, sparse, cur_stream(), ignore_index.has_value(),
+                 (int)ignore_index.value_or(0), vc);
+}
+Tensor count_valid_labels(Tensor labels, int64_t ignore_index) {
+  TORCH_CHECK(labels.scalar_type() == at::kInt, "count_valid_labels: int32 labels");
+  check_contig(labels, "count_valid_labels: labels");
+  Tensor out = at::empty({1}, labels.options().dtype(at::kFloat));
+  ffk::count_valid_labels(labels.data_ptr<int>(), labels.numel(), (int)ignore_index, out.data_ptr<float>(),
+                          cur_stream());
+  return out;
 }
 void mse_grad(Tensor pred, Tensor label, Tensor dpred, optional<Tensor> loss, double gscale) {
   TORCH_CHECK(pred.numel() == label.numel() && dpred.numel() == pred.numel());
@@ -373,12 +398,13 @@ void mse_grad(Tensor pred, Tensor label, Tensor dpred, optional<Tensor> loss, do
   ffk::mse_grad(dtcode(pred), pred.data_ptr(), label.data_ptr(), dpred.data_ptr(), ptr<float>(loss), pred.numel(),
                 gscale, cur_stream());
 }
-void metrics_classify(Tensor probs, Tensor labels, int64_t rows, int64_t cols, Tensor out) {
+void metrics_classify(Tensor probs, Tensor labels, int64_t rows, int64_t cols, Tensor out,
+                      optional<int64_t> ignore_index) {
   TORCH_CHECK(probs.numel() == rows * cols && labels.numel() >= rows && out.numel() >= 3);
   check_contig(probs, "metrics_classify: probs"); check_contig(labels, "metrics_classify: labels");
   check_contig(out, "metrics_classify: out");
   ffk::metrics_classify(dtcode(probs), probs.data_ptr(), labels.data_ptr<int>(), rows, cols, out.data_ptr<float>(),
-                        cur_stream());
+                        cur_stream(), ignore_index.has_value(), (int)ignore_index.value_or(0));
 }
 void reduce_rows(Tensor x, Tensor y, int64_t outer, int64_t red, int64_t inner, bool mean) {
   TORCH_CHECK(x.numel() == outer * red * inner && y.numel() == outer * inner);
@@ -1010,10 +1036,15 @@ PYBIND11_MODULE(_C, m) {
   m.def("softmax_fwd", &softmax_fwd);
   m.def("softmax_bwd", &softmax_bwd);
   m.def("softmax_xent", &softmax_xent, py::arg("logits"), py::arg("labels"), py::arg("loss"), py::arg("dlogits"),
-        py::arg("rows"), py::arg("cols"), py::arg("gscale"), py::arg("acc3") = py::none());
-  m.def("xent_grad", &xent_grad);
+        py::arg("rows"), py::arg("cols"), py::arg("gscale"), py::arg("acc3") = py::none(),
+        py::arg("ignore_index") = py::none(), py::arg("valid_count") = py::none());
+  m.def("xent_grad", &xent_grad, py::arg("probs"), py::arg("labels"), py::arg("onehot"), py::arg("dprobs"),
+        py::arg("loss"), py::arg("rows"), py::arg("cols"), py::arg("gscale"), py::arg("sparse"),
+        py::arg("ignore_index") = py::none(), py::arg("valid_count") = py::none());
+  m.def("count_valid_labels", &count_valid_labels);
   m.def("mse_grad", &mse_grad);
-  m.def("metrics_classify", &metrics_classify);
+  m.def("metrics_classify", &metrics_classify, py::arg("probs"), py::arg("labels"), py::arg("rows"), py::arg("cols"),
+        py::arg("out"), py::arg("ignore_index") = py::none());
   m.def("reduce_rows", &reduce_rows);
   m.def("sgd_update", &sgd_update, py::arg("master"), py::arg("grad"), py::arg("mom"), py::arg("lowp"), py::arg("lr"),
         py::arg("momentum"), py::arg("nesterov"), py::arg("wd"), py::arg("gscale"), py::arg("max_blocks") = 0);

@@ -105,11 +105,19 @@ void softmax_fwd(int dt, const void* x, void* y, int rows, int cols, float scale
 void softmax_bwd(int dt, const void* y, const void* dy, void* dx, int rows, int cols, float scale, int accumulate,
                  hipStream_t st);
 // Fused softmax + sparse categorical cross-entropy: writes per-row loss (fp32) and dlogits = (p - onehot)*gscale.
+// ignore: rows whose label equals ignore_index are left out (loss 0, zero gradient row, logits not
+// read, not counted in acc3); valid_count (device, fp32 [1], or null): the gradient scale is
+// 1 / max(*valid_count, 1) instead of gscale. Same for xent_grad (sparse labels) and, without the
+// scale, metrics_classify.
 void softmax_xent_fwd_bwd(int dt, const void* logits, const int* labels, float* loss, void* dlogits, int rows,
-                          int cols, float gscale, float* acc3 /*[3] or null*/, hipStream_t st);
+                          int cols, float gscale, float* acc3 /*[3] or null*/, hipStream_t st, bool ignore = false,
+                          int ignore_index = 0, const float* valid_count = nullptr);
+// out[0] = number of labels != ignore_index (overwritten): the valid_count above
+void count_valid_labels(const int* labels, int64_t n, int ignore_index, float* out, hipStream_t st);
 // Loss on already-normalised probabilities (reference semantics: loss follows a Softmax op)
 void xent_grad(int dt, const void* probs, const int* labels, const void* onehot, void* dprobs, float* loss, int rows,
-               int cols, float gscale, int sparse, hipStream_t st);
+               int cols, float gscale, int sparse, hipStream_t st, bool ignore = false, int ignore_index = 0,
+               const float* valid_count = nullptr);
 void mse_grad(int dt, const void* pred, const void* label, void* dpred, float* loss, int64_t n, float gscale,
               hipStream_t st);
 
@@ -146,7 +154,7 @@ void flash_attn_bwd(const void* q, const void* k, const void* v, const void* o, 
 void reduce_rows(int dt, const void* x, void* y, int64_t outer, int64_t red, int64_t inner, int mean,
                  hipStream_t st);
 void metrics_classify(int dt, const void* probs, const int* labels, int rows, int cols, float* out /*[3]*/,
-                      hipStream_t st);
+                      hipStream_t st, bool ignore = false, int ignore_index = 0);
 
 // rnn.hip: pointwise LSTM step (gate order i, f, g, o; G rows of stride ldg; c in fp32)
 void lstm_fwd_cell(int dt, void* G, int64_t ldg, const float* c_prev, float* c_out, void* h_out, int64_t ldh, int B,

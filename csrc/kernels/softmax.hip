@@ -101,17 +101,44 @@ __device__ __forceinline__ void row_visit(const T* __restrict__ xr, int cols, in
 // never written): pass 1 = online max / sum-exp / argmax with 16-B loads, pass 2 = the gradient
 // (p - onehot) * gscale.  Optional acc3 += {correct, sum CE, rows} folds the accuracy / CE metrics
 // (reference metrics_functions.cu) into the same read of the logits.
-template <typename T>
+// IGNORE (opt-in ignore_index; false is the kernel every call without one launches, and ignore_index /
+// valid_count are dead arguments there): a row whose label equals ignore_index is left out. Its
+// logits are never read (neither pass runs, they may hold NaN), its loss is 0, its gradient row is
+// zero-filled and it adds nothing to acc3, so acc3[2] counts the valid rows. labels[row] is the same
+// for the whole wave: the branch is uniform. With valid_count set (the device-side number of
+// non-ignored labels of the global batch, count_valid_kernel) the gradient scale is
+// 1 / max(*valid_count, 1) instead of gscale: torch's reduction="mean" with no host read.
+template <typename T, bool IGNORE>
 __global__ void __launch_bounds__(256) softmax_xent_kernel(const T* __restrict__ logits, const int* __restrict__ labels,
                                     float* __restrict__ loss, T* __restrict__ dlogits, int rows, int cols,
-                                    float gscale, float* __restrict__ acc3) {
+                                    float gscale, float* __restrict__ acc3, int ignore_index,
+                                    const float* __restrict__ valid_count) {
   constexpr int V = 16 / sizeof(T);
   const int lane = threadIdx.x & 63;
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int nwaves = (gridDim.x * blockDim.x) >> 6;
   float correct = 0.f, ce = 0.f, cnt = 0.f;
+  if (IGNORE && valid_count) gscale = 1.f / fmaxf(*valid_count, 1.f);
   for (int row = wave; row < rows; row += nwaves) {
     const T* xr = logits + (int64_t)row * cols;
+    if (IGNORE && labels[row] == ignore_index) {
+      if (lane == 0 && loss) loss[row] = 0.f;
+      if (dlogits) {  // the gradient pass's store pattern (head / 16-B body / tail, or scalar), storing +0
+        T* dr = dlogits + (int64_t)row * cols;
+        const T z = Cvt<T>::from_f(0.f);
+        if ((((uintptr_t)dr ^ (uintptr_t)xr) & 15) == 0) {
+          const int head = min(cols, (int)(((16 - ((uintptr_t)dr & 15)) & 15) / sizeof(T)));
+          if (lane < head) dr[lane] = z;
+          const int nvec = (cols - head) / V;
+          uint4* body = reinterpret_cast<uint4*>(dr + head);
+          for (int i = lane; i < nvec; i += 64) body[i] = make_uint4(0u, 0u, 0u, 0u);
+          for (int c = head + nvec * V + lane; c < cols; c += 64) dr[c] = z;
+        } else {
+          for (int c = lane; c < cols; c += 64) dr[c] = z;
+        }
+      }
+      continue;
+    }
     float m = -INFINITY, s = 0.f;
     int bi = 0x7fffffff;
     row_visit(xr, cols, lane, [&](int c, float v) {
@@ -282,17 +309,26 @@ __global__ void __launch_bounds__(256) softmax_xent_reg_kernel(const bf16_t* __r
 // Reference semantics (src/loss_functions/loss_functions.cu): the model ends in a Softmax op,
 // the loss gradient w.r.t. the softmax INPUT is (p - y) * scale and Softmax::backward passes it
 // through. dprobs here is that gradient.
-template <typename T>
+// IGNORE (sparse labels only), as in softmax_xent_kernel: a row labelled ignore_index gets a zero
+// gradient row and loss 0 and its probabilities are not read; valid_count replaces gscale.
+template <typename T, bool IGNORE>
 __global__ void xent_grad_kernel(const T* __restrict__ probs, const int* __restrict__ labels,
                                  const T* __restrict__ onehot, T* __restrict__ dprobs, float* __restrict__ loss,
-                                 int rows, int cols, float gscale, int sparse) {
+                                 int rows, int cols, float gscale, int sparse, int ignore_index,
+                                 const float* __restrict__ valid_count) {
   const int lane = threadIdx.x & 63;
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int nwaves = (gridDim.x * blockDim.x) >> 6;
+  if (IGNORE && valid_count) gscale = 1.f / fmaxf(*valid_count, 1.f);
   for (int row = wave; row < rows; row += nwaves) {
     const int64_t base = (int64_t)row * cols;
     float l = 0.f;
     const int lab = sparse ? labels[row] : -1;
+    if (IGNORE && lab == ignore_index) {
+      for (int c = lane; c < cols; c += 64) dprobs[base + c] = Cvt<T>::from_f(0.f);
+      if (lane == 0 && loss) loss[row] = 0.f;
+      continue;
+    }
     for (int c = lane; c < cols; c += 64) {
       const float p = Cvt<T>::to_f(probs[base + c]);
       const float t = sparse ? (c == lab ? 1.f : 0.f) : Cvt<T>::to_f(onehot[base + c]);
@@ -320,14 +356,16 @@ __global__ void mse_grad_kernel(const T* __restrict__ pred, const T* __restrict_
 }
 
 // metrics: out[0] += #correct (argmax == label), out[1] += sum CE, out[2] += rows
-template <typename T>
+// IGNORE: rows labelled ignore_index are skipped unread, so out[2] counts the valid rows
+template <typename T, bool IGNORE>
 __global__ void metrics_kernel(const T* __restrict__ probs, const int* __restrict__ labels, int rows, int cols,
-                               float* __restrict__ out) {
+                               float* __restrict__ out, int ignore_index) {
   const int lane = threadIdx.x & 63;
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int nwaves = (gridDim.x * blockDim.x) >> 6;
   float correct = 0.f, ce = 0.f, cnt = 0.f;
   for (int row = wave; row < rows; row += nwaves) {
+    if (IGNORE && labels[row] == ignore_index) continue;
     const int64_t base = (int64_t)row * cols;
     float best = -INFINITY;
     int bi = 0x7fffffff;
@@ -352,6 +390,27 @@ __global__ void metrics_kernel(const T* __restrict__ probs, const int* __restric
     atomicAdd(out + 0, correct);
     atomicAdd(out + 1, ce);
     atomicAdd(out + 2, cnt);
+  }
+}
+
+// out[0] = #{labels != ignore_index} (overwritten, fp32: exact below 2^24 labels). One 1024-thread
+// workgroup: the labels of a step number at most a few hundred thousand, and a single workgroup
+// needs neither a zeroing launch nor atomics.
+__global__ void __launch_bounds__(1024) count_valid_kernel(const int* __restrict__ labels, int64_t n, int ignore_index,
+                                                           float* __restrict__ out) {
+  __shared__ int red[16];
+  int c = 0;
+#pragma unroll 4
+  for (int64_t i = threadIdx.x; i < n; i += 1024) c += labels[i] != ignore_index ? 1 : 0;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int t = 0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) t += red[i];
+    out[0] = (float)t;
   }
 }
 
@@ -395,14 +454,17 @@ void softmax_bwd(int dt, const void* y, const void* dy, void* dx, int rows, int 
                                      (const T*)dy, (T*)dx, rows, cols, scale, accumulate));
 }
 void softmax_xent_fwd_bwd(int dt, const void* logits, const int* labels, float* loss, void* dlogits, int rows,
-                          int cols, float gscale, float* acc3, hipStream_t st) {
+                          int cols, float gscale, float* acc3, hipStream_t st, bool ignore, int ignore_index,
+                          const float* valid_count) {
   if (rows == 0) return;
   // opt-in (FF_XENT_REG=1): despite moving 1 GB less per call, the register-resident kernel measured
   // 0.6 ms/step SLOWER in a same-box A/B of the BERT-Large step (53.2 vs 52.6 ms, profiles/
   // softmax_xent_ab_r1.txt): one row per 256-thread workgroup with 4-B loads leaves too little
   // memory-level parallelism, which the two-pass kernel's 16-B x 4-deep loads have
+  // The register-resident kernel has no ignore form: a call with ignore_index always takes the
+  // two-pass kernel, whose per-row skip is what the ignore path is for.
   static const int reg_ok = getenv("FF_XENT_REG") ? atoi(getenv("FF_XENT_REG")) : 0;
-  if (reg_ok && dt == DT_BF16 && cols % 2 == 0 && cols >= 4096 && cols <= 2 * 256 * 64) {
+  if (!ignore && reg_ok && dt == DT_BF16 && cols % 2 == 0 && cols >= 4096 && cols <= 2 * 256 * 64) {
     const int g = std::min(rows, 2048);
     if (cols <= 2 * 256 * 32)
       hipLaunchKernelGGL(softmax_xent_reg_kernel<32>, dim3(g), dim3(256), 0, st, (const bf16_t*)logits, labels, loss,
@@ -419,15 +481,25 @@ void softmax_xent_fwd_bwd(int dt, const void* logits, const int* labels, float* 
   // profiles/softmax_xent_grid_r2.txt). FF_XENT_GRID overrides the cap.
   static const int grid_cap = getenv("FF_XENT_GRID") ? atoi(getenv("FF_XENT_GRID")) : 768;
   const int g = grid_cap > 0 ? std::min(row_blocks(rows), grid_cap) : row_blocks(rows);
-  DT_DISPATCH(dt, hipLaunchKernelGGL(softmax_xent_kernel<T>, dim3(g), dim3(256), 0, st,
-                                     (const T*)logits, labels, loss, (T*)dlogits, rows, cols, gscale, acc3));
+  if (ignore)
+    DT_DISPATCH(dt, hipLaunchKernelGGL((softmax_xent_kernel<T, true>), dim3(g), dim3(256), 0, st, (const T*)logits,
+                                       labels, loss, (T*)dlogits, rows, cols, gscale, acc3, ignore_index, valid_count));
+  else
+    DT_DISPATCH(dt, hipLaunchKernelGGL((softmax_xent_kernel<T, false>), dim3(g), dim3(256), 0, st, (const T*)logits,
+                                       labels, loss, (T*)dlogits, rows, cols, gscale, acc3, 0, (const float*)nullptr));
 }
 void xent_grad(int dt, const void* probs, const int* labels, const void* onehot, void* dprobs, float* loss, int rows,
-               int cols, float gscale, int sparse, hipStream_t st) {
+               int cols, float gscale, int sparse, hipStream_t st, bool ignore, int ignore_index,
+               const float* valid_count) {
   if (rows == 0) return;
-  DT_DISPATCH(dt, hipLaunchKernelGGL(xent_grad_kernel<T>, dim3(row_blocks(rows)), dim3(256), 0, st,
-                                     (const T*)probs, labels, (const T*)onehot, (T*)dprobs, loss, rows, cols, gscale,
-                                     sparse));
+  if (ignore && sparse)
+    DT_DISPATCH(dt, hipLaunchKernelGGL((xent_grad_kernel<T, true>), dim3(row_blocks(rows)), dim3(256), 0, st,
+                                       (const T*)probs, labels, (const T*)onehot, (T*)dprobs, loss, rows, cols, gscale,
+                                       sparse, ignore_index, valid_count));
+  else
+    DT_DISPATCH(dt, hipLaunchKernelGGL((xent_grad_kernel<T, false>), dim3(row_blocks(rows)), dim3(256), 0, st,
+                                       (const T*)probs, labels, (const T*)onehot, (T*)dprobs, loss, rows, cols, gscale,
+                                       sparse, 0, (const float*)nullptr));
 }
 void mse_grad(int dt, const void* pred, const void* label, void* dpred, float* loss, int64_t n, float gscale,
               hipStream_t st) {
@@ -436,10 +508,18 @@ void mse_grad(int dt, const void* pred, const void* label, void* dpred, float* l
                                      (const T*)label, (T*)dpred, loss, n, gscale));
 }
 void metrics_classify(int dt, const void* probs, const int* labels, int rows, int cols, float* out,
-                      hipStream_t st) {
+                      hipStream_t st, bool ignore, int ignore_index) {
   if (rows == 0) return;
-  DT_DISPATCH(dt, hipLaunchKernelGGL(metrics_kernel<T>, dim3(std::min(row_blocks(rows), 1024)), dim3(256), 0, st,
-                                     (const T*)probs, labels, rows, cols, out));
+  const int g = std::min(row_blocks(rows), 1024);
+  if (ignore)
+    DT_DISPATCH(dt, hipLaunchKernelGGL((metrics_kernel<T, true>), dim3(g), dim3(256), 0, st, (const T*)probs, labels,
+                                       rows, cols, out, ignore_index));
+  else
+    DT_DISPATCH(dt, hipLaunchKernelGGL((metrics_kernel<T, false>), dim3(g), dim3(256), 0, st, (const T*)probs, labels,
+                                       rows, cols, out, 0));
+}
+void count_valid_labels(const int* labels, int64_t n, int ignore_index, float* out, hipStream_t st) {
+  hipLaunchKernelGGL(count_valid_kernel, dim3(1), dim3(1024), 0, st, labels, n, ignore_index, out);
 }
 void reduce_rows(int dt, const void* x, void* y, int64_t outer, int64_t red, int64_t inner, int mean,
                  hipStream_t st) {

@@ -1,9 +1,13 @@
 """bert-tiny on right-padded variable-length batches: every sample carries its number of real
 tokens, the data loader feeds those lengths next to the token ids, and every attention layer
 leaves the pad positions out as keys (`key_lengths`, read on the device: the step still captures
-into a graph). Synthetic data; the labels of pad positions are not masked out of the loss.
+into a graph). Synthetic data. By default the labels of pad positions still count in the loss;
+`--ignore-pad-labels` writes -100 there and compiles with `ignore_index=-100,
+loss_reduction="valid"`, so the pad rows leave loss, gradients and accuracy and the loss is the
+mean over the real tokens.
 
     python examples/python/native/bert_varlen.py -b 8 --seq-length 64 --iterations 20
+    python examples/python/native/bert_varlen.py -b 8 --seq-length 64 --iterations 20 --ignore-pad-labels
 """
 import argparse
 import sys
@@ -20,6 +24,7 @@ def top_level_task(argv=None):
     ap.add_argument("--seq-length", type=int, default=64)
     ap.add_argument("--iterations", type=int, default=20)
     ap.add_argument("--min-length", type=int, default=8)
+    ap.add_argument("--ignore-pad-labels", action="store_true")
     args, rest = ap.parse_known_args(sys.argv[1:] if argv is None else argv)
     ffconfig = FFConfig(rest)
     ffmodel = FFModel(ffconfig)
@@ -28,14 +33,19 @@ def top_level_task(argv=None):
     lengths = ffmodel.create_tensor([b], DataType.DT_INT32, name="key_lengths")
     ids, pos, _ = build_bert(ffmodel, b, bc, key_lengths=lengths)
     ffmodel.optimizer = AdamOptimizer(ffmodel, 1e-3)
-    ffmodel.compile(loss_type=LossType.LOSS_SPARSE_CATEGORICAL_CROSSENTROPY, metrics=[MetricsType.METRICS_ACCURACY])
+    masking = dict(ignore_index=-100, loss_reduction="valid") if args.ignore_pad_labels else {}
+    ffmodel.compile(loss_type=LossType.LOSS_SPARSE_CATEGORICAL_CROSSENTROPY, metrics=[MetricsType.METRICS_ACCURACY],
+                    **masking)
     # a synthetic corpus: n sentences of min-length .. s tokens, right-padded with token 0
     rng = np.random.default_rng(0)
     n = b * args.iterations
     lens = rng.integers(min(args.min_length, s), s + 1, n).astype(np.int32)
     tok = rng.integers(1, bc.vocab, (n, s)).astype(np.int32)
-    tok[np.arange(s)[None, :] >= lens[:, None]] = 0
+    pad = np.arange(s)[None, :] >= lens[:, None]
+    tok[pad] = 0
     labels = ((tok + 1) % bc.vocab)[..., None].astype(np.int32)  # learnable: the next id of each token
+    if args.ignore_pad_labels:
+        labels[pad] = -100
     loaders = [ffmodel.create_data_loader(ids, tok),
                ffmodel.create_data_loader(pos, np.tile(np.arange(s, dtype=np.int32), (n, 1))),
                ffmodel.create_data_loader(lengths, lens),
@@ -50,6 +60,9 @@ def top_level_task(argv=None):
     run_time = 1e-6 * (ffconfig.get_current_time() - ts)
     print("bert-tiny varlen: %d iterations, mean length %.1f of %d, %.4fs, THROUGHPUT = %.2f samples/s, loss %.4f" %
           (args.iterations, lens.mean(), s, run_time, b * args.iterations / run_time, pm.get_loss()))
+    if args.ignore_pad_labels:
+        print("pad labels ignored: loss is the mean over %d real tokens, accuracy %.2f%%" %
+              (pm.train_all, pm.get_accuracy()))
     return pm
 
 

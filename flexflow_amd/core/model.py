@@ -81,6 +81,8 @@ class FFModel:
         self.layers: List[Layer] = []
         self.optimizer = None
         self.loss_type = None
+        self.ignore_index = None
+        self.loss_reduction = "batch"
         self.metrics = []
         self.comp_mode = CompMode.TRAINING
         self.label_tensor: Optional[Tensor] = None
@@ -428,13 +430,28 @@ class FFModel:
         self._output = t
 
     # ================================================================== compile
-    def compile(self, optimizer=None, loss_type=None, metrics=None, comp_mode=None):
+    def compile(self, optimizer=None, loss_type=None, metrics=None, comp_mode=None, ignore_index=None,
+                loss_reduction="batch"):
+        """ignore_index (sparse categorical cross-entropy only; e.g. -100 as torch, or a pad class id as
+        Keras' ignore_class): rows with that label contribute nothing to the loss, the gradients or
+        the metrics, and their logits are never read. loss_reduction: "batch" scales the loss gradient
+        by 1 / batch as without ignore_index; "valid" by 1 / max(N_valid, 1) with N_valid the
+        non-ignored rows of the global batch (torch's reduction="mean"; a step with no valid row gives
+        zero gradients and loss 0 where torch gives NaN)."""
         cfg = self.config
+        if loss_reduction not in ("batch", "valid"):
+            raise ValueError(f"loss_reduction must be 'batch' or 'valid', got {loss_reduction!r}")
+        if ignore_index is not None and loss_type != LossType.LOSS_SPARSE_CATEGORICAL_CROSSENTROPY:
+            raise ValueError("ignore_index needs loss_type LOSS_SPARSE_CATEGORICAL_CROSSENTROPY")
+        if loss_reduction == "valid" and ignore_index is None:
+            raise ValueError("loss_reduction='valid' needs ignore_index")
         if optimizer is not None:
             self.optimizer = optimizer
         if comp_mode is not None:
             self.comp_mode = comp_mode
         self.loss_type = loss_type
+        self.ignore_index = None if ignore_index is None else int(ignore_index)
+        self.loss_reduction = loss_reduction
         self.metrics = list(metrics or [])
         _ensure_dist(cfg)
         self.subst_report = None
@@ -455,7 +472,8 @@ class FFModel:
         self.strategy, self.search_report = choose_strategy(self)
         from ..runtime.executor import Executor
         training = self.comp_mode == CompMode.TRAINING
-        self.executor = Executor(self, self.strategy, loss_type, self.metrics, training=training)
+        self.executor = Executor(self, self.strategy, loss_type, self.metrics, training=training,
+                                 ignore_index=self.ignore_index, loss_reduction=loss_reduction)
         self.executor.init_weights(cfg.seed)
         if os.environ.get("FF_NO_INPLACE") != "1":
             self.executor._plan_inplace()

@@ -14,8 +14,13 @@ class CategoricalCrossentropy(Loss):
 
 
 class SparseCategoricalCrossentropy(Loss):
+    """ignore_class (as in Keras, e.g. a pad id): labels of that class are left out of the loss, the
+    gradients and the metrics (FFModel.compile's ignore_index)."""
     type = LossType.LOSS_SPARSE_CATEGORICAL_CROSSENTROPY
     label_dtype = DataType.DT_INT32
+
+    def __init__(self, ignore_class=None):
+        self.ignore_class = None if ignore_class is None else int(ignore_class)
 
 
 class MeanSquaredError(Loss):

@@ -171,7 +171,8 @@ class Model(Layer):
         self._ff_output = outs[0]
         self._optimizer = kopt.get(optimizer)
         ff.optimizer = self._optimizer.create_ffhandle(ff)
-        ff.compile(loss_type=self._loss.type, metrics=[m.type for m in self._metrics], comp_mode=comp_mode)
+        ff.compile(loss_type=self._loss.type, metrics=[m.type for m in self._metrics], comp_mode=comp_mode,
+                   ignore_index=getattr(self._loss, "ignore_class", None))
         self._ffmodel = ff
 
     def _loaders(self, x, y):

@@ -1158,31 +1158,70 @@ def softmax_bwd(y2d, dy2d):
     return (y * (d - (d * y).sum(-1, keepdim=True))).to(dy2d.dtype)
 
 
-def xent_grad(probs2d, labels, onehot, gscale, sparse):
-    """(p - y)*gscale and per-row CE; labels int32 [rows] (sparse) or onehot [rows, C]."""
+def count_valid_labels(labels, ignore_index):
+    """Number of labels != ignore_index as fp32 [1] on the labels' device (overwritten, no host read):
+    the `valid_count` of the loss kernels below."""
+    if native(labels):
+        return ext().count_valid_labels(labels.reshape(-1).to(torch.int32).contiguous(), int(ignore_index))
+    return (labels != int(ignore_index)).sum().float().reshape(1)
+
+
+def _ignore_kw(ignore_index, valid_count):
+    """Trailing arguments of the native loss entry points: none without ignore_index, so a call
+    without one is the call it always was."""
+    if ignore_index is None:
+        if valid_count is not None:
+            raise ValueError("valid_count needs ignore_index")
+        return {}
+    return {"ignore_index": int(ignore_index), "valid_count": valid_count}
+
+
+def _ignore_scale(gscale, valid_count):
+    """CPU fallbacks: the gradient scale, 1 / max(valid_count, 1) when the count is given."""
+    return gscale if valid_count is None else 1.0 / valid_count.float().clamp_min(1.0)
+
+
+def xent_grad(probs2d, labels, onehot, gscale, sparse, ignore_index=None, valid_count=None):
+    """(p - y)*gscale and per-row CE; labels int32 [rows] (sparse) or onehot [rows, C].
+    ignore_index / valid_count (sparse only): as in softmax_xent."""
     rows, cols = probs2d.shape
+    if ignore_index is not None and not sparse:
+        raise ValueError("ignore_index needs sparse labels")
+    kw = _ignore_kw(ignore_index, valid_count)
     if native(probs2d):
         probs2d = probs2d.contiguous()
         d = torch.empty_like(probs2d)
         loss = torch.empty(rows, device=probs2d.device, dtype=torch.float32)
         ext().xent_grad(probs2d, labels.contiguous() if sparse else None,
-                        None if sparse else onehot.contiguous(), d, loss, rows, cols, gscale, sparse)
+                        None if sparse else onehot.contiguous(), d, loss, rows, cols, gscale, sparse, **kw)
         return d, loss
     p = probs2d.float()
+    if ignore_index is not None:
+        keep = labels.long() != int(ignore_index)
+        t = F.one_hot(labels.long().clamp(0, cols - 1), cols).float()
+        t = t * ((labels.long() >= 0) & (labels.long() < cols))[:, None]
+        # where, not a product: an ignored row may hold NaN, which must not leak
+        d = torch.where(keep[:, None], (p - t) * _ignore_scale(gscale, valid_count), torch.zeros_like(p))
+        loss = torch.where(keep, -(t * torch.log(p.clamp_min(1e-12))).sum(-1), torch.zeros(rows))
+        return d.to(probs2d.dtype), loss
     t = F.one_hot(labels.long(), cols).float() if sparse else onehot.float()
     d = ((p - t) * gscale).to(probs2d.dtype)
     loss = -(t * torch.log(p.clamp_min(1e-12))).sum(-1)
     return d, loss
 
 
-def softmax_xent(logits2d, labels, gscale, acc3=None):
-    """(dlogits, per-row CE) of softmax + sparse CE; acc3 (fp32 [3]) += {correct, sum CE, rows}."""
+def softmax_xent(logits2d, labels, gscale, acc3=None, ignore_index=None, valid_count=None):
+    """(dlogits, per-row CE) of softmax + sparse CE; acc3 (fp32 [3]) += {correct, sum CE, rows}.
+    ignore_index: rows with that label are left out (gradient row +0, CE 0, logits never read, not
+    counted in acc3). valid_count (fp32 [1] on the device, count_valid_labels): the gradient scale
+    is 1 / max(valid_count, 1) instead of gscale."""
     rows, cols = logits2d.shape
+    kw = _ignore_kw(ignore_index, valid_count)
     if native(logits2d):
         logits2d = logits2d.contiguous()
         d = torch.empty_like(logits2d)
         loss = torch.empty(rows, device=logits2d.device, dtype=torch.float32)
-        ext().softmax_xent(logits2d, labels.contiguous(), loss, d, rows, cols, gscale, acc3)
+        ext().softmax_xent(logits2d, labels.contiguous(), loss, d, rows, cols, gscale, acc3, **kw)
         return d, loss
     lf = logits2d.float()
     p = torch.softmax(lf, -1)
@@ -1190,6 +1229,15 @@ def softmax_xent(logits2d, labels, gscale, acc3=None):
     valid = (lab >= 0) & (lab < cols)
     t = F.one_hot(lab.clamp(0, cols - 1), cols).float() * valid[:, None]
     ce = -(t * torch.log_softmax(lf, -1)).sum(-1)
+    if ignore_index is not None:
+        keep = lab != int(ignore_index)
+        ce = torch.where(keep, ce, torch.zeros_like(ce))
+        if acc3 is not None:
+            acc3[0] += ((lf.argmax(-1) == lab) & keep).float().sum()
+            acc3[1] += ce.sum()
+            acc3[2] += keep.float().sum()
+        d = torch.where(keep[:, None], (p - t) * _ignore_scale(gscale, valid_count), torch.zeros_like(p))
+        return d.to(logits2d.dtype), ce
     if acc3 is not None:
         acc3[0] += (lf.argmax(-1) == lab).float().sum()
         acc3[1] += ce.sum()
@@ -1575,12 +1623,23 @@ def fill(out, v):
         out.fill_(v)
 
 
-def metrics_classify(probs2d, labels, acc3):
+def metrics_classify(probs2d, labels, acc3, ignore_index=None):
+    """acc3 += {correct, sum CE, rows}; rows labelled ignore_index are left out of all three."""
     if native(probs2d):
-        ext().metrics_classify(probs2d.contiguous(), labels.contiguous(), probs2d.shape[0], probs2d.shape[1], acc3)
+        kw = {} if ignore_index is None else {"ignore_index": int(ignore_index)}
+        ext().metrics_classify(probs2d.contiguous(), labels.contiguous(), probs2d.shape[0], probs2d.shape[1], acc3,
+                               **kw)
         return
     p = probs2d.float()
     lab = labels.long()
+    if ignore_index is not None:
+        keep = lab != int(ignore_index)
+        inr = keep & (lab >= 0) & (lab < p.shape[1])
+        acc3[0] += ((p.argmax(-1) == lab) & keep).float().sum()
+        pl = p.gather(1, lab.clamp(0, p.shape[1] - 1)[:, None])[:, 0]
+        acc3[1] += torch.where(inr, -torch.log(pl.clamp_min(1e-12)), torch.zeros_like(pl)).sum()
+        acc3[2] += keep.float().sum()
+        return
     acc3[0] += (p.argmax(-1) == lab).float().sum()
     acc3[1] += -torch.log(p.gather(1, lab[:, None]).clamp_min(1e-12)).sum()
     acc3[2] += p.shape[0]

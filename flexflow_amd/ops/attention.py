@@ -16,8 +16,8 @@ right-padded batch has L_b = clamp(key_lengths[b], 0, Sk) real keys; key j takes
 iff j < L_b (and j <= q with `causal`). Every query row is still computed (as with torch's
 key_padding_mask); L_b = 0 gives zero output rows and zero gradients. The lengths are read on the
 device only, by every path (flash, zero-padded head dims, fp32 device, reference, CPU), so a step
-that takes them still captures into a graph. Not covered: arbitrary masks, query-side skipping or
-packing, loss masking.
+that takes them still captures into a graph. The pad positions' labels are left out of the loss by
+`FFModel.compile(ignore_index=...)`. Not covered: arbitrary masks, query-side skipping or packing.
 
 Attention dropout (`dropout` = p in [0, 1), torch's `dropout_p`): in a training forward every
 attention probability is dropped with the effective rate p_eff = round(256 p) / 256 and the kept ones

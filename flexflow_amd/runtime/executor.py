@@ -73,7 +73,8 @@ def _device_for(config):
 
 
 class Executor:
-    def __init__(self, model, strategy: Dict[str, OpConfig], loss_type: Optional[LossType], metrics, training=True):
+    def __init__(self, model, strategy: Dict[str, OpConfig], loss_type: Optional[LossType], metrics, training=True,
+                 ignore_index: Optional[int] = None, loss_reduction: str = "batch"):
         self.model = model
         cfg = model.config
         self.config = cfg
@@ -91,6 +92,11 @@ class Executor:
         self.layers = list(model.layers)
         self.strategy = strategy
         self.loss_type = loss_type
+        # sparse cross-entropy only (FFModel.compile checks): rows labelled ignore_index are left out
+        # of loss, gradients and metrics; "valid" scales the gradient by 1 / #valid rows of the global
+        # batch (torch's reduction="mean") instead of 1 / batch
+        self.ignore_index = ignore_index
+        self.loss_reduction = loss_reduction
         self.metrics = list(metrics or [])
         self.step_idx = 0
         self.comm = Communicator(self.rank, self.world)
@@ -367,6 +373,8 @@ class Executor:
         self.loss_fwd_tx = Transfer(pl, self.loss_layout, pl.partial, self.rank)
         self.loss_bwd_tx = Transfer(self.loss_layout, pl.with_(partial=False), False, self.rank)
         self._rank_sets += self.loss_fwd_tx.rank_sets() + self.loss_bwd_tx.rank_sets()
+        if self.loss_reduction == "valid" and d0 > 1:
+            self._rank_sets.append(tuple(devs))  # the valid-label count is all-reduced over the batch shards
         owner = out.owner_layer
         self.softmax_fused = (owner.op_type == OperatorType.OP_SOFTMAX and self.loss_type in (
             LossType.LOSS_CATEGORICAL_CROSSENTROPY, LossType.LOSS_SPARSE_CATEGORICAL_CROSSENTROPY))
@@ -533,15 +541,28 @@ class Executor:
             rows = v.reshape(v.shape[0], -1) if lt != LossType.LOSS_SPARSE_CATEGORICAL_CROSSENTROPY else \
                 v.reshape(-1, v.shape[-1])
             logits = not self.softmax_fused or self._softmax_emitted_logits()
+            n_valid = None
             if lt == LossType.LOSS_SPARSE_CATEGORICAL_CROSSENTROPY:
                 labels = lab.reshape(-1).to(torch.int32)
+                ign = {}
+                if self.ignore_index is not None:
+                    ign["ignore_index"] = self.ignore_index
+                    if self.loss_reduction == "valid":
+                        n_valid = K.count_valid_labels(labels, self.ignore_index)
+                        ign["valid_count"] = self._global_valid_count(n_valid)
                 if not logits:
-                    g, lrow = K.xent_grad(rows.contiguous(), labels, None, 1.0 / B, True)
+                    g, lrow = K.xent_grad(rows.contiguous(), labels, None, 1.0 / B, True, **ign)
                     self._metric_acc[0] += lrow.sum()
                 else:  # fused softmax + cross-entropy (+ accuracy/CE metrics) straight from the logits
                     acc3 = torch.zeros(3, dtype=torch.float32, device=rows.device)
-                    g, lrow = K.softmax_xent(rows.contiguous(), labels, 1.0 / B, acc3)
-                    self._metric_acc[0] += acc3[1]
+                    g, lrow = K.softmax_xent(rows.contiguous(), labels, 1.0 / B, acc3, **ign)
+                    if ign:
+                        # the per-row losses summed in a fixed order: acc3[1] gathers them by float
+                        # atomics in whatever order the waves finish, so two identical steps report
+                        # losses a few ulps apart; the masked loss is reproducible run to run
+                        self._metric_acc[0] += lrow.sum()
+                    else:
+                        self._metric_acc[0] += acc3[1]
                     self._xent_acc3 = acc3
                 self._lrow = lrow
             elif lt == LossType.LOSS_CATEGORICAL_CROSSENTROPY:
@@ -561,9 +582,25 @@ class Executor:
                 g = torch.full_like(v, 1.0 / B)
                 self._metric_acc[0] += v.float().sum()
             g = g.reshape(v.shape)
-            self._metric_acc[7] += v.shape[0]
+            if n_valid is not None:
+                # "valid": get_loss() is the mean CE per valid row. The local count, added on the
+                # device: metrics_snapshot sums the ranks
+                self._metric_acc[7] += n_valid[0]
+            else:
+                self._metric_acc[7] += v.shape[0]
             self._accumulate_metrics(v, lab)
         return self.loss_bwd_tx.run(self.comm, g, self._like(out))
+
+    def _global_valid_count(self, n_local):
+        """The valid-label count of the global batch: the local one, all-reduced over the ranks of
+        the loss layout when the batch is sharded. One one-element collective on the compute stream,
+        before the loss kernel that reads the result through its pointer: no host sync."""
+        devs = self.loss_layout.devices
+        if len(devs) <= 1 or not self.comm.distributed:
+            return n_local
+        n = n_local.clone()  # the local count still feeds the metrics
+        dist.all_reduce(n, group=self.comm.group(devs))
+        return n
 
     def _accumulate_metrics(self, v, lab):
         mets = set(self.metrics)
@@ -589,7 +626,10 @@ class Executor:
                 have_probs = self.softmax_fused and not self._softmax_emitted_logits()
                 acc3 = torch.zeros(3, dtype=torch.float32, device=v.device)
                 # argmax of logits == argmax of probabilities: accuracy needs no softmax pass
-                K.metrics_classify(rows.contiguous(), labels, acc3)
+                if lt == LossType.LOSS_SPARSE_CATEGORICAL_CROSSENTROPY and self.ignore_index is not None:
+                    K.metrics_classify(rows.contiguous(), labels, acc3, ignore_index=self.ignore_index)
+                else:
+                    K.metrics_classify(rows.contiguous(), labels, acc3)
                 self._metric_acc[1] += acc3[0]
                 self._metric_acc[3] += acc3[2]
                 if have_probs:
