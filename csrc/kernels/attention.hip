@@ -21,6 +21,7 @@
 #include "ops.h"
 #include "attention.h"
 #include "attn_dropout.h"
+#include <type_traits>
 #include <utility>
 
 namespace ffk {
@@ -1587,11 +1588,11 @@ int64_t attn_bwd_workspace_floats(int B, int H, int Sq, int Sk, int D) {
   return (int64_t)nkb * B * H * Sq * D + 2 * (int64_t)B * H * Sq + (int64_t)B * H * D * (2 + 2 * nkb);
 }
 
-// Forward structure: 3 (default) = 64 rows per wave (attn_fwd2_kernel; D = 64 and Sq >= 512, else
-// 1), 1 = 4 waves with LDS-DMA K/V staging, 0 = 4 waves through registers (also the fallback
-// without 16-B aligned K / V rows, and D = 128). All three run the same per-row arithmetic (bitwise
-// equal outputs). Removed in round 6 as measured slower: the persistent 64-rows-per-wave kernel
-// and the 8-wave ping-pong (profiles/attn_fwd_variants_r4.txt, attn_fwd_pingpong_r4.txt).
+// Forward structure: 3 (default) = 64 rows per wave (attn_fwd2_kernel; D = 64, Sq >= 512 and no
+// dropout, else 1), 1 = 4 waves with LDS-DMA K/V staging, 0 = 4 waves through registers (also the
+// fallback without 16-B aligned K / V rows, and D = 128). All three run the same per-row arithmetic
+// (bitwise equal outputs). Removed in round 6 as measured slower: the persistent 64-rows-per-wave
+// kernel and the 8-wave ping-pong (profiles/attn_fwd_variants_r4.txt, attn_fwd_pingpong_r4.txt).
 // attn_set_fwd_variant; default from FF_ATTN_FWD; other values mean 3.
 static int g_fwd_variant = -1;
 int attn_fwd_variant() {
@@ -1669,75 +1670,70 @@ void attn_dropout_mask(uint8_t* out, int B, int H, int Sq, int Sk, int b0, int h
                      H_total, rng_step, rng_seed, drop_thr);
 }
 
+// LDS-DMA staging of a [rows][D] operand (row stride ss elements) needs 16-B aligned rows and
+// buffer offsets below 2 GiB, one tile past the last row included
+static bool dma_rows_ok(const void* p, int64_t ss, int rows) {
+  return ((uintptr_t)p & 15) == 0 && ss % 8 == 0 && (int64_t)(rows + 64) * ss * 2 < 0x7fffffffLL;
+}
+
+// one workgroup per 128 QB query rows of a (batch, head), QB 32-row blocks per wave: QB = 2 is
+// attn_fwd2_kernel (D = 64, LDS-DMA, no dropout form), QB = 1 attn_fwd_kernel, whose DROP
+// instantiations are always MASK = true
+template <int D, int QB, bool DMA>
+static void launch_fwd(const AttnArgs& a, bool mask, hipStream_t st) {
+  constexpr int ROWS = 128 * QB;
+  const dim3 grid((unsigned)((a.Sq + ROWS - 1) / ROWS * a.B * a.H));
+  if constexpr (QB == 2) {
+    static_assert(D == 64 && DMA, "attn_fwd2_kernel is fixed to D = 64 and LDS-DMA staging");
+    if (mask) hipLaunchKernelGGL((attn_fwd2_kernel<true>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((attn_fwd2_kernel<false>), grid, dim3(256), 0, st, a);
+  } else if (a.drop_thr > 0) {
+    hipLaunchKernelGGL((attn_fwd_kernel<D, true, DMA, true>), grid, dim3(256), 0, st, a);
+  } else if (mask) {
+    hipLaunchKernelGGL((attn_fwd_kernel<D, true, DMA>), grid, dim3(256), 0, st, a);
+  } else {
+    hipLaunchKernelGGL((attn_fwd_kernel<D, false, DMA>), grid, dim3(256), 0, st, a);
+  }
+}
+
 void attn_fwd(AttnArgs a, hipStream_t st) {
-  const dim3 grid((unsigned)((a.Sq + 127) / 128 * a.B * a.H));
   const bool mask = a.causal || a.Sk % 64 != 0 || a.key_lens != nullptr;
   a.rescale_thr = attn_rescale_thr();
-  // the DMA path needs 16-B aligned K / V rows and buffer offsets below 2 GiB
-  const bool dma_ok = ((uintptr_t)a.k & 15) == 0 && ((uintptr_t)a.v & 15) == 0 && a.k_ss % 8 == 0 &&
-                      a.v_ss % 8 == 0 && (int64_t)(a.Sk + 64) * a.k_ss * 2 < 0x7fffffffLL &&
-                      (int64_t)(a.Sk + 64) * a.v_ss * 2 < 0x7fffffffLL;
-  const bool dma = attn_fwd_variant() >= 1 && dma_ok;
-  if (a.drop_thr > 0) {
-    // attention dropout: the DROP instantiations of the 4-wave kernel (always MASK = true);
-    // attn_fwd2_kernel's DROP form (230 VGPRs, no scratch) measured slower than this kernel's: 60.1
-    // against 57.8 us at B32 H16 S512 (docs/PERFORMANCE.md, 'Attention dropout'), so it has none
-    if (a.H_total <= 0) a.H_total = a.H;
-    if (a.D == 64) {
-      if (dma) hipLaunchKernelGGL((attn_fwd_kernel<64, true, true, true>), grid, dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((attn_fwd_kernel<64, true, false, true>), grid, dim3(256), 0, st, a);
-    } else if (a.D == 128) {
-      hipLaunchKernelGGL((attn_fwd_kernel<128, true, false, true>), grid, dim3(256), 0, st, a);
-    }
-    return;
-  }
-  // 64 query rows per wave (attn_fwd2_kernel): 2-6 % faster from S = 512 up, slower at S = 256
-  // (half the workgroups), profiles/attn_fwd_variants_r4.txt
-  if (attn_fwd_variant() == 3 && dma_ok && a.D == 64 && a.Sq >= 512) {
-    const dim3 g3((unsigned)((a.Sq + 255) / 256 * a.B * a.H));
-    if (mask) hipLaunchKernelGGL((attn_fwd2_kernel<true>), g3, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((attn_fwd2_kernel<false>), g3, dim3(256), 0, st, a);
-    return;
-  }
+  const bool drop = a.drop_thr > 0;
+  if (drop && a.H_total <= 0) a.H_total = a.H;
+  const int v = attn_fwd_variant();
+  const bool dma_ok = dma_rows_ok(a.k, a.k_ss, a.Sk) && dma_rows_ok(a.v, a.v_ss, a.Sk);
   if (a.D == 64) {
-    if (dma) {
-      if (mask) hipLaunchKernelGGL((attn_fwd_kernel<64, true, true>), grid, dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((attn_fwd_kernel<64, false, true>), grid, dim3(256), 0, st, a);
-    } else {
-      if (mask) hipLaunchKernelGGL((attn_fwd_kernel<64, true, false>), grid, dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((attn_fwd_kernel<64, false, false>), grid, dim3(256), 0, st, a);
-    }
+    // 64 query rows per wave (attn_fwd2_kernel): 2-6 % faster from S = 512 up, slower at S = 256
+    // (half the workgroups), profiles/attn_fwd_variants_r4.txt; its DROP form (230 VGPRs, no
+    // scratch) measured slower at S = 512 too, 60.1 against 57.8 us at B32 H16 (docs/PERFORMANCE.md
+    // 'Attention dropout'), so it has none
+    if (v == 3 && dma_ok && !drop && a.Sq >= 512) launch_fwd<64, 2, true>(a, mask, st);
+    else if (v >= 1 && dma_ok) launch_fwd<64, 1, true>(a, mask, st);
+    else launch_fwd<64, 1, false>(a, mask, st);
   } else if (a.D == 128) {
-    if (mask) hipLaunchKernelGGL((attn_fwd_kernel<128, true, false>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((attn_fwd_kernel<128, false, false>), grid, dim3(256), 0, st, a);
+    launch_fwd<128, 1, false>(a, mask, st);
   }
 }
 
-// attention dropout: the DROP instantiations of attn_bwd_kernel (always MASK = true)
+// attn_bwd_kernel, chained (one launch per key block) or as slabs; the DROP instantiations
+// (attention dropout) are always MASK = true
 template <int D, int NW, bool DMA = false>
-static void launch_bwd_drop(AttnArgs a, int nkb, bool chain, hipStream_t st) {
-  const int bh = a.B * a.H;
-  if (chain) {
-    for (int p = 0; p < nkb; ++p)
-      hipLaunchKernelGGL((attn_bwd_kernel<D, NW, true, true, DMA, true>), dim3(bh), dim3(64 * NW), 0, st, a, nkb, p);
-  } else {
-    hipLaunchKernelGGL((attn_bwd_kernel<D, NW, true, false, DMA, true>), dim3(bh * nkb), dim3(64 * NW), 0, st, a, nkb, 0);
-  }
-}
-
-template <int D, int NW, bool DMA = false>
-static void launch_bwd_main(AttnArgs a, int nkb, bool chain, hipStream_t st) {
+static void launch_bwd(const AttnArgs& a, int nkb, bool chain, hipStream_t st) {
   const bool mask = a.causal || a.Sk % (32 * NW) != 0 || a.Sq % 64 != 0 || a.key_lens != nullptr;
   const int bh = a.B * a.H;
-  if (chain) {
-    for (int p = 0; p < nkb; ++p) {
-      if (mask) hipLaunchKernelGGL((attn_bwd_kernel<D, NW, true, true, DMA>), dim3(bh), dim3(64 * NW), 0, st, a, nkb, p);
-      else hipLaunchKernelGGL((attn_bwd_kernel<D, NW, false, true, DMA>), dim3(bh), dim3(64 * NW), 0, st, a, nkb, p);
+  auto go = [&](auto m, auto d) {
+    constexpr bool MASK = decltype(m)::value, DROP = decltype(d)::value;
+    if (chain) {
+      for (int p = 0; p < nkb; ++p)
+        hipLaunchKernelGGL((attn_bwd_kernel<D, NW, MASK, true, DMA, DROP>), dim3(bh), dim3(64 * NW), 0, st, a, nkb, p);
+    } else {
+      hipLaunchKernelGGL((attn_bwd_kernel<D, NW, MASK, false, DMA, DROP>), dim3(bh * nkb), dim3(64 * NW), 0, st, a, nkb, 0);
     }
-  } else {
-    if (mask) hipLaunchKernelGGL((attn_bwd_kernel<D, NW, true, false, DMA>), dim3(bh * nkb), dim3(64 * NW), 0, st, a, nkb, 0);
-    else hipLaunchKernelGGL((attn_bwd_kernel<D, NW, false, false, DMA>), dim3(bh * nkb), dim3(64 * NW), 0, st, a, nkb, 0);
-  }
+  };
+  if (a.drop_thr > 0) go(std::true_type{}, std::true_type{});
+  else if (mask) go(std::true_type{}, std::false_type{});
+  else go(std::false_type{}, std::false_type{});
 }
 
 bool attn_bwd(AttnArgs a, hipStream_t st) {
@@ -1757,17 +1753,13 @@ bool attn_bwd(AttnArgs a, hipStream_t st) {
   const bool chain = a.B * a.H >= 256;
   const bool finish = !chain && nkb > 1;
   // the DMA paths need 16-B aligned Q / dO rows and buffer offsets below 2 GiB
-  const bool dma_ok = v == 10 && ((uintptr_t)a.q & 15) == 0 && ((uintptr_t)a.dout & 15) == 0 && a.q_ss % 8 == 0 &&
-                      a.do_ss % 8 == 0 && (int64_t)(a.Sq + 64) * a.q_ss * 2 < 0x7fffffffLL &&
-                      (int64_t)(a.Sq + 64) * a.do_ss * 2 < 0x7fffffffLL;
+  const bool dma_ok = v == 10 && dma_rows_ok(a.q, a.q_ss, a.Sq) && dma_rows_ok(a.dout, a.do_ss, a.Sq);
   if (a.D == 64) {
     hipLaunchKernelGGL(attn_bwd_pre_kernel<64>, gpre, dim3(256), 0, st, a);
-    if (drop) {
-      // attn_bwd1b_kernel has no DROP instantiation (it uses every VGPR already): the generic kernel
-      // runs the chained form too, and the fused bias gradient is left to the caller (returns false)
-      if (dma_ok) launch_bwd_drop<64, 8, true>(a, nkb, chain, st);
-      else launch_bwd_drop<64, 8>(a, nkb, chain, st);
-    } else if (chain && dma_ok) {
+    // attn_bwd1b_kernel has no DROP instantiation (it uses every VGPR already): with dropout the
+    // generic kernel runs the chained form too, and the fused bias gradient is left to the caller
+    // (returns false)
+    if (chain && dma_ok && !drop) {
       const bool m = a.causal || a.Sk % 256 != 0 || a.Sq % 64 != 0 || a.key_lens != nullptr;
       const int bh = a.B * a.H;
       // fused bias-gradient sums: non-causal (every query tile's last key block is the last launch)
@@ -1778,15 +1770,14 @@ bool attn_bwd(AttnArgs a, hipStream_t st) {
         else hipLaunchKernelGGL((attn_bwd1b_kernel<false, true, true>), dim3(bh), dim3(512), 0, st, a, nkb, p);
       }
     } else if (dma_ok) {
-      launch_bwd_main<64, 8, true>(a, nkb, chain, st);
+      launch_bwd<64, 8, true>(a, nkb, chain, st);
     } else {
-      launch_bwd_main<64, 8>(a, nkb, chain, st);
+      launch_bwd<64, 8>(a, nkb, chain, st);
     }
     if (finish) hipLaunchKernelGGL(attn_dq_finish_kernel<64>, gfin, dim3(256), 0, st, a, nkb);
   } else if (a.D == 128) {
     hipLaunchKernelGGL(attn_bwd_pre_kernel<128>, gpre, dim3(256), 0, st, a);
-    if (drop) launch_bwd_drop<128, 4>(a, nkb, chain, st);
-    else launch_bwd_main<128, 4>(a, nkb, chain, st);
+    launch_bwd<128, 4>(a, nkb, chain, st);
     if (finish) hipLaunchKernelGGL(attn_dq_finish_kernel<128>, gfin, dim3(256), 0, st, a, nkb);
   }
   if (bias_done)

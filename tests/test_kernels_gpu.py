@@ -250,6 +250,35 @@ def test_flash_attention(ffC, S, D, causal, variant):
     ffC.attn_set_bwd_variant(prev_variant)
 
 
+def test_flash_attention_fwd_cross_lengths(ffC):
+    """Forward with Sq != Sk at Sq >= 512: Sq = 577 leaves the 64-rows-per-wave form a last query
+    block of 65 rows (one full 64-row wave, one wave with a single row, two empty) and the
+    32-rows-per-wave forms one of 65 as well; Sk = 130 ends in a 2-key tile. Non-causal. The three
+    forward structures are bitwise equal and match fp32 torch."""
+    torch.manual_seed(5)
+    B, H, D, Sq, Sk = 1, 2, 64, 577, 130
+    q = torch.randn(B, H, Sq, D, device=DEV).bfloat16()
+    k = torch.randn(B, H, Sk, D, device=DEV).bfloat16()
+    v = torch.randn(B, H, Sk, D, device=DEV).bfloat16()
+    sq, sk = [H * Sq * D, Sq * D, D], [H * Sk * D, Sk * D, D]
+    scale = 1.0 / math.sqrt(D)
+    prev_fwd = ffC.attn_fwd_variant()
+    outs = {}
+    try:
+        for fv in (0, 1, 3):
+            ffC.attn_set_fwd_variant(fv)
+            o, lse = torch.full_like(q, 3.0), torch.full((B * H * Sq,), 3.0, device=DEV)
+            ffC.attn_fwd(q, sq, k, sk, v, sk, o, sq, lse, B, H, Sq, Sk, D, scale, False)
+            outs[fv] = (o, lse)
+    finally:
+        ffC.attn_set_fwd_variant(prev_fwd)
+    for fv in (1, 3):
+        assert torch.equal(outs[0][0], outs[fv][0]) and torch.equal(outs[0][1], outs[fv][1]), fv
+    ref, ref_lse = _attn_ref(q.float(), k.float(), v.float(), scale, False)
+    assert _rel(outs[3][0], ref) < 2e-2
+    assert _rel(outs[3][1].view(B, H, Sq), ref_lse) < 1e-3
+
+
 @pytest.mark.parametrize("thr", [0.0, 3.0, 8.0])
 @pytest.mark.parametrize("ramp,causal", [(2.0, False), (-2.0, False), (6.0, True), (0.5, True)])
 def test_flash_attention_deferred_max(ffC, thr, ramp, causal):
