@@ -1,6 +1,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 namespace ffk {
 
@@ -59,5 +60,34 @@ void key_len_mask_f32(float* s, int64_t rows, int Sk, const int* key_len, float 
 // C[M,N] bf16 = (A.B) * act'(zin), colpart as above. False when the shape / alignment does not
 // fit the 256-row kernel's coalesced epilogue (the caller then runs GEMM + bias_act_bwd).
 bool gemm_dact_bf16(GemmArgs p, hipStream_t stream);
+
+// ---- host helpers shared by the gemm*.hip launchers
+
+// Calls f(A_K, B_K) with the operand orientations as std::bool_constant values, so that a generic
+// lambda launches the <A_K, B_K> instantiation of its kernel.
+template <class F>
+inline void gemm_with_layout(bool a_kcontig, bool b_kcontig, F&& f) {
+  if (a_kcontig && b_kcontig) f(std::true_type(), std::true_type());
+  else if (a_kcontig) f(std::true_type(), std::false_type());
+  else if (b_kcontig) f(std::false_type(), std::true_type());
+  else f(std::false_type(), std::false_type());
+}
+
+// What every LDS-DMA kernel (gemm_big, gemm256, gemm_pp) needs of its operands: 16-B aligned bases
+// and rows, whole 8-element chunks along an MN-contiguous extent, byte extents that fit the 31 bits
+// of a buffer descriptor's range. Each entry adds its own conditions (K multiple, batch strides,
+// tile floor, non-empty extents, store limits).
+inline bool gemm_dma_operands_ok(const GemmArgs& p, int64_t a_bytes, int64_t b_bytes) {
+  if (a_bytes > 0x7fffffffLL || b_bytes > 0x7fffffffLL) return false;
+  if (((uintptr_t)p.A & 15) || ((uintptr_t)p.B & 15) || p.lda % 8 || p.ldb % 8) return false;
+  if (!p.a_kcontig && p.M % 8) return false;
+  if (!p.b_kcontig && p.N % 8) return false;
+  return true;
+}
+
+// K extent of one split-K slice: ceil(K / splitk) rounded up to the kernel's K granule
+inline int gemm_kchunk(int K, int splitk, int granule) {
+  return ((K + splitk - 1) / splitk + granule - 1) / granule * granule;
+}
 
 }  // namespace ffk

@@ -17,22 +17,21 @@
 // accumulator holds 4 consecutive output columns per lane -> 8/16-B epilogue stores.
 // Block ids are remapped XCD-aware (T1, bijective) and grouped along M for L2 reuse.
 // Split-K writes fp32 partial slabs that a second kernel reduces and finishes the epilogue.
+// The LDS images, the fragment read and the tile order are the ones of gemm_tile.h, the scattered
+// epilogue is gemm_scatter_epilogue.h, all shared with the LDS-DMA kernels; the register staging
+// (Stager) is this kernel's own.
 //
 // Replaces the reference's cuBLAS Linear/BatchMatmul kernels
 // (reference: src/ops/kernels/linear_kernels.cu forward_kernel/backward_kernel,
 //  src/ops/batch_matmul.cu).
-#include "common.h"
-#include "gemm.h"
+#include "gemm_tile.h"
 #include "ops.h"
 
 namespace ffk {
+using namespace gtile;
 
 constexpr int BM = 128, BN = 128, BK = 64, NT = 256;
 constexpr int TILE_BYTES = BM * BK * 2;  // 16 KiB per operand tile
-
-__device__ __forceinline__ int swz_mn(int row) {  // 256-B row image, T10 (b)
-  return ((row & 3) << 2) | ((row >> 2) & 3);
-}
 
 // ALIGNED: rows of the contiguous dim start 16-B aligned and its extent is a multiple of 8, so a
 // whole 8-element chunk is in or out of bounds and loads as one dwordx4. Otherwise (e.g. a 30522-
@@ -97,48 +96,6 @@ struct Stager {
   }
 };
 
-// Read one 16x32 (rows x k) bf16 fragment for mfma_16x16x32: lane holds row r0+(l&15),
-// k = 32*kk + 8*(l>>4) + j, j=0..7.
-template <bool KCONT>
-__device__ __forceinline__ bf16x8 read_frag(const char* lds, int r0, int kk, int lane) {
-  if (KCONT) {
-    const int row = r0 + (lane & 15);
-    const int c = kk * 4 + (lane >> 4);
-    return *reinterpret_cast<const bf16x8*>(lds + row * 128 + ((c ^ (row & 7)) << 4));
-  } else {
-    const int g = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
-    const int chunk = (r0 >> 3) + (p >> 1);
-    bf16x8 out;
-#pragma unroll
-    for (int hf = 0; hf < 2; ++hf) {
-      const int krow = 32 * kk + 8 * g + 4 * hf + q;
-      const int off = krow * 256 + ((chunk ^ swz_mn(krow)) << 4) + 8 * (p & 1);
-      typedef short v4s __attribute__((ext_vector_type(4)));
-      v4s v = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-          (__attribute__((address_space(3))) v4s*)(lds + off));
-      bf16x4 b = __builtin_bit_cast(bf16x4, v);
-      out[4 * hf + 0] = b[0];
-      out[4 * hf + 1] = b[1];
-      out[4 * hf + 2] = b[2];
-      out[4 * hf + 3] = b[3];
-    }
-    return out;
-  }
-}
-
-__device__ __forceinline__ void tile_coords(int bid, int tm, int tn, int& tile_m, int& tile_n) {
-  const int nwg = tm * tn;
-  bid = xcd_remap(bid, nwg);
-  constexpr int GM = 8;
-  const int per_group = GM * tn;
-  const int group = bid / per_group;
-  const int first_m = group * GM;
-  const int gsize = min(tm - first_m, GM);
-  const int in_g = bid % per_group;
-  tile_m = first_m + in_g % gsize;
-  tile_n = in_g / gsize;
-}
-
 // OUT_MODE: 0 = bf16 output with full epilogue, 1 = fp32 output with full epilogue,
 //           2 = fp32 split-K partial (alpha only, no beta/bias/act)
 template <bool A_K, bool B_K, int OUT_MODE, bool A_AL = true, bool B_AL = true>
@@ -187,9 +144,9 @@ __global__ void __launch_bounds__(NT, 2) gemm_kernel(GemmArgs p) {
     for (int kk = 0; kk < 2; ++kk) {
       bf16x8 af[4], bfr[4];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) af[i] = read_frag<A_K>(cur, wm * 64 + i * 16, kk, lane);
+      for (int i = 0; i < 4; ++i) af[i] = frag<A_K, BK, false>(cur, wm * 64 + i * 16, kk, lane);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) bfr[j] = read_frag<B_K>(cur + TILE_BYTES, wn * 64 + j * 16, kk, lane);
+      for (int j = 0; j < 4; ++j) bfr[j] = frag<B_K, BK, false>(cur + TILE_BYTES, wn * 64 + j * 16, kk, lane);
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int i = 0; i < 4; ++i)
@@ -208,6 +165,7 @@ __global__ void __launch_bounds__(NT, 2) gemm_kernel(GemmArgs p) {
   // Epilogue: lane holds C[m][n..n+3], m = m0+wm*64+i*16+(lane&15), n = n0+wn*64+j*16+(lane>>4)*4.
   const int mrow = m0 + wm * 64 + (lane & 15);
   const int ncol = n0 + wn * 64 + (lane >> 4) * 4;
+  // Own slab write: the shared text's wording of it compiles to another (shorter, untimed) stream here.
   if (OUT_MODE == 2) {
     float* W = p.ws + (int64_t)z * p.M * p.N;
 #pragma unroll
@@ -231,54 +189,8 @@ __global__ void __launch_bounds__(NT, 2) gemm_kernel(GemmArgs p) {
     }
     return;
   }
-  typedef typename std::conditional<OUT_MODE == 0, bf16_t, float>::type OutT;
-  OutT* C = reinterpret_cast<OutT*>(p.C) + (int64_t)b * p.sC;
-  bf16_t* Zp = p.Z ? reinterpret_cast<bf16_t*>(p.Z) + (int64_t)b * p.sC : nullptr;
-  const bool vec_ok = p.vec_ok;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int m = mrow + i * 16;
-    if (m >= p.M) continue;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int n = ncol + j * 16;
-      if (n >= p.N) continue;
-      float v[4];
-      const bool full = vec_ok && (n + 3 < p.N);
-      OutT* dst = C + (int64_t)m * p.ldc + n;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float x = acc[i][j][r] * p.alpha;
-        if (p.beta != 0.f && n + r < p.N) x += p.beta * Cvt<OutT>::to_f(dst[r]);
-        if (p.bias && n + r < p.N) x += p.bias_bf16 ? bf2f(((const bf16_t*)p.bias)[n + r]) : ((const float*)p.bias)[n + r];
-        v[r] = x;
-      }
-      if (Zp) {
-        bf16_t* zd = Zp + (int64_t)m * p.ldc + n;
-        if (full) {
-          ushort4 o; o.x = f2bf(v[0]); o.y = f2bf(v[1]); o.z = f2bf(v[2]); o.w = f2bf(v[3]);
-          *reinterpret_cast<ushort4*>(zd) = o;
-        } else {
-          for (int r = 0; r < 4; ++r) if (n + r < p.N) zd[r] = f2bf(v[r]);
-        }
-      }
-      if (p.act != ACT_NONE) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = act_fwd(p.act, v[r]);
-      }
-      if (full) {
-        if (OUT_MODE == 0) {
-          ushort4 o; o.x = f2bf(v[0]); o.y = f2bf(v[1]); o.z = f2bf(v[2]); o.w = f2bf(v[3]);
-          *reinterpret_cast<ushort4*>(dst) = o;
-        } else {
-          *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
-        }
-      } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) if (n + r < p.N) dst[r] = Cvt<OutT>::from_f(v[r]);
-      }
-    }
-  }
+  constexpr int NI = 4, NJ = 4;
+#include "gemm_scatter_epilogue.h"
 }
 
 // Split-K reduction + epilogue: ws holds batch*splitk slabs of [M][N] fp32.
@@ -335,10 +247,9 @@ static void launch_tiled(const GemmArgs& p, dim3 grid, hipStream_t s, bool a_al,
 
 template <int MODE>
 static void dispatch_layout(const GemmArgs& p, dim3 grid, hipStream_t s, bool a_al, bool b_al) {
-  if (p.a_kcontig && p.b_kcontig) launch_tiled<true, true, MODE>(p, grid, s, a_al, b_al);
-  else if (p.a_kcontig && !p.b_kcontig) launch_tiled<true, false, MODE>(p, grid, s, a_al, b_al);
-  else if (!p.a_kcontig && p.b_kcontig) launch_tiled<false, true, MODE>(p, grid, s, a_al, b_al);
-  else launch_tiled<false, false, MODE>(p, grid, s, a_al, b_al);
+  gemm_with_layout(p.a_kcontig, p.b_kcontig, [&](auto ak, auto bk) {
+    launch_tiled<decltype(ak)::value, decltype(bk)::value, MODE>(p, grid, s, a_al, b_al);
+  });
 }
 
 static bool aligned16(const void* ptr) { return ((uintptr_t)ptr & 15) == 0; }
@@ -405,7 +316,7 @@ void gemm_bf16(GemmArgs p, hipStream_t stream) {
   }
   const int tm = (p.M + BM - 1) / BM, tn = (p.N + BN - 1) / BN;
   if (p.splitk > 1 && p.ws != nullptr) {
-    p.kchunk = ((p.K + p.splitk - 1) / p.splitk + BK - 1) / BK * BK;
+    p.kchunk = gemm_kchunk(p.K, p.splitk, BK);
     dim3 grid(tm * tn, p.batch * p.splitk);
     if (!try_large(p, a_al, b_al, stream)) dispatch_layout<2>(p, grid, stream, a_al, b_al);
     if (p.skip_reduce) return;

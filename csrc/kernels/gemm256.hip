@@ -140,10 +140,9 @@ __global__ void __launch_bounds__(NT, 1) gemm256_kernel(GemmArgs p, int64_t a_by
 
 template <int BN, int MODE>
 static void launch(const GemmArgs& p, dim3 grid, hipStream_t s, int64_t ab, int64_t bb) {
-  if (p.a_kcontig && p.b_kcontig) hipLaunchKernelGGL((gemm256_kernel<true, true, BN, MODE>), grid, dim3(NT), 0, s, p, ab, bb);
-  else if (p.a_kcontig) hipLaunchKernelGGL((gemm256_kernel<true, false, BN, MODE>), grid, dim3(NT), 0, s, p, ab, bb);
-  else if (p.b_kcontig) hipLaunchKernelGGL((gemm256_kernel<false, true, BN, MODE>), grid, dim3(NT), 0, s, p, ab, bb);
-  else hipLaunchKernelGGL((gemm256_kernel<false, false, BN, MODE>), grid, dim3(NT), 0, s, p, ab, bb);
+  gemm_with_layout(p.a_kcontig, p.b_kcontig, [&](auto ak, auto bk) {
+    hipLaunchKernelGGL((gemm256_kernel<decltype(ak)::value, decltype(bk)::value, BN, MODE>), grid, dim3(NT), 0, s, p, ab, bb);
+  });
 }
 
 template <int BN>
@@ -169,13 +168,12 @@ bool gemm256_bf16(const GemmArgs& p0, int64_t a_bytes, int64_t b_bytes, hipStrea
   using namespace g256;
   GemmArgs p = p0;
   const int bn = gemm256_bn(p.M, p.N, p.batch, p.splitk > 1 && p.ws ? p.splitk : 1);
-  if (p.K % (bn == 256 ? 32 : 64) != 0 || a_bytes > 0x7fffffffLL || b_bytes > 0x7fffffffLL || a_bytes <= 0 || b_bytes <= 0) return false;
-  if (((uintptr_t)p.A & 15) || ((uintptr_t)p.B & 15) || p.lda % 8 || p.ldb % 8 || p.sA % 8 || p.sB % 8) return false;
-  if (!p.a_kcontig && p.M % 8) return false;
-  if (!p.b_kcontig && p.N % 8) return false;
+  if (p.K % (bn == 256 ? 32 : 64) != 0 || a_bytes <= 0 || b_bytes <= 0 || p.sA % 8 || p.sB % 8 ||
+      !gemm_dma_operands_ok(p, a_bytes, b_bytes))
+    return false;
   const bool split = p.splitk > 1 && p.ws != nullptr;
   if (!split) p.splitk = 1;
-  p.kchunk = split ? ((p.K + p.splitk - 1) / p.splitk + 63) / 64 * 64 : p.K;
+  p.kchunk = split ? gemm_kchunk(p.K, p.splitk, 64) : p.K;  // 64 for both tile widths
   const int tm = (p.M + BM - 1) / BM, tn = (p.N + bn - 1) / bn;
   dim3 grid(tm * tn, p.batch * p.splitk);
   const int mode = split ? 2 : (p.out_f32 ? 1 : 0);

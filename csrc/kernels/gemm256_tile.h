@@ -1,11 +1,13 @@
 // Shared tile machinery of the 256-row MFMA GEMMs (gemm256.hip: one output tile per workgroup;
 // kept separate so that variants can be built as their own translation units, guide rule 19).
+// The swizzles, the fragment read and the tile order come from gemm_tile.h, the scattered epilogue
+// from gemm_scatter_epilogue.h: every tiled bf16 kernel shares them.
 #pragma once
-#include "common.h"
-#include "gemm.h"
+#include "gemm_tile.h"
 
 namespace ffk {
 namespace g256 {
+using namespace gtile;
 
 constexpr int BM = 256, NT = 512;
 
@@ -15,16 +17,6 @@ constexpr int BM = 256, NT = 512;
 template <int BN> struct Geo;
 template <> struct Geo<256> { static constexpr int BK = 32, NBUF = 4; };
 template <> struct Geo<128> { static constexpr int BK = 64, NBUF = 3; };
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-// 16-B chunk swizzle of a K-contiguous row of BK bf16 (64-B rows: 4 chunks, 128-B rows: 8 chunks)
-template <int BK>
-__device__ __forceinline__ int swz_k(int row) {
-  if constexpr (BK == 32) return ((row >> 2) & 1) << 1;
-  else return row & 7;
-}
-__device__ __forceinline__ int swz_mn(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
 
 // One 1-KiB DMA piece of an operand tile. K-contiguous: 1024 / (2 BK) rows of 2 BK bytes.
 // MN-contiguous: 4 k-rows of one 128-wide half (256 B each).
@@ -44,48 +36,6 @@ __device__ __forceinline__ void dma_piece(__amdgpu_buffer_rsrc_t rsrc, char* lds
     elem = (int64_t)(k0 + krow) * ld + mn0 + half * 128 + c * 8;
   }
   __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)(lds_tile + piece * 1024), 16, (int)(elem * 2), 0, 0, 0);
-}
-
-// 16 (rows along M or N) x 32 (k, sub-step kk of the K-tile) fragment for mfma_f32_16x16x32_bf16.
-template <bool KCONT, int BK>
-__device__ __forceinline__ bf16x8 frag(const char* tile, int r0, int kk, int lane) {
-  if (KCONT) {
-    const int row = r0 + (lane & 15);
-    const int c = kk * 4 + (lane >> 4);
-    return *reinterpret_cast<const bf16x8*>(tile + row * (BK * 2) + ((c ^ swz_k<BK>(row)) << 4));
-  } else {
-    const char* hl = tile + (r0 >> 7) * (BK * 256);
-    const int rr = r0 & 127;
-    const int g = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
-    const int chunk = (rr >> 3) + (p >> 1);
-    bf16x8 out;
-#pragma unroll
-    for (int hf = 0; hf < 2; ++hf) {
-      const int krow = 32 * kk + 8 * g + 4 * hf + q;
-      const int off = krow * 256 + ((chunk ^ swz_mn(krow)) << 4) + 8 * (p & 1);
-      typedef short v4s __attribute__((ext_vector_type(4)));
-      v4s v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s*)(hl + off));
-      bf16x4 b = __builtin_bit_cast(bf16x4, v);
-      out[4 * hf + 0] = b[0];
-      out[4 * hf + 1] = b[1];
-      out[4 * hf + 2] = b[2];
-      out[4 * hf + 3] = b[3];
-    }
-    return out;
-  }
-}
-
-__device__ __forceinline__ void tile_coords(int bid, int tm, int tn, int& tile_m, int& tile_n) {
-  const int nwg = tm * tn;
-  bid = xcd_remap(bid, nwg);
-  constexpr int GM = 8;
-  const int per_group = GM * tn;
-  const int group = bid / per_group;
-  const int first_m = group * GM;
-  const int gsize = min(tm - first_m, GM);
-  const int in_g = bid % per_group;
-  tile_m = first_m + in_g % gsize;
-  tile_n = in_g / gsize;
 }
 
 __device__ __forceinline__ void barrier() {
@@ -267,77 +217,10 @@ __device__ __forceinline__ void store_tile(const GemmArgs& p, f32x4 (&acc)[8][WN
   }
 
   if constexpr (SCATTER) {
-  const int mrow = m0 + wr * 128 + (lane & 15);
-  const int ncol = n0 + wc * WN + (lane >> 4) * 4;
-  if (OUT_MODE == 2) {
-    float* W = p.ws + (int64_t)z * p.M * p.N;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int m = mrow + i * 16;
-      if (m >= p.M) continue;
-#pragma unroll
-      for (int j = 0; j < NF; ++j) {
-        const int n = ncol + j * 16;
-        float* dst = W + (int64_t)m * p.N + n;
-        if (n + 3 < p.N && (p.N & 3) == 0) {
-          *reinterpret_cast<float4*>(dst) = make_float4(acc[i][j][0] * p.alpha, acc[i][j][1] * p.alpha,
-                                                        acc[i][j][2] * p.alpha, acc[i][j][3] * p.alpha);
-        } else {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) if (n + r < p.N) dst[r] = acc[i][j][r] * p.alpha;
-        }
-      }
-    }
-    return;
-  }
-  typedef typename std::conditional<OUT_MODE == 0, bf16_t, float>::type OutT;
-  OutT* C = reinterpret_cast<OutT*>(p.C) + (int64_t)b * p.sC;
-  bf16_t* Zp = p.Z ? reinterpret_cast<bf16_t*>(p.Z) + (int64_t)b * p.sC : nullptr;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int m = mrow + i * 16;
-    if (m >= p.M) continue;
-#pragma unroll
-    for (int j = 0; j < NF; ++j) {
-      const int n = ncol + j * 16;
-      if (n >= p.N) continue;
-      float v[4];
-      const bool full = p.vec_ok && (n + 3 < p.N);
-      OutT* dst = C + (int64_t)m * p.ldc + n;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float x = acc[i][j][r] * p.alpha;
-        if (p.beta != 0.f && n + r < p.N) x += p.beta * Cvt<OutT>::to_f(dst[r]);
-        if (p.bias && n + r < p.N)
-          x += p.bias_bf16 ? bf2f(((const bf16_t*)p.bias)[n + r]) : ((const float*)p.bias)[n + r];
-        v[r] = x;
-      }
-      if (Zp) {
-        bf16_t* zd = Zp + (int64_t)m * p.ldc + n;
-        if (full) {
-          ushort4 o; o.x = f2bf(v[0]); o.y = f2bf(v[1]); o.z = f2bf(v[2]); o.w = f2bf(v[3]);
-          *reinterpret_cast<ushort4*>(zd) = o;
-        } else {
-          for (int r = 0; r < 4; ++r) if (n + r < p.N) zd[r] = f2bf(v[r]);
-        }
-      }
-      if (p.act != ACT_NONE) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = act_fwd(p.act, v[r]);
-      }
-      if (full) {
-        if (OUT_MODE == 0) {
-          ushort4 o; o.x = f2bf(v[0]); o.y = f2bf(v[1]); o.z = f2bf(v[2]); o.w = f2bf(v[3]);
-          *reinterpret_cast<ushort4*>(dst) = o;
-        } else {
-          *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
-        }
-      } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) if (n + r < p.N) dst[r] = Cvt<OutT>::from_f(v[r]);
-      }
-    }
-  }
+    constexpr int NI = 8, NJ = NF;
+    const int mrow = m0 + wr * 128 + (lane & 15);
+    const int ncol = n0 + wc * WN + (lane >> 4) * 4;
+#include "gemm_scatter_epilogue.h"
   }
 }
 

@@ -159,10 +159,9 @@ void gemm_f32(const GemmArgs& p, hipStream_t stream) {
   auto al = [](const void* q, int64_t ld, int64_t st) { return ((uintptr_t)q % 16) == 0 && ld % 4 == 0 && st % 4 == 0; };
   const bool va = al(p.A, p.lda, p.sA), vb = al(p.B, p.ldb, p.sB);
   dim3 grid(((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN), 1, p.batch);
-  if (p.a_kcontig && p.b_kcontig) launch<true, true>(p, grid, stream, va, vb);
-  else if (p.a_kcontig) launch<true, false>(p, grid, stream, va, vb);
-  else if (p.b_kcontig) launch<false, true>(p, grid, stream, va, vb);
-  else launch<false, false>(p, grid, stream, va, vb);
+  gemm_with_layout(p.a_kcontig, p.b_kcontig, [&](auto ak, auto bk) {
+    launch<decltype(ak)::value, decltype(bk)::value>(p, grid, stream, va, vb);
+  });
 }
 
 // scores[b][i][j] = -inf for j > i + (Sk - Sq): the causal mask of the fp32 attention path, before

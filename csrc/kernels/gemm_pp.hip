@@ -33,7 +33,7 @@
 //
 // Epilogue: alpha, bias (fp32 / bf16), bf16 or fp32 output, through a wave-private LDS image into
 // whole-row range-checked buffer stores (see epilogue()). Requires batch 1, beta 0, no activation, K % 64 == 0, 16-B aligned operand
-// rows, operands and output < 2 GiB. Image formats / swizzles: gemm_pp_core.h, gemm256_tile.h.
+// rows, operands and output < 2 GiB. Image formats / swizzles: gemm_pp_core.h, gemm_tile.h.
 #include "gemm_pp_core.h"
 
 namespace ffk {
@@ -602,10 +602,10 @@ gemm_pp_kernel(GemmArgs p, int64_t a_bytes, int64_t b_bytes) {
 
 template <bool F32OUT, bool SPLIT, int ACTK, bool HB>
 static void launch_hb(const GemmArgs& p, dim3 grid, hipStream_t s, int64_t ab, int64_t bb) {
-  if (p.a_kcontig && p.b_kcontig) hipLaunchKernelGGL((gemm_pp_kernel<true, true, F32OUT, SPLIT, ACTK, 0, HB>), grid, dim3(NTHR), 0, s, p, ab, bb);
-  else if (p.a_kcontig) hipLaunchKernelGGL((gemm_pp_kernel<true, false, F32OUT, SPLIT, ACTK, 0, HB>), grid, dim3(NTHR), 0, s, p, ab, bb);
-  else if (p.b_kcontig) hipLaunchKernelGGL((gemm_pp_kernel<false, true, F32OUT, SPLIT, ACTK, 0, HB>), grid, dim3(NTHR), 0, s, p, ab, bb);
-  else hipLaunchKernelGGL((gemm_pp_kernel<false, false, F32OUT, SPLIT, ACTK, 0, HB>), grid, dim3(NTHR), 0, s, p, ab, bb);
+  gemm_with_layout(p.a_kcontig, p.b_kcontig, [&](auto ak, auto bk) {
+    hipLaunchKernelGGL((gemm_pp_kernel<decltype(ak)::value, decltype(bk)::value, F32OUT, SPLIT, ACTK, 0, HB>), grid,
+                       dim3(NTHR), 0, s, p, ab, bb);
+  });
 }
 template <bool F32OUT, bool SPLIT, int ACTK = 0>
 static void launch(const GemmArgs& p, dim3 grid, hipStream_t s, int64_t ab, int64_t bb) {
@@ -643,12 +643,9 @@ bool gemm_pp_bf16(const GemmArgs& p, int64_t a_bytes, int64_t b_bytes, hipStream
                 (int64_t)p.splitk * p.M * p.N * 4 > 0x7fffff00LL))
     return false;
   if ((p.beta != 0.f && !split) || p.batch != 1 || p.K % BK != 0 ||
-      p.K <= 0 || a_bytes > 0x7fffffffLL || b_bytes > 0x7fffffffLL || a_bytes <= 0 || b_bytes <= 0)
+      p.K <= 0 || a_bytes <= 0 || b_bytes <= 0 || !gemm_dma_operands_ok(p, a_bytes, b_bytes))
     return false;
-  if (((uintptr_t)p.A & 15) || ((uintptr_t)p.B & 15) || p.lda % 8 || p.ldb % 8) return false;
   if ((int64_t)p.M * p.ldc * (p.out_f32 ? 4 : 2) > 0x7fffff00LL) return false;  // buffer-store offsets
-  if (!p.a_kcontig && p.M % 8) return false;
-  if (!p.b_kcontig && p.N % 8) return false;
   if (p.N % 8 || p.ldc % 8 || ((uintptr_t)p.C & 15)) return false;  // whole 8-column row stores
   if (p.bias && ((uintptr_t)p.bias & 15)) return false;
   if (g_pp_cus == 0) {

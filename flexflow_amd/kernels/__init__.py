@@ -577,11 +577,9 @@ def gemm(A, B, C, M, N, K, a_k, b_k, lda, ldb, ldc, alpha=1.0, beta=0.0, bias=No
             Z.copy_(Zf)
         return C
     # CPU reference (plain torch)
-    Af = A.as_strided((batch, M, K), (sA, lda, 1)) if a_k else A.as_strided((batch, K, M), (sA, lda, 1)).transpose(1, 2)
-    Bf = B.as_strided((batch, N, K), (sB, ldb, 1)).transpose(1, 2) if b_k else B.as_strided((batch, K, N), (sB, ldb, 1))
+    Af, Bf, Cv = _views(A, B, C, M, N, K, a_k, b_k, lda, ldb, ldc, batch, sA, sB, sC)
     cdt = torch.float32
     r = torch.matmul(Af.to(cdt), Bf.to(cdt)) * alpha
-    Cv = C.as_strided((batch, M, N), (sC, ldc, 1))
     if beta != 0.0:
         r = r + beta * Cv.to(cdt)
     if bias is not None:

@@ -195,6 +195,101 @@ def test_gemm_splitk_and_batch(ffC):
     assert _rel(C, torch.bmm(A.float(), B.float().transpose(1, 2))) < 1e-2
 
 
+_SCATTER_M = 2056
+_scatter_cache = {}
+
+
+def _scatter_case(N, K):
+    """Inputs and float64 references of test_gemm_scattered_epilogue, built once per (N, K) and only
+    read afterwards: Am [M][K], Bn [N][K] bf16, ab = Am . Bn^T and s = |Am| . |Bn|^T in float64."""
+    if (N, K) not in _scatter_cache:
+        g = torch.Generator(device=DEV).manual_seed(1000 * N + K)
+        Am = torch.randn(_SCATTER_M, K, device=DEV, generator=g).bfloat16()
+        Bn = torch.randn(N, K, device=DEV, generator=g).bfloat16()
+        ab = Am.double() @ Bn.double().t()
+        s = Am.double().abs() @ Bn.double().abs().t()
+        bias = torch.randn(N, device=DEV, generator=g)
+        c0 = torch.randn(_SCATTER_M, N, device=DEV, generator=g)
+        _scatter_cache[(N, K)] = (Am, Am.t().contiguous(), Bn, ab, s, bias, c0)
+    return _scatter_cache[(N, K)]
+
+
+def _guarded(M, N, dtype, fill):
+    """[M][N] output with ldc = N inside a larger buffer: one guard row before and one after."""
+    buf = torch.full(((M + 2) * N,), fill, device=DEV, dtype=dtype)
+    return buf, buf[N:(M + 1) * N].view(M, N)
+
+
+def _guards_intact(buf, M, N, fill):
+    return bool((buf[:N] == fill).all()) and bool((buf[(M + 1) * N:] == fill).all())
+
+
+@pytest.mark.parametrize("a_k,b_k", [(True, True), (False, True)])
+@pytest.mark.parametrize("N", [1898, 1900])
+@pytest.mark.parametrize("impl", [0, 1, 2])
+def test_gemm_scattered_epilogue(ffC, impl, N, a_k, b_k):
+    """The scattered epilogue (csrc/kernels/gemm_scatter_epilogue.h, one text shared by gemm.hip,
+    gemm_big.hip and gemm256_tile.h) element by element against a float64 reference: a wrong partial
+    quad of columns at a tile edge hides inside the Frobenius norms of the other GEMM tests.
+
+    M = 2056 (a multiple of 8, dead rows in the last row tile), N = 1898 (ldc % 4 != 0: no vector
+    stores, the last quad of columns partial) and N = 1900 (vector stores, N % 8 == 4: the 256-row
+    kernel takes its scattered branch with whole quads); 9 x 15 tiles of 256 x 128 >= the floor of
+    gemm_big. Cases: (i) bf16 out, bf16 bias, Z store, GELU; (ii) fp32 out, fp32 bias, alpha 0.5,
+    beta 1 over a random C; (iii) fp32 out, split-K 2 with a workspace, beta 1. Outputs without beta
+    start as a sentinel, and the guard rows around C and Z (ldc = N, so they are also the columns
+    >= N of the neighbouring rows) must keep theirs.
+
+    Tolerances, derived (s = sum_k |a_k| |b_k|): fp32 accumulation of K <= 128 products errs by at
+    most K 2^-24 s = 2^-17 s, rounding to bf16 by 2^-9 |ref|; with a factor of two (GELU' <= 1.13)
+    fp32 outputs must be within 2^-15 s + 2^-20 |ref| and bf16 outputs within 2^-8 |ref| + 2^-14 s.
+    A plain fp32 torch evaluation of the same formulas on the CPU stays inside these bounds (largest
+    error / bound over all elements: 0.007 for the fp32 cases, 0.97 for the bf16 case, where a
+    round-to-nearest just above a power of two takes all of 2^-8 |ref|), so they are not tighter
+    than the arithmetic allows. No element is exempt."""
+    M = _SCATTER_M
+    SENT = 777.0
+
+    def operands(K):
+        Am, At, Bn, ab, s, bias, c0 = _scatter_case(N, K)
+        return (Am if a_k else At), Bn, ab, s, bias, c0
+
+    def check(name, got, ref, s, bf16):
+        err = (got.double() - ref).abs()
+        tol = (2.0 ** -8 * ref.abs() + 2.0 ** -14 * s) if bf16 else (2.0 ** -15 * s + 2.0 ** -20 * ref.abs())
+        worst = (err / tol).max().item()
+        print(f"{name}: impl {impl} N {N} a_k {a_k}: max err/tol {worst:.3f}, max err {err.max().item():.3e}")
+        bad = int((err > tol).sum())
+        assert bad == 0, f"{name}: {bad} of {err.numel()} elements outside the bound (worst err/tol {worst:.2f})"
+
+    # (i) bf16 out, bf16 bias, pre-activation store, GELU
+    A, B, ab, s, bias, c0 = operands(64)
+    bias16 = bias.bfloat16()
+    cbuf, C = _guarded(M, N, torch.bfloat16, SENT)
+    zbuf, Z = _guarded(M, N, torch.bfloat16, SENT)
+    _gemm(ffC, A, B, C, M, N, 64, a_k, b_k, bias=bias16, Z=Z, act=14, impl=impl)
+    z_ref = ab + bias16.double()
+    check("Z", Z, z_ref, s, True)
+    check("gelu", C, 0.5 * z_ref * (1.0 + torch.erf(z_ref / math.sqrt(2.0))), s, True)
+    assert _guards_intact(cbuf, M, N, SENT) and _guards_intact(zbuf, M, N, SENT)
+
+    # (ii) fp32 out, fp32 bias, alpha = 0.5, beta = 1 over a random C
+    cbuf, C = _guarded(M, N, torch.float32, SENT)
+    C.copy_(c0)
+    _gemm(ffC, A, B, C, M, N, 64, a_k, b_k, bias=bias, alpha=0.5, beta=1.0, impl=impl)
+    check("f32 alpha beta bias", C, 0.5 * ab + c0.double() + bias.double(), s, False)
+    assert _guards_intact(cbuf, M, N, SENT)
+
+    # (iii) fp32 out, split-K 2 through a workspace, beta = 1
+    A, B, ab, s, bias, c0 = operands(128)
+    cbuf, C = _guarded(M, N, torch.float32, SENT)
+    C.copy_(c0)
+    ws = torch.full((2 * M * N,), SENT, device=DEV)
+    _gemm(ffC, A, B, C, M, N, 128, a_k, b_k, beta=1.0, splitk=2, ws=ws, impl=impl)
+    check("f32 split-K", C, ab + c0.double(), s, False)
+    assert _guards_intact(cbuf, M, N, SENT)
+
+
 def _attn_ref(q, k, v, scale, causal):
     s = torch.einsum("bhqd,bhkd->bhqk", q, k) * scale
     if causal:
