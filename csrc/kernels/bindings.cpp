@@ -424,8 +424,17 @@ void sgd_sparse_rows(Tensor idx, Tensor mark, Tensor master, Tensor grad, option
                        mark.data_ptr<int>(), master.data_ptr<float>(), grad.data_ptr<float>(), ptr(lowp), lr,
                        cur_stream());
 }
+// an optional one-element fp32 scalar on `like`'s device (alpha_dev / gscale_dev style arguments)
+const float* dev_scalar(const optional<Tensor>& t, const Tensor& like, const char* what) {
+  if (!t.has_value() || !t->defined()) return nullptr;
+  TORCH_CHECK(t->scalar_type() == at::kFloat && t->numel() == 1 && t->is_cuda() && t->device() == like.device(), what,
+              " must be a one-element fp32 tensor on the same device");
+  return t->data_ptr<float>();
+}
 void sgd_update(Tensor master, Tensor grad, optional<Tensor> mom, optional<Tensor> lowp, double lr,
-                double momentum, bool nesterov, double wd, double gscale, int64_t max_blocks) {
+                double momentum, bool nesterov, double wd, double gscale, int64_t max_blocks,
+                optional<Tensor> gscale_dev) {
+  const float* gsd = dev_scalar(gscale_dev, master, "sgd_update: gscale_dev");
   TORCH_CHECK(master.scalar_type() == at::kFloat && grad.scalar_type() == at::kFloat);
   TORCH_CHECK(master.numel() == grad.numel());
   if (momentum > 0) TORCH_CHECK(mom.has_value() && mom->numel() == master.numel());
@@ -441,10 +450,12 @@ void sgd_update(Tensor master, Tensor grad, optional<Tensor> mom, optional<Tenso
     check_aligned(*lowp, 8, "sgd_update: lowp");
   }
   ffk::sgd_update(master.data_ptr<float>(), grad.data_ptr<float>(), ptr<float>(mom), ptr(lowp), master.numel(), lr,
-                  momentum, nesterov, wd, gscale, cur_stream(), (int)max_blocks);
+                  momentum, nesterov, wd, gscale, cur_stream(), (int)max_blocks, gsd);
 }
 void adam_update(Tensor master, Tensor grad, Tensor m, Tensor v, optional<Tensor> lowp, double alpha_t, double b1,
-                 double b2, double wd, double eps, double gscale, int64_t max_blocks, optional<Tensor> alpha_dev) {
+                 double b2, double wd, double eps, double gscale, int64_t max_blocks, optional<Tensor> alpha_dev,
+                 optional<Tensor> gscale_dev) {
+  const float* gsd = dev_scalar(gscale_dev, master, "adam_update: gscale_dev");
   if (alpha_dev) TORCH_CHECK(alpha_dev->scalar_type() == at::kFloat && alpha_dev->numel() == 1 && alpha_dev->is_cuda(),
                              "adam_update: alpha_dev must be a one-element fp32 device tensor");
   TORCH_CHECK(master.numel() == grad.numel() && m.numel() == master.numel() && v.numel() == master.numel());
@@ -459,7 +470,23 @@ void adam_update(Tensor master, Tensor grad, Tensor m, Tensor v, optional<Tensor
   }
   ffk::adam_update(master.data_ptr<float>(), grad.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
                    ptr(lowp), master.numel(), alpha_t, b1, b2, wd, eps, gscale, cur_stream(), (int)max_blocks,
-                   alpha_dev ? alpha_dev->data_ptr<float>() : nullptr);
+                   alpha_dev ? alpha_dev->data_ptr<float>() : nullptr, gsd);
+}
+void grad_sumsq(Tensor x, Tensor partials, Tensor out, bool accumulate) {
+  check_dev(x, "x");
+  TORCH_CHECK(x.scalar_type() == at::kFloat && partials.scalar_type() == at::kFloat, "grad_sumsq: fp32");
+  check_contig(x, "grad_sumsq: x"); check_contig(partials, "grad_sumsq: partials");
+  check_aligned(x, 16, "grad_sumsq: x");
+  TORCH_CHECK(partials.is_cuda() && partials.numel() >= ffk::grad_sumsq_partials(),
+              "grad_sumsq: partials must hold ", ffk::grad_sumsq_partials(), " fp32 on the device");
+  dev_scalar(out, x, "grad_sumsq: out");
+  ffk::grad_sumsq(x.data_ptr<float>(), x.numel(), partials.data_ptr<float>(), out.data_ptr<float>(), accumulate,
+                  cur_stream());
+}
+void clip_coef(Tensor sumsq, double max_norm, Tensor norm, Tensor coef, double eps) {
+  dev_scalar(norm, sumsq, "clip_coef: norm"); dev_scalar(coef, sumsq, "clip_coef: coef");
+  ffk::clip_coef(dev_scalar(sumsq, sumsq, "clip_coef: sumsq"), max_norm, eps, norm.data_ptr<float>(),
+                 coef.data_ptr<float>(), cur_stream());
 }
 void embedding_fwd(Tensor idx, Tensor table, Tensor out, int64_t n_rows, int64_t bag, int64_t dim, bool avg) {
   TORCH_CHECK(idx.numel() == n_rows * bag && out.numel() == n_rows * dim && table.size(-1) == dim);
@@ -1047,11 +1074,16 @@ PYBIND11_MODULE(_C, m) {
         py::arg("out"), py::arg("ignore_index") = py::none());
   m.def("reduce_rows", &reduce_rows);
   m.def("sgd_update", &sgd_update, py::arg("master"), py::arg("grad"), py::arg("mom"), py::arg("lowp"), py::arg("lr"),
-        py::arg("momentum"), py::arg("nesterov"), py::arg("wd"), py::arg("gscale"), py::arg("max_blocks") = 0);
+        py::arg("momentum"), py::arg("nesterov"), py::arg("wd"), py::arg("gscale"), py::arg("max_blocks") = 0,
+        py::arg("gscale_dev") = py::none());
   m.def("sgd_sparse_rows", &sgd_sparse_rows);
   m.def("adam_update", &adam_update, py::arg("master"), py::arg("grad"), py::arg("m"), py::arg("v"), py::arg("lowp"),
         py::arg("alpha_t"), py::arg("b1"), py::arg("b2"), py::arg("wd"), py::arg("eps"), py::arg("gscale"),
-        py::arg("max_blocks") = 0, py::arg("alpha_dev") = py::none());
+        py::arg("max_blocks") = 0, py::arg("alpha_dev") = py::none(), py::arg("gscale_dev") = py::none());
+  m.def("grad_sumsq", &grad_sumsq, py::arg("x"), py::arg("partials"), py::arg("out"), py::arg("accumulate") = false);
+  m.def("grad_sumsq_partials", []() { return ffk::grad_sumsq_partials(); });
+  m.def("clip_coef", &clip_coef, py::arg("sumsq"), py::arg("max_norm"), py::arg("norm"), py::arg("coef"),
+        py::arg("eps") = 1e-6);
   m.def("embedding_fwd", &embedding_fwd);
   m.def("embedding_bwd", &embedding_bwd);
   m.def("init_uniform", &init_uniform);

@@ -127,9 +127,17 @@ void mse_grad(int dt, const void* pred, const void* label, void* dpred, float* l
 void sgd_sparse_rows(const int64_t* idx, int n, int64_t rows, int dim, int* mark, float* master, float* grad,
                      void* lowp, float lr, hipStream_t st);
 void sgd_update(float* master, const float* grad, float* mom, void* param_lowp, int64_t n, float lr, float momentum,
-                int nesterov, float wd, float gscale, hipStream_t st, int max_blocks = 0);
+                int nesterov, float wd, float gscale, hipStream_t st, int max_blocks = 0,
+                const float* gscale_dev = nullptr);
 void adam_update(float* master, const float* grad, float* m, float* v, void* param_lowp, int64_t n, float alpha_t,
-                 float beta1, float beta2, float wd, float eps, float gscale, hipStream_t st, int max_blocks = 0, const float* alpha_dev = nullptr);
+                 float beta1, float beta2, float wd, float eps, float gscale, hipStream_t st, int max_blocks = 0, const float* alpha_dev = nullptr,
+                 const float* gscale_dev = nullptr);
+// gradient clipping by global norm: out (+)= sum x^2 over n fp32 elements (x 16-byte aligned; partial:
+// grad_sumsq_partials() floats of caller-owned workspace; deterministic, no atomics), then
+// norm = sqrt(sumsq), coef = min(1, max_norm / (norm + eps)) for the updates' gscale_dev
+int grad_sumsq_partials();
+void grad_sumsq(const float* x, int64_t n, float* partial, float* out, int accumulate, hipStream_t st);
+void clip_coef(const float* sumsq, float max_norm, float eps, float* norm, float* coef, hipStream_t st);
 
 // embedding.hip
 void embedding_fwd(int dt, int idx64, const void* idx, const void* table, void* out, int64_t n_out_rows, int bag,

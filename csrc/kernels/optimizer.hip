@@ -11,7 +11,8 @@ namespace ffk {
 
 __global__ void sgd_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ v,
                            bf16_t* __restrict__ wl, int64_t n, float lr, float momentum, int nesterov, float wd,
-                           float gscale) {
+                           float gscale, const float* __restrict__ gscale_dev) {
+  if (gscale_dev) gscale *= *gscale_dev;
   const int64_t nv = n / 4;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += stride) {
@@ -52,10 +53,14 @@ __global__ void sgd_kernel(float* __restrict__ w, const float* __restrict__ g, f
 
 // alpha_dev: the step size read from device memory instead of the argument (a captured hipGraph
 // of the whole training step replays one launch whose alpha_t changes every step)
+// gscale_dev (both kernels): a device factor multiplied into gscale, the clipping coefficient
+// clip_coef leaves on the device; the weight-decay term wd * w is not scaled by it
 __global__ void adam_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m,
                             float* __restrict__ v, bf16_t* __restrict__ wl, int64_t n, float alpha_t, float b1,
-                            float b2, float wd, float eps, float gscale, const float* __restrict__ alpha_dev) {
+                            float b2, float wd, float eps, float gscale, const float* __restrict__ alpha_dev,
+                            const float* __restrict__ gscale_dev) {
   if (alpha_dev) alpha_t = *alpha_dev;
+  if (gscale_dev) gscale *= *gscale_dev;
   const int64_t nv = n / 4;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += stride) {
@@ -143,17 +148,109 @@ static int opt_grid(int64_t n, int max_blocks) {
   return max_blocks > 0 ? std::min(g, max_blocks) : g;
 }
 void sgd_update(float* master, const float* grad, float* mom, void* param_lowp, int64_t n, float lr, float momentum,
-                int nesterov, float wd, float gscale, hipStream_t st, int max_blocks) {
+                int nesterov, float wd, float gscale, hipStream_t st, int max_blocks, const float* gscale_dev) {
   if (n == 0) return;
   hipLaunchKernelGGL(sgd_kernel, dim3(opt_grid(n, max_blocks)), dim3(256), 0, st, master, grad, mom,
-                     (bf16_t*)param_lowp, n, lr, momentum, nesterov, wd, gscale);
+                     (bf16_t*)param_lowp, n, lr, momentum, nesterov, wd, gscale, gscale_dev);
 }
 void adam_update(float* master, const float* grad, float* m, float* v, void* param_lowp, int64_t n, float alpha_t,
                  float beta1, float beta2, float wd, float eps, float gscale, hipStream_t st, int max_blocks,
-                 const float* alpha_dev) {
+                 const float* alpha_dev, const float* gscale_dev) {
   if (n == 0) return;
   hipLaunchKernelGGL(adam_kernel, dim3(opt_grid(n, max_blocks)), dim3(256), 0, st, master, grad, m, v,
-                     (bf16_t*)param_lowp, n, alpha_t, beta1, beta2, wd, eps, gscale, alpha_dev);
+                     (bf16_t*)param_lowp, n, alpha_t, beta1, beta2, wd, eps, gscale, alpha_dev, gscale_dev);
+}
+
+// ---------------------------------------------------------------- gradient clipping by global norm
+// grad_sumsq: sum of x[i]^2 over a contiguous, 16-byte aligned fp32 range into one device scalar,
+// with no float atomics: the result is a pure function of the values and n (same bits every run,
+// whatever the device or the launch order).
+//   nv = n / 4 float4 groups; G = clamp(ceil(nv / (256 * 8)), 1, 2048) workgroups of 256 threads
+//   (G = 0 when nv = 0), T = 256 * G threads, iters = ceil(nv / T).
+//   pass 1: thread t takes groups t + k * T (k < iters) into four float4 accumulators (k mod 4, one
+//     fma per element: the square is not rounded on its own), adds the four accumulators pairwise,
+//     their four components pairwise, then block_sum<256> (6 butterfly steps in the wave, 4 adds
+//     over the waves' LDS slots) -> partial[block].
+//   pass 2 (one workgroup): thread t adds partial[t + 256 * j] (j < pf = ceil(G / 256)) in order,
+//     block_sum<256> again; thread 0 then folds in the n % 4 tail elements and adds the result to
+//     *out (accumulate) or stores it.
+// Longest chain of fp32 additions any element passes through:
+//   d(n) = ceil(iters / 4) + 2 + 2 + 10 + pf + 10 + 3 + 1
+// (10 = 6 + 4 of one block_sum, 3 = tail, 1 = the accumulate into *out); d(2^22 + 3) = 32, and
+// d = 76 for the 335 M elements of BERT-Large. The relative error of the sum is at most about
+// d * 2^-24 (every term is non-negative, so there is no cancellation).
+constexpr int kSumsqMaxBlocks = 2048;
+static int sumsq_grid(int64_t n) {
+  const int64_t nv = n / 4;
+  if (nv == 0) return 0;
+  return (int)std::min<int64_t>((nv + 256 * 8 - 1) / (256 * 8), kSumsqMaxBlocks);
+}
+int grad_sumsq_partials() { return kSumsqMaxBlocks; }
+
+__global__ void __launch_bounds__(256) grad_sumsq_kernel(const float* __restrict__ x, int64_t nv, int64_t iters,
+                                                         float* __restrict__ partial) {
+  __shared__ float red[4];
+  const int64_t T = (int64_t)gridDim.x * 256;
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const float4* xv = reinterpret_cast<const float4*>(x);
+  float4 a[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) a[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int64_t k = 0; k < iters; k += 4) {
+    float4 v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {  // four 16-byte loads in flight per lane
+      const int64_t i = t + (k + u) * T;
+      v[u] = (k + u < iters && i < nv) ? xv[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      a[u].x = fmaf(v[u].x, v[u].x, a[u].x);
+      a[u].y = fmaf(v[u].y, v[u].y, a[u].y);
+      a[u].z = fmaf(v[u].z, v[u].z, a[u].z);
+      a[u].w = fmaf(v[u].w, v[u].w, a[u].w);
+    }
+  }
+  float4 s;
+  s.x = (a[0].x + a[1].x) + (a[2].x + a[3].x);
+  s.y = (a[0].y + a[1].y) + (a[2].y + a[3].y);
+  s.z = (a[0].z + a[1].z) + (a[2].z + a[3].z);
+  s.w = (a[0].w + a[1].w) + (a[2].w + a[3].w);
+  const float r = block_sum<256>((s.x + s.y) + (s.z + s.w), red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = r;
+}
+__global__ void __launch_bounds__(256) grad_sumsq_final_kernel(const float* __restrict__ partial, int npart,
+                                                               const float* __restrict__ x, int64_t n,
+                                                               float* __restrict__ out, int accumulate) {
+  __shared__ float red[4];
+  float s = 0.f;
+  for (int j = threadIdx.x; j < npart; j += 256) s += partial[j];
+  s = block_sum<256>(s, red);
+  if (threadIdx.x == 0) {
+    for (int64_t i = n / 4 * 4; i < n; ++i) s = fmaf(x[i], x[i], s);
+    *out = accumulate ? *out + s : s;
+  }
+}
+void grad_sumsq(const float* x, int64_t n, float* partial, float* out, int accumulate, hipStream_t st) {
+  const int g = sumsq_grid(n);
+  if (g > 0) {
+    const int64_t nv = n / 4, T = (int64_t)g * 256;
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(g), dim3(256), 0, st, x, nv, (nv + T - 1) / T, partial);
+  }
+  hipLaunchKernelGGL(grad_sumsq_final_kernel, dim3(1), dim3(256), 0, st, partial, g, x, n, out, accumulate);
+}
+
+// norm = sqrt(sumsq), coef = min(1, max_norm / (norm + eps)): torch's clip_grad_norm_ coefficient,
+// left on the device for the update kernels' gscale_dev (no host sync; a NaN norm gives a NaN coef)
+__global__ void clip_coef_kernel(const float* __restrict__ sumsq, float max_norm, float eps, float* __restrict__ norm,
+                                 float* __restrict__ coef) {
+  const float nr = sqrtf(*sumsq);
+  const float c = max_norm / (nr + eps);
+  *norm = nr;
+  *coef = c < 1.f ? c : (c >= 1.f ? 1.f : c);  // NaN stays NaN (fminf would drop it)
+}
+void clip_coef(const float* sumsq, float max_norm, float eps, float* norm, float* coef, hipStream_t st) {
+  hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(1), 0, st, sumsq, max_norm, eps, norm, coef);
 }
 
 }  // namespace ffk

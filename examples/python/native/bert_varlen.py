@@ -4,10 +4,12 @@ leaves the pad positions out as keys (`key_lengths`, read on the device: the ste
 into a graph). Synthetic data. By default the labels of pad positions still count in the loss;
 `--ignore-pad-labels` writes -100 there and compiles with `ignore_index=-100,
 loss_reduction="valid"`, so the pad rows leave loss, gradients and accuracy and the loss is the
-mean over the real tokens.
+mean over the real tokens. `--clip-grad-norm C` is FFConfig's flag: it goes through to the
+optimizer, which then clips the global gradient norm to C on the device.
 
     python examples/python/native/bert_varlen.py -b 8 --seq-length 64 --iterations 20
     python examples/python/native/bert_varlen.py -b 8 --seq-length 64 --iterations 20 --ignore-pad-labels
+    python examples/python/native/bert_varlen.py -b 8 --seq-length 64 --ignore-pad-labels --clip-grad-norm 1.0
 """
 import argparse
 import sys
@@ -63,6 +65,9 @@ def top_level_task(argv=None):
     if args.ignore_pad_labels:
         print("pad labels ignored: loss is the mean over %d real tokens, accuracy %.2f%%" %
               (pm.train_all, pm.get_accuracy()))
+    if ffmodel.optimizer.clip_norm:  # --clip-grad-norm, taken from the config by AdamOptimizer
+        print("gradient norm clipped to %g: the last step's norm before clipping was %.4f" %
+              (ffmodel.optimizer.clip_norm, ffmodel.get_grad_norm()))
     return pm
 
 

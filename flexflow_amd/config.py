@@ -88,6 +88,9 @@ class FFConfig:
         # 'overlapped update'; bitwise-identical, BERT-Large 47.56 -> 47.35 ms/step on one
         # MI355X); --overlap-update / --no-overlap-update, FF_OVERLAP_UPDATE=0|1
         self.overlap_update = os.environ.get("FF_OVERLAP_UPDATE", "1") != "0"
+        # --clip-grad-norm C: optimizers built with this model and no clip_norm of their own clip the
+        # global gradient norm to C (core/optimizers.py; 0 = off)
+        self.clip_grad_norm = 0.0
         self.seed = 1234
         self.cpu_only = False  # -ll:gpu 0 / --device cpu: run on the host even with a GPU present
         self.trace_dir = ""
@@ -240,6 +243,8 @@ class FFConfig:
                     self.grad_comm_dtype = nxt()
                     if self.grad_comm_dtype not in ("fp32", "bf16"):
                         raise ValueError(f"--grad-comm-dtype must be fp32 or bf16, not {self.grad_comm_dtype!r}")
+                elif a == "--clip-grad-norm":
+                    self.clip_grad_norm = float(nxt())
                 elif a == "--seed":
                     self.seed = int(nxt())
                 elif a == "--trace-dir":

@@ -592,6 +592,14 @@ class FFModel:
     def get_perf_metrics(self):
         return PerfMetrics(self.executor.metrics_snapshot(), self.metrics)
 
+    def get_grad_norm(self):
+        """The global L2 norm of the gradient the last update() saw, before clipping, as a Python
+        float; None when the optimizer does not clip (clip_norm / --clip-grad-norm). Reading it
+        syncs with the device — the clipping path itself never does."""
+        if self.executor is None or not getattr(self.optimizer, "clip_norm", None):
+            return None
+        return self.executor.grad_norm()
+
     def set_optimizer(self, optimizer):
         self.optimizer = optimizer
         if self.executor is not None:

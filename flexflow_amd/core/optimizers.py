@@ -14,11 +14,29 @@ import torch
 from .. import kernels as K
 
 
+def _resolve_clip_norm(ffmodel, clip_norm):
+    """clip_norm=None takes the model's --clip-grad-norm (0 = off); returns None when off."""
+    if clip_norm is None:
+        clip_norm = getattr(getattr(ffmodel, "config", None), "clip_grad_norm", 0.0)
+    c = float(clip_norm)
+    if not math.isfinite(c) or c < 0:
+        raise ValueError(f"clip_norm must be a finite value >= 0 (0 or None = off), got {clip_norm!r}")
+    return c or None
+
+
 class Optimizer:
-    def __init__(self, ffmodel=None, lr=0.01):
+    def __init__(self, ffmodel=None, lr=0.01, clip_norm=None):
         self.lr = lr
         self.ffmodel = ffmodel
         self.state = {}
+        # gradient clipping by global L2 norm (torch's clip_grad_norm_ over all trainable weights,
+        # world-wide): the executor leaves coef = min(1, clip_norm / (norm + 1e-6)) in
+        # clip_coef_dev before the step* calls of an update, which hand it to the kernels
+        self.clip_norm = _resolve_clip_norm(ffmodel, clip_norm)
+        self.clip_coef_dev = None
+
+    def _gscale_dev(self):
+        return self.clip_coef_dev if self.clip_norm else None
 
     def set_learning_rate(self, learning_rate):
         self.lr = learning_rate
@@ -39,8 +57,8 @@ class Optimizer:
 
 
 class SGDOptimizer(Optimizer):
-    def __init__(self, ffmodel=None, lr=0.01, momentum=0.0, nesterov=False, weight_decay=0.0):
-        super().__init__(ffmodel, lr)
+    def __init__(self, ffmodel=None, lr=0.01, momentum=0.0, nesterov=False, weight_decay=0.0, clip_norm=None):
+        super().__init__(ffmodel, lr, clip_norm)
         self.momentum = momentum
         self.nesterov = nesterov
         self.weight_decay = weight_decay
@@ -51,18 +69,19 @@ class SGDOptimizer(Optimizer):
 
     def step(self, arena):
         K.sgd_update(arena.master, arena.grad, self.state.get(id(arena)), arena.lowp, self.lr, self.momentum,
-                     self.nesterov, self.weight_decay)
+                     self.nesterov, self.weight_decay, gscale_dev=self._gscale_dev())
 
     def step_range(self, arena, lo, hi, max_blocks=0):
         mom = self.state.get(id(arena))
         K.sgd_update(arena.master[lo:hi], arena.grad[lo:hi], mom[lo:hi] if mom is not None else None,
                      arena.lowp[lo:hi] if arena.lowp is not None else None, self.lr, self.momentum, self.nesterov,
-                     self.weight_decay, max_blocks=max_blocks)
+                     self.weight_decay, max_blocks=max_blocks, gscale_dev=self._gscale_dev())
 
 
 class AdamOptimizer(Optimizer):
-    def __init__(self, ffmodel=None, alpha=0.001, beta1=0.9, beta2=0.999, weight_decay=0.0, epsilon=1e-8):
-        super().__init__(ffmodel, alpha)
+    def __init__(self, ffmodel=None, alpha=0.001, beta1=0.9, beta2=0.999, weight_decay=0.0, epsilon=1e-8,
+                 clip_norm=None):
+        super().__init__(ffmodel, alpha, clip_norm)
         self.alpha = alpha
         self.beta1, self.beta2 = beta1, beta2
         self.weight_decay = weight_decay
@@ -96,10 +115,11 @@ class AdamOptimizer(Optimizer):
     def step(self, arena):
         m, v = self.state[id(arena)]
         K.adam_update(arena.master, arena.grad, m, v, arena.lowp, self.alpha_t, self.beta1, self.beta2,
-                      self.weight_decay, self.epsilon, alpha_dev=self.alpha_dev)
+                      self.weight_decay, self.epsilon, alpha_dev=self.alpha_dev, gscale_dev=self._gscale_dev())
 
     def step_range(self, arena, lo, hi, max_blocks=0):
         m, v = self.state[id(arena)]
         K.adam_update(arena.master[lo:hi], arena.grad[lo:hi], m[lo:hi], v[lo:hi],
                       arena.lowp[lo:hi] if arena.lowp is not None else None, self.alpha_t, self.beta1, self.beta2,
-                      self.weight_decay, self.epsilon, max_blocks=max_blocks, alpha_dev=self.alpha_dev)
+                      self.weight_decay, self.epsilon, max_blocks=max_blocks, alpha_dev=self.alpha_dev,
+                      gscale_dev=self._gscale_dev())

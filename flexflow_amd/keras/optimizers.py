@@ -1,4 +1,8 @@
-"""Keras optimizers (reference keras/optimizers.py) -> fused HIP SGD / Adam of flexflow_amd.core."""
+"""Keras optimizers (reference keras/optimizers.py) -> fused HIP SGD / Adam of flexflow_amd.core.
+
+global_clipnorm=C clips the global gradient norm of all trainable weights to C (the core optimizers'
+clip_norm). Keras' clipnorm (per variable) and clipvalue (per element) are not implemented: they
+are accepted and ignored, like every other unknown keyword."""
 from __future__ import annotations
 
 from ..core.optimizers import AdamOptimizer, SGDOptimizer
@@ -17,23 +21,27 @@ class Optimizer:
 
 
 class SGD(Optimizer):
-    def __init__(self, learning_rate=0.01, momentum=0.0, nesterov=False, weight_decay=0.0, **kw):
+    def __init__(self, learning_rate=0.01, momentum=0.0, nesterov=False, weight_decay=0.0, global_clipnorm=None, **kw):
         self.learning_rate = float(kw.pop("lr", learning_rate))
         self.momentum, self.nesterov, self.weight_decay = float(momentum), bool(nesterov), float(weight_decay)
+        self.global_clipnorm = global_clipnorm
 
     def create_ffhandle(self, ffmodel):
-        self.ffhandle = SGDOptimizer(ffmodel, self.learning_rate, self.momentum, self.nesterov, self.weight_decay)
+        self.ffhandle = SGDOptimizer(ffmodel, self.learning_rate, self.momentum, self.nesterov, self.weight_decay,
+                                     clip_norm=self.global_clipnorm)
         return self.ffhandle
 
 
 class Adam(Optimizer):
-    def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-8, weight_decay=0.0, **kw):
+    def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-8, weight_decay=0.0,
+                 global_clipnorm=None, **kw):
         self.learning_rate = float(kw.pop("lr", learning_rate))
         self.beta_1, self.beta_2, self.epsilon, self.weight_decay = beta_1, beta_2, epsilon, weight_decay
+        self.global_clipnorm = global_clipnorm
 
     def create_ffhandle(self, ffmodel):
         self.ffhandle = AdamOptimizer(ffmodel, self.learning_rate, self.beta_1, self.beta_2, self.weight_decay,
-                                      self.epsilon)
+                                      self.epsilon, clip_norm=self.global_clipnorm)
         return self.ffhandle
 
 

@@ -1519,11 +1519,42 @@ def lstm_bwd_cell(G, ldg, c, c_prev, dy, lddy, dh_rec, dc, dG, B, H):
 
 
 # ----------------------------------------------------------------------------- optimizers
-def sgd_update(master, grad, mom, lowp, lr, momentum, nesterov, wd, gscale=1.0, max_blocks=0):
-    """max_blocks > 0 caps the launch grid (overlapped side-stream updates, Executor._on_bucket_ready)."""
-    if native(master):
-        ext().sgd_update(master, grad, mom, lowp, lr, momentum, nesterov, wd, gscale, max_blocks)
+GRAD_SUMSQ_PARTIALS = 2048  # fp32 workspace elements grad_sumsq needs (csrc: grad_sumsq_partials())
+
+
+def grad_sumsq(x, partials, out, accumulate=False):
+    """out (+)= sum of x**2 over a contiguous, 16-byte aligned fp32 range, in fp32, deterministic
+    (no atomics: the same input gives the same bits). out: fp32 [1]; partials: fp32
+    [GRAD_SUMSQ_PARTIALS] workspace the caller allocates once."""
+    if native(x):
+        ext().grad_sumsq(x, partials, out, bool(accumulate))
         return
+    s = (x.float() * x.float()).sum(dtype=torch.float32)
+    if accumulate:
+        out.add_(s)
+    else:
+        out.fill_(s)
+
+
+def clip_coef(sumsq, max_norm, norm, coef, eps=1e-6):
+    """norm = sqrt(sumsq), coef = min(1, max_norm / (norm + eps)) (torch's clip_grad_norm_), all
+    fp32 [1] on the device: the update kernels read coef through gscale_dev, with no host sync."""
+    if native(sumsq):
+        ext().clip_coef(sumsq, float(max_norm), norm, coef, float(eps))
+        return
+    norm.copy_(sumsq.sqrt())
+    coef.copy_(torch.clamp(max_norm / (norm + eps), max=1.0))
+
+
+def sgd_update(master, grad, mom, lowp, lr, momentum, nesterov, wd, gscale=1.0, max_blocks=0, gscale_dev=None):
+    """max_blocks > 0 caps the launch grid (overlapped side-stream updates, Executor._on_bucket_ready).
+    gscale_dev: optional one-element fp32 device tensor multiplied into gscale (the clipping
+    coefficient of clip_coef); the weight-decay term is not scaled."""
+    if native(master):
+        ext().sgd_update(master, grad, mom, lowp, lr, momentum, nesterov, wd, gscale, max_blocks, gscale_dev)
+        return
+    if gscale_dev is not None:
+        gscale = gscale * float(gscale_dev.item())
     g = grad * gscale + wd * master
     if momentum > 0:
         mom.mul_(momentum).add_(g)
@@ -1550,14 +1581,19 @@ def sgd_sparse_rows(idx, mark, master, grad, lowp, lr):
         lowp[rows] = master[rows].to(lowp.dtype)
 
 
-def adam_update(master, grad, m, v, lowp, alpha_t, b1, b2, wd, eps, gscale=1.0, max_blocks=0, alpha_dev=None):
+def adam_update(master, grad, m, v, lowp, alpha_t, b1, b2, wd, eps, gscale=1.0, max_blocks=0, alpha_dev=None,
+                gscale_dev=None):
     """alpha_dev: optional one-element fp32 device tensor the kernel reads the step size from (a
-    captured training step replays the launch while alpha_t changes every step)."""
+    captured training step replays the launch while alpha_t changes every step). gscale_dev: as in
+    sgd_update."""
     if native(master):
-        ext().adam_update(master, grad, m, v, lowp, alpha_t, b1, b2, wd, eps, gscale, max_blocks, alpha_dev)
+        ext().adam_update(master, grad, m, v, lowp, alpha_t, b1, b2, wd, eps, gscale, max_blocks, alpha_dev,
+                          gscale_dev)
         return
     if alpha_dev is not None:
         alpha_t = float(alpha_dev.item())
+    if gscale_dev is not None:
+        gscale = gscale * float(gscale_dev.item())
     g = grad * gscale + wd * master
     m.mul_(b1).add_((1 - b1) * g)
     v.mul_(b2).add_((1 - b2) * g * g)

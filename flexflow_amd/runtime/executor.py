@@ -648,7 +648,9 @@ class Executor:
         opt = self.model.optimizer
         from ..core.optimizers import Optimizer
         ranged = opt is not None and getattr(type(opt), "step_range", None) not in (None, Optimizer.step_range)
+        # clipping by global norm needs every gradient before any weight moves: no overlapped update
         return (self.training and ranged and not self.zero
+                and not getattr(opt, "clip_norm", None)
                 and not self._sparse_plan(opt)
                 and not self.hooks and self.device.type == "cuda"
                 and not torch.cuda.is_current_stream_capturing()
@@ -1089,13 +1091,15 @@ class Executor:
         regularizer. {arena group: [(entry index, layer name)]}. FF_SPARSE_EMB=0 disables."""
         # hyper-parameters are part of the key: setting momentum / weight decay on the same
         # optimizer object after the first update must switch the tables back to the dense step
+        # (clip_norm too: the row-sparse kernel has no gradient scale, a clipped step runs dense)
         key = (id(optimizer), getattr(optimizer, "momentum", None), getattr(optimizer, "weight_decay", None),
-               getattr(optimizer, "nesterov", None))
+               getattr(optimizer, "nesterov", None), getattr(optimizer, "clip_norm", None))
         if self._sparse_key == key:
             return self._sparse
         plan = {}
         from ..core.optimizers import SGDOptimizer
         if (isinstance(optimizer, SGDOptimizer) and not optimizer.momentum and not optimizer.weight_decay
+                and not getattr(optimizer, "clip_norm", None)
                 and os.environ.get("FF_SPARSE_EMB", "1") != "0" and not self.zero):
             for L in self.layers:
                 if L.op_type != OperatorType.OP_EMBEDDING or L.name not in self.ctx or not self.layer_bwd.get(L.name):
@@ -1136,6 +1140,8 @@ class Executor:
             self.wait_all_gathers()
         self.bucketer.flush()
         self._apply_regularizers()
+        if getattr(optimizer, "clip_norm", None):
+            self._clip_coefficient(optimizer)
         if self._opt_next_done is not optimizer:
             optimizer.next()
         self._master_stale = False
@@ -1250,6 +1256,53 @@ class Executor:
     def init_optimizer(self, optimizer):
         for ar in self.arenas.values():
             optimizer.init_state(ar)
+        if getattr(optimizer, "clip_norm", None):
+            self._clip_setup(optimizer)
+
+    def _clip_setup(self, optimizer):
+        """Gradient clipping's device scalars [sum of squares, norm, coefficient] and grad_sumsq's
+        workspace: allocated once (init_optimizer), outside any step or capture."""
+        if getattr(self, "_clip", None) is None:
+            self._clip = torch.tensor([0.0, 0.0, 1.0], dtype=torch.float32, device=self.device)
+            self._clip_ws = torch.empty(K.GRAD_SUMSQ_PARTIALS, dtype=torch.float32, device=self.device)
+        optimizer.clip_coef_dev = self._clip[2:3]
+
+    def _clip_coefficient(self, optimizer):
+        """Global gradient norm and clipping coefficient of this update, left on the device for the
+        step* launches (Optimizer.clip_coef_dev): one grad_sumsq pass per distinct gradient shard,
+        one scalar all-reduce over the world, clip_coef. No host sync, so a captured update replays
+        it. Each shard counts once: a replicated (all-reduced) arena on the lowest rank of its
+        group, a ZeRO arena by every rank's own chunk of every bucket (the reduce-scattered part),
+        a rank-private arena whole. Whole ranges are summed, padding included: the padding between
+        arena entries (WeightArena.add, and the ZeRO round-up) is allocated zero and written by no
+        kernel — every gradient kernel and the regularizers write through the entries' views — so
+        it adds exact zeros (tests/test_grad_clip_gpu.py checks it on odd-sized weights)."""
+        if getattr(self, "_clip", None) is None or optimizer.clip_coef_dev is None:
+            self._clip_setup(optimizer)  # clip_norm set after init_optimizer
+        sumsq, norm, coef = self._clip[0:1], self._clip[1:2], optimizer.clip_coef_dev
+        sumsq.zero_()
+        for grp, ar in self.arenas.items():
+            if not ar.size:
+                continue
+            bs = self.zero_buckets.get(grp)
+            if bs is not None:
+                for b in bs:
+                    lo, hi = b["own"]
+                    if hi > lo:
+                        K.grad_sumsq(ar.grad[lo:hi], self._clip_ws, sumsq, accumulate=True)
+            elif len(grp) <= 1 or self.rank == min(grp):
+                K.grad_sumsq(ar.grad[:ar.size], self._clip_ws, sumsq, accumulate=True)
+        if self.comm.distributed and self.comm.world > 1:
+            # every rank takes part, on the compute stream, ahead of the kernel that reads the sum
+            dist.all_reduce(sumsq, group=dist.group.WORLD)
+        K.clip_coef(sumsq, optimizer.clip_norm, norm, coef)
+
+    def grad_norm(self) -> Optional[float]:
+        """The pre-clip global gradient norm of the last update (None without clipping). Reads the
+        device scalar: the one host sync of the clipping path."""
+        if getattr(self, "_clip", None) is None:
+            return None
+        return float(self._clip[1].item())
 
     # ------------------------------------------------------------------ value access
     def gather_full(self, t, local: Optional[torch.Tensor], layout: Layout,

@@ -93,7 +93,9 @@ class StepGraph:
     def _full_step(self, m, ex) -> bool:
         """Capture the optimizer update too (its overlapped per-bucket launches on the side stream
         included): one process, Adam (its launches read the per-step alpha_t from a device scalar
-        that next() refreshes before each replay). Other optimizers and multi-rank steps keep
+        that next() refreshes before each replay; with clip_norm the captured update also holds the
+        gradient's sum of squares, the coefficient kernel and the Adam launches that read it, all
+        on the device). Other optimizers and multi-rank steps keep
         update() eager after the replay. Opt-in (FF_GRAPH_UPDATE=1): same-box A/B AlexNet 1.665-1.671
         vs 1.670-1.682 ms, ResNet-50 7.58-7.60 vs 7.60 ms (profiles/graph_update_ab_r5.txt) — the
         eager update after the replay was not exposed enough for the overlap to pay."""
