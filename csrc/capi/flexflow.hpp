@@ -429,6 +429,18 @@ class AdamOptimizer : public Optimizer {
                   "AdamOptimizer") {}
 };
 
+// LAMB: Adam moments, decoupled weight decay, one trust ratio per weight; exclude_1d leaves biases
+// and LayerNorm vectors out of the decay and the ratio
+class LAMBOptimizer : public Optimizer {
+ public:
+  explicit LAMBOptimizer(const FFModel& m, double lr = 0.001, double beta1 = 0.9, double beta2 = 0.999,
+                         double weight_decay = 0.01, double epsilon = 1e-6, bool bias_correction = true,
+                         bool exclude_1d = true)
+      : Optimizer(flexflow_lamb_optimizer_create(m.raw(), lr, beta1, beta2, weight_decay, epsilon, bias_correction,
+                                                 exclude_1d),
+                  "LAMBOptimizer") {}
+};
+
 // wall-clock microseconds (reference Realm::Clock::current_time_in_microseconds)
 inline double current_time_in_microseconds() {
   using namespace std::chrono;

@@ -518,6 +518,9 @@ void flexflow_model_set_sgd_optimizer(flexflow_model_t h, flexflow_sgd_optimizer
 void flexflow_model_set_adam_optimizer(flexflow_model_t h, flexflow_adam_optimizer_t o) {
   FF_VOID("model_set_opt", "(OO)", obj(h.impl), obj(o.impl));
 }
+void flexflow_model_set_lamb_optimizer(flexflow_model_t h, flexflow_lamb_optimizer_t o) {
+  FF_VOID("model_set_opt", "(OO)", obj(h.impl), obj(o.impl));
+}
 void flexflow_model_set_optimizer(flexflow_model_t h, flexflow_optimizer_t o) {
   FF_VOID("model_set_opt", "(OO)", obj(h.impl), obj(o.impl));
 }
@@ -682,6 +685,15 @@ flexflow_adam_optimizer_t flexflow_adam_optimizer_create(flexflow_model_t m, dou
 }
 void flexflow_adam_optimizer_destroy(flexflow_adam_optimizer_t h) { drop(h.impl); }
 void flexflow_adam_optimizer_set_lr(flexflow_adam_optimizer_t h, double lr) {
+  FF_VOID("optimizer_set_lr", "(Od)", obj(h.impl), lr);
+}
+flexflow_lamb_optimizer_t flexflow_lamb_optimizer_create(flexflow_model_t m, double lr, double b1, double b2, double wd,
+                                                         double eps, bool bias_correction, bool exclude_1d) {
+  FF_HANDLE(flexflow_lamb_optimizer_t, "lamb_create", "(Odddddii)", obj(m.impl), lr, b1, b2, wd, eps,
+            (int)bias_correction, (int)exclude_1d);
+}
+void flexflow_lamb_optimizer_destroy(flexflow_lamb_optimizer_t h) { drop(h.impl); }
+void flexflow_lamb_optimizer_set_lr(flexflow_lamb_optimizer_t h, double lr) {
   FF_VOID("optimizer_set_lr", "(Od)", obj(h.impl), lr);
 }
 

@@ -488,6 +488,77 @@ void clip_coef(Tensor sumsq, double max_norm, Tensor norm, Tensor coef, double e
   ffk::clip_coef(dev_scalar(sumsq, sumsq, "clip_coef: sumsq"), max_norm, eps, norm.data_ptr<float>(),
                  coef.data_ptr<float>(), cur_stream());
 }
+// LAMB: the chunk table (int64 [n_chunks, 2]) and the weight table (int32 [n_weights, 4]) are built and
+// checked on the host by kernels.lamb_table; the kernels skip any chunk that leaves [0, n)
+struct LambArgs {
+  int n_chunks, n_weights;
+};
+LambArgs lamb_check(const char* fn, const Tensor& like, const Tensor& chunks, const Tensor& wtab, const Tensor& hyper) {
+  check_dev(like, fn);
+  TORCH_CHECK(chunks.scalar_type() == at::kLong && chunks.dim() == 2 && chunks.size(1) == 2, fn,
+              ": chunks must be int64 [n_chunks, 2]");
+  TORCH_CHECK(wtab.scalar_type() == at::kInt && wtab.dim() == 2 && wtab.size(1) == 4, fn,
+              ": wtab must be int32 [n_weights, 4]");
+  TORCH_CHECK(hyper.scalar_type() == at::kFloat && hyper.numel() >= 3, fn, ": hyper must hold 3 fp32");
+  for (const Tensor* t : {&chunks, &wtab, &hyper}) {
+    TORCH_CHECK(t->is_cuda() && t->device() == like.device(), fn, ": tables and hyper must be on the arena's device");
+    check_contig(*t, fn);
+  }
+  check_aligned(chunks, 16, fn); check_aligned(wtab, 16, fn);
+  TORCH_CHECK(chunks.size(0) < (1 << 30) && wtab.size(0) < (1 << 30), fn, ": table too large");
+  return {(int)chunks.size(0), (int)wtab.size(0)};
+}
+void lamb_f32(const char* fn, const Tensor& t, const Tensor& like, int64_t min_numel, bool aligned) {
+  TORCH_CHECK(t.scalar_type() == at::kFloat, fn, ": fp32 expected");
+  TORCH_CHECK(t.is_cuda() && t.device() == like.device(), fn, ": tensor on another device");
+  TORCH_CHECK(t.numel() >= min_numel, fn, ": tensor holds ", t.numel(), " elements, needs ", min_numel);
+  check_contig(t, fn);
+  if (aligned) check_aligned(t, 16, fn);
+}
+void lamb_moments(Tensor master, Tensor grad, Tensor m, Tensor v, Tensor chunks, Tensor wtab, Tensor hyper,
+                  optional<Tensor> gscale_dev, double b1, double b2, double eps, Tensor partials) {
+  const char* fn = "lamb_moments";
+  const LambArgs a = lamb_check(fn, master, chunks, wtab, hyper);
+  const int64_t n = master.numel();
+  lamb_f32(fn, master, master, n, true); lamb_f32(fn, grad, master, n, true);
+  lamb_f32(fn, m, master, n, true); lamb_f32(fn, v, master, n, true);
+  TORCH_CHECK(grad.numel() == n && m.numel() == n && v.numel() == n, fn, ": master, grad, m, v differ in size");
+  lamb_f32(fn, partials, master, 2 * (int64_t)a.n_chunks, false);
+  const float* gsd = dev_scalar(gscale_dev, master, "lamb_moments: gscale_dev");
+  ffk::lamb_moments(master.data_ptr<float>(), grad.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), n,
+                    chunks.data_ptr(), a.n_chunks, wtab.data_ptr(), a.n_weights, hyper.data_ptr<float>(), gsd, b1, b2,
+                    (float)eps, partials.data_ptr<float>(), cur_stream());
+}
+void lamb_norms(Tensor partials, int64_t n_chunks, Tensor wtab, bool count, Tensor norms) {
+  const char* fn = "lamb_norms";
+  check_dev(partials, fn);
+  TORCH_CHECK(wtab.scalar_type() == at::kInt && wtab.dim() == 2 && wtab.size(1) == 4 && wtab.is_cuda() &&
+              wtab.device() == partials.device(), fn, ": wtab must be int32 [n_weights, 4] on the device");
+  check_contig(wtab, fn); check_aligned(wtab, 16, fn);
+  TORCH_CHECK(n_chunks >= 0 && n_chunks < (1 << 30) && wtab.size(0) < (1 << 30), fn, ": table too large");
+  lamb_f32(fn, partials, partials, 2 * n_chunks, false);
+  lamb_f32(fn, norms, partials, 2 * wtab.size(0), false);
+  ffk::lamb_norms(partials.data_ptr<float>(), (int)n_chunks, wtab.data_ptr(), (int)wtab.size(0), count ? 1 : 0,
+                  norms.data_ptr<float>(), cur_stream());
+}
+void lamb_apply(Tensor master, Tensor m, Tensor v, optional<Tensor> lowp, Tensor chunks, Tensor wtab, Tensor hyper,
+                double eps, Tensor norms) {
+  const char* fn = "lamb_apply";
+  const LambArgs a = lamb_check(fn, master, chunks, wtab, hyper);
+  const int64_t n = master.numel();
+  lamb_f32(fn, master, master, n, true); lamb_f32(fn, m, master, n, true); lamb_f32(fn, v, master, n, true);
+  TORCH_CHECK(m.numel() == n && v.numel() == n, fn, ": master, m, v differ in size");
+  lamb_f32(fn, norms, master, 2 * (int64_t)a.n_weights, false);
+  if (lowp.has_value() && lowp->defined()) {
+    TORCH_CHECK(lowp->scalar_type() == at::kBFloat16 && lowp->numel() == n && lowp->is_cuda() &&
+                lowp->device() == master.device(), fn, ": lowp must be bf16 of master's size");
+    check_contig(*lowp, "lamb_apply: lowp");
+    check_aligned(*lowp, 8, "lamb_apply: lowp");
+  }
+  ffk::lamb_apply(master.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), ptr(lowp), n, chunks.data_ptr(),
+                  a.n_chunks, wtab.data_ptr(), a.n_weights, hyper.data_ptr<float>(), (float)eps,
+                  norms.data_ptr<float>(), cur_stream());
+}
 void embedding_fwd(Tensor idx, Tensor table, Tensor out, int64_t n_rows, int64_t bag, int64_t dim, bool avg) {
   TORCH_CHECK(idx.numel() == n_rows * bag && out.numel() == n_rows * dim && table.size(-1) == dim);
   check_contig(idx, "embedding_fwd: idx"); check_contig(table, "embedding_fwd: table");
@@ -1084,6 +1155,14 @@ PYBIND11_MODULE(_C, m) {
   m.def("grad_sumsq_partials", []() { return ffk::grad_sumsq_partials(); });
   m.def("clip_coef", &clip_coef, py::arg("sumsq"), py::arg("max_norm"), py::arg("norm"), py::arg("coef"),
         py::arg("eps") = 1e-6);
+  m.def("lamb_chunk", []() { return ffk::lamb_chunk(); });
+  m.def("lamb_moments", &lamb_moments, py::arg("master"), py::arg("grad"), py::arg("m"), py::arg("v"), py::arg("chunks"),
+        py::arg("wtab"), py::arg("hyper"), py::arg("gscale_dev"), py::arg("b1"), py::arg("b2"), py::arg("eps"),
+        py::arg("partials"));
+  m.def("lamb_norms", &lamb_norms, py::arg("partials"), py::arg("n_chunks"), py::arg("wtab"), py::arg("count"),
+        py::arg("norms"));
+  m.def("lamb_apply", &lamb_apply, py::arg("master"), py::arg("m"), py::arg("v"), py::arg("lowp"), py::arg("chunks"),
+        py::arg("wtab"), py::arg("hyper"), py::arg("eps"), py::arg("norms"));
   m.def("embedding_fwd", &embedding_fwd);
   m.def("embedding_bwd", &embedding_bwd);
   m.def("init_uniform", &init_uniform);

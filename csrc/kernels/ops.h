@@ -138,6 +138,19 @@ void adam_update(float* master, const float* grad, float* m, float* v, void* par
 int grad_sumsq_partials();
 void grad_sumsq(const float* x, int64_t n, float* partial, float* out, int accumulate, hipStream_t st);
 void clip_coef(const float* sumsq, float max_norm, float eps, float* norm, float* coef, hipStream_t st);
+// LAMB over one arena of n fp32 elements, driven by a chunk table on the device (chunks: n_chunks x
+// {int64 start, int32 len, int32 weight}; wtab: n_weights x {float lambda, int32 flags, int32 first,
+// int32 count}; see optimizer.hip). hyper: {lr, 1/(1-beta1^t), 1/(1-beta2^t)} on the device;
+// partial: 2 * n_chunks floats; norms: 2 * n_weights floats (sum w^2, sum u^2 per weight)
+int lamb_chunk();
+void lamb_moments(const float* master, const float* grad, float* m, float* v, int64_t n, const void* chunks,
+                  int n_chunks, const void* wtab, int n_weights, const float* hyper, const float* gscale_dev,
+                  double beta1, double beta2, float eps, float* partial, hipStream_t st);
+void lamb_norms(const float* partial, int n_chunks, const void* wtab, int n_weights, int count, float* norms,
+                hipStream_t st);
+void lamb_apply(float* master, const float* m, const float* v, void* param_lowp, int64_t n, const void* chunks,
+                int n_chunks, const void* wtab, int n_weights, const float* hyper, float eps, const float* norms,
+                hipStream_t st);
 
 // embedding.hip
 void embedding_fwd(int dt, int idx64, const void* idx, const void* table, void* out, int64_t n_out_rows, int bag,

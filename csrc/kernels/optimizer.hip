@@ -253,4 +253,200 @@ void clip_coef(const float* sumsq, float max_norm, float eps, float* norm, float
   hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(1), 0, st, sumsq, max_norm, eps, norm, coef);
 }
 
+// -------------------------------------------------------------------------------------------- LAMB
+// (You et al., "Large Batch Optimization for Deep Learning", ICLR 2020.) Adam moments, decoupled
+// weight decay and one trust ratio per logical weight:
+//   g' = c g;  m = b1 m + (1-b1) g';  v = b2 v + (1-b2) g'^2;  u = m rc1 / (sqrt(v rc2) + eps) + lam_p w
+//   r_p = |w_p| / |u_p| (1 when the weight is excluded or either norm is not > 0);  w -= lr r_p u
+// The norms run over whole weights, which a flat range [lo, hi) cannot express, so the launches
+// are driven by a chunk table the host builds once (kernels.lamb_table): every piece (an arena
+// entry cut by an update range) is split into chunks of at most kLambChunk elements with a 16-byte
+// aligned start; the padding between entries belongs to no chunk and is never touched.
+//   lamb_moments (one workgroup per chunk): m, v updated, u formed, sum w^2 and sum u^2 -> partials
+//   lamb_norms   (one workgroup per weight): the weight's chunk partials, in index order -> norms
+//   (the caller all-reduces norms over the world)
+//   lamb_apply   (one workgroup per chunk): r_p from norms, u recomputed from the stored m, v, w by
+//     the same lamb_u as stage 1 (no arena-sized u buffer), w and its bf16 copy written
+// No float atomics anywhere: the same input gives the same bits. hyper = {lr, rc1, rc2} on the
+// device (rc = 1 / (1 - beta^t), or 1 without bias correction), gscale_dev = the clipping
+// coefficient or null.
+// Longest chain of fp32 additions an element's square passes through, for a weight of cc chunks:
+//   lamb_moments: thread t takes float4 groups t + 256 k (k < kLambChunk / 1024 = 8) into one float4
+//     accumulator (one fma per element): 8; its components pairwise: 2; one of the <= 3 tail
+//     elements of the chunk: 1; block_sum<256>: 6 + 4 = 10
+//   lamb_norms: thread t adds partial[first + t + 256 j] (j < ceil(cc / 256)) in order, then
+//     block_sum<256>: 10
+//   d(cc) = 8 + 2 + 1 + 10 + ceil(cc / 256) + 10 = 31 + ceil(cc / 256)
+// (d = 32 up to 2 M elements; the 31 M-element embedding table of BERT-Large: cc = 3816, d = 46.)
+// Every term is non-negative, so the relative error of a sum is at most about d * 2^-24.
+constexpr int kLambChunk = 8192;
+int lamb_chunk() { return kLambChunk; }
+
+struct LambChunk {  // 16 bytes, as kernels.lamb_table packs them
+  int64_t start;    // first element, a multiple of 4
+  int len;          // 1 .. kLambChunk
+  int weight;       // row of the weight table
+};
+struct LambWeight {  // 16 bytes
+  float lambda;      // decoupled weight decay of this weight (0 when excluded)
+  int flags;         // bit 0: adapt (trust ratio applies); bit 1: this table owns the row
+  int first, count;  // the weight's chunks are [first, first + count) of this table
+};
+
+__device__ __forceinline__ float lamb_u(float m, float v, float w, float rc1, float rc2, float eps, float lambda) {
+  return fmaf(lambda, w, (m * rc1) / (sqrtf(v * rc2) + eps));
+}
+
+// a chunk the table's builder would not have produced is skipped, never followed out of bounds
+__device__ __forceinline__ bool lamb_chunk_ok(const LambChunk& c, int64_t n, int n_weights) {
+  return c.start >= 0 && (c.start & 3) == 0 && c.len > 0 && c.len <= kLambChunk && c.start + c.len <= n &&
+         c.weight >= 0 && c.weight < n_weights;
+}
+
+__global__ void __launch_bounds__(256)
+lamb_moments_kernel(const float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m,
+                    float* __restrict__ v, int64_t n, const LambChunk* __restrict__ chunks,
+                    const LambWeight* __restrict__ wtab, int n_weights, const float* __restrict__ hyper,
+                    const float* __restrict__ gscale_dev, float b1, float c1, float b2, float c2, float eps,
+                    float* __restrict__ partial) {
+  __shared__ float red_w[4], red_u[4];
+  const LambChunk c = chunks[blockIdx.x];
+  const bool ok = lamb_chunk_ok(c, n, n_weights);  // uniform over the workgroup
+  float4 aw = make_float4(0.f, 0.f, 0.f, 0.f), au = aw;
+  float sw = 0.f, su = 0.f;
+  if (ok) {
+    const float gs = gscale_dev ? *gscale_dev : 1.f;
+    const float rc1 = hyper[1], rc2 = hyper[2];
+    const float lambda = wtab[c.weight].lambda;
+    const int nv = c.len >> 2;
+    const float4* wv4 = reinterpret_cast<const float4*>(w + c.start);
+    const float4* gv4 = reinterpret_cast<const float4*>(g + c.start);
+    float4* mv4 = reinterpret_cast<float4*>(m + c.start);
+    float4* vv4 = reinterpret_cast<float4*>(v + c.start);
+#pragma unroll 2
+    for (int i = threadIdx.x; i < nv; i += 256) {
+      const float4 wv = wv4[i];
+      const float4 gv = gv4[i];
+      float4 mv = mv4[i];
+      float4 vv = vv4[i];
+      const float* wp = &wv.x; const float* gp = &gv.x;
+      float* mp = &mv.x; float* vp = &vv.x; float* awp = &aw.x; float* aup = &au.x;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float gt = gp[j] * gs;
+        mp[j] = fmaf(b1, mp[j], c1 * gt);
+        vp[j] = fmaf(b2, vp[j], c2 * gt * gt);
+        const float u = lamb_u(mp[j], vp[j], wp[j], rc1, rc2, eps, lambda);
+        awp[j] = fmaf(wp[j], wp[j], awp[j]);
+        aup[j] = fmaf(u, u, aup[j]);
+      }
+      mv4[i] = mv;
+      vv4[i] = vv;
+    }
+    sw = (aw.x + aw.y) + (aw.z + aw.w);
+    su = (au.x + au.y) + (au.z + au.w);
+    const int64_t t = c.start + (nv << 2) + threadIdx.x;  // the chunk's len % 4 tail elements
+    if ((int)threadIdx.x < (c.len & 3)) {
+      const float gt = g[t] * gs;
+      const float mt = fmaf(b1, m[t], c1 * gt);
+      const float vt = fmaf(b2, v[t], c2 * gt * gt);
+      const float wt = w[t];
+      const float u = lamb_u(mt, vt, wt, rc1, rc2, eps, lambda);
+      m[t] = mt;
+      v[t] = vt;
+      sw = fmaf(wt, wt, sw);
+      su = fmaf(u, u, su);
+    }
+  }
+  sw = block_sum<256>(sw, red_w);
+  su = block_sum<256>(su, red_u);
+  if (threadIdx.x == 0) {
+    partial[2 * (int64_t)blockIdx.x] = sw;
+    partial[2 * (int64_t)blockIdx.x + 1] = su;
+  }
+}
+
+// count = 0: this rank must not count the arena (a replica another rank counts): zeros
+__global__ void __launch_bounds__(256)
+lamb_norms_kernel(const float* __restrict__ partial, int n_chunks, const LambWeight* __restrict__ wtab, int count,
+                  float* __restrict__ norms) {
+  __shared__ float red_w[4], red_u[4];
+  const LambWeight e = wtab[blockIdx.x];
+  if (!(e.flags & 2)) return;  // another arena's weight (uniform over the workgroup)
+  float sw = 0.f, su = 0.f;
+  if (count && e.first >= 0 && e.count > 0 && e.first <= n_chunks - e.count) {
+    for (int j = threadIdx.x; j < e.count; j += 256) {
+      sw += partial[2 * (int64_t)(e.first + j)];
+      su += partial[2 * (int64_t)(e.first + j) + 1];
+    }
+  }
+  sw = block_sum<256>(sw, red_w);
+  su = block_sum<256>(su, red_u);
+  if (threadIdx.x == 0) {
+    norms[2 * blockIdx.x] = sw;
+    norms[2 * blockIdx.x + 1] = su;
+  }
+}
+
+__global__ void __launch_bounds__(256)
+lamb_apply_kernel(float* __restrict__ w, const float* __restrict__ m, const float* __restrict__ v,
+                  bf16_t* __restrict__ wl, int64_t n, const LambChunk* __restrict__ chunks,
+                  const LambWeight* __restrict__ wtab, int n_weights, const float* __restrict__ hyper, float eps,
+                  const float* __restrict__ norms) {
+  const LambChunk c = chunks[blockIdx.x];
+  if (!lamb_chunk_ok(c, n, n_weights)) return;
+  const LambWeight e = wtab[c.weight];
+  const float rc1 = hyper[1], rc2 = hyper[2];
+  const float wn = sqrtf(norms[2 * c.weight]), un = sqrtf(norms[2 * c.weight + 1]);
+  const float step = hyper[0] * (((e.flags & 1) && wn > 0.f && un > 0.f) ? wn / un : 1.f);
+  const int nv = c.len >> 2;
+  float4* wv4 = reinterpret_cast<float4*>(w + c.start);
+  const float4* mv4 = reinterpret_cast<const float4*>(m + c.start);
+  const float4* vv4 = reinterpret_cast<const float4*>(v + c.start);
+#pragma unroll 2
+  for (int i = threadIdx.x; i < nv; i += 256) {
+    float4 wv = wv4[i];
+    const float4 mv = mv4[i];
+    const float4 vv = vv4[i];
+    float* wp = &wv.x; const float* mp = &mv.x; const float* vp = &vv.x;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) wp[j] -= step * lamb_u(mp[j], vp[j], wp[j], rc1, rc2, eps, e.lambda);
+    wv4[i] = wv;
+    if (wl) {
+      ushort4 o;
+      o.x = f2bf(wp[0]); o.y = f2bf(wp[1]); o.z = f2bf(wp[2]); o.w = f2bf(wp[3]);
+      reinterpret_cast<ushort4*>(wl + c.start)[i] = o;
+    }
+  }
+  const int64_t t = c.start + (nv << 2) + threadIdx.x;
+  if ((int)threadIdx.x < (c.len & 3)) {
+    const float wt = w[t] - step * lamb_u(m[t], v[t], w[t], rc1, rc2, eps, e.lambda);
+    w[t] = wt;
+    if (wl) wl[t] = f2bf(wt);
+  }
+}
+
+void lamb_moments(const float* master, const float* grad, float* m, float* v, int64_t n, const void* chunks,
+                  int n_chunks, const void* wtab, int n_weights, const float* hyper, const float* gscale_dev,
+                  double beta1, double beta2, float eps, float* partial, hipStream_t st) {
+  if (n_chunks <= 0) return;
+  // 1 - beta rounded once from double (1.f - 0.999f is 4.7e-5 off 0.001)
+  hipLaunchKernelGGL(lamb_moments_kernel, dim3(n_chunks), dim3(256), 0, st, master, grad, m, v, n,
+                     (const LambChunk*)chunks, (const LambWeight*)wtab, n_weights, hyper, gscale_dev, (float)beta1,
+                     (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), eps, partial);
+}
+void lamb_norms(const float* partial, int n_chunks, const void* wtab, int n_weights, int count, float* norms,
+                hipStream_t st) {
+  if (n_weights <= 0) return;
+  hipLaunchKernelGGL(lamb_norms_kernel, dim3(n_weights), dim3(256), 0, st, partial, n_chunks,
+                     (const LambWeight*)wtab, count, norms);
+}
+void lamb_apply(float* master, const float* m, const float* v, void* param_lowp, int64_t n, const void* chunks,
+                int n_chunks, const void* wtab, int n_weights, const float* hyper, float eps, const float* norms,
+                hipStream_t st) {
+  if (n_chunks <= 0) return;
+  hipLaunchKernelGGL(lamb_apply_kernel, dim3(n_chunks), dim3(256), 0, st, master, m, v, (bf16_t*)param_lowp, n,
+                     (const LambChunk*)chunks, (const LambWeight*)wtab, n_weights, hyper, eps, norms);
+}
+
 }  // namespace ffk

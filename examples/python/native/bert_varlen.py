@@ -5,11 +5,13 @@ into a graph). Synthetic data. By default the labels of pad positions still coun
 `--ignore-pad-labels` writes -100 there and compiles with `ignore_index=-100,
 loss_reduction="valid"`, so the pad rows leave loss, gradients and accuracy and the loss is the
 mean over the real tokens. `--clip-grad-norm C` is FFConfig's flag: it goes through to the
-optimizer, which then clips the global gradient norm to C on the device.
+optimizer, which then clips the global gradient norm to C on the device. `--optimizer lamb` trains
+with LAMB (decoupled weight decay, one trust ratio per weight) in place of Adam.
 
     python examples/python/native/bert_varlen.py -b 8 --seq-length 64 --iterations 20
     python examples/python/native/bert_varlen.py -b 8 --seq-length 64 --iterations 20 --ignore-pad-labels
     python examples/python/native/bert_varlen.py -b 8 --seq-length 64 --ignore-pad-labels --clip-grad-norm 1.0
+    python examples/python/native/bert_varlen.py -b 8 --seq-length 64 --ignore-pad-labels --optimizer lamb
 """
 import argparse
 import sys
@@ -27,6 +29,7 @@ def top_level_task(argv=None):
     ap.add_argument("--iterations", type=int, default=20)
     ap.add_argument("--min-length", type=int, default=8)
     ap.add_argument("--ignore-pad-labels", action="store_true")
+    ap.add_argument("--optimizer", choices=["adam", "lamb"], default="adam")
     args, rest = ap.parse_known_args(sys.argv[1:] if argv is None else argv)
     ffconfig = FFConfig(rest)
     ffmodel = FFModel(ffconfig)
@@ -34,7 +37,7 @@ def top_level_task(argv=None):
     bc = BertConfig.tiny(s)
     lengths = ffmodel.create_tensor([b], DataType.DT_INT32, name="key_lengths")
     ids, pos, _ = build_bert(ffmodel, b, bc, key_lengths=lengths)
-    ffmodel.optimizer = AdamOptimizer(ffmodel, 1e-3)
+    ffmodel.optimizer = LAMBOptimizer(ffmodel, 1e-3) if args.optimizer == "lamb" else AdamOptimizer(ffmodel, 1e-3)
     masking = dict(ignore_index=-100, loss_reduction="valid") if args.ignore_pad_labels else {}
     ffmodel.compile(loss_type=LossType.LOSS_SPARSE_CATEGORICAL_CROSSENTROPY, metrics=[MetricsType.METRICS_ACCURACY],
                     **masking)
@@ -65,7 +68,7 @@ def top_level_task(argv=None):
     if args.ignore_pad_labels:
         print("pad labels ignored: loss is the mean over %d real tokens, accuracy %.2f%%" %
               (pm.train_all, pm.get_accuracy()))
-    if ffmodel.optimizer.clip_norm:  # --clip-grad-norm, taken from the config by AdamOptimizer
+    if ffmodel.optimizer.clip_norm:  # --clip-grad-norm, taken from the config by the optimizer
         print("gradient norm clipped to %g: the last step's norm before clipping was %.4f" %
               (ffmodel.optimizer.clip_norm, ffmodel.get_grad_norm()))
     return pm

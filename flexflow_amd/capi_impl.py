@@ -12,7 +12,7 @@ import ctypes
 import numpy as np
 
 from .config import FFConfig
-from .core import AdamOptimizer, FFModel, SGDOptimizer
+from .core import AdamOptimizer, FFModel, LAMBOptimizer, SGDOptimizer
 from .type import ActiMode, AggrMode, CompMode, DataType, LossType, MetricsType, PoolType
 
 
@@ -56,6 +56,10 @@ def sgd_create(m, lr, momentum, nesterov, wd):
 
 def adam_create(m, alpha, b1, b2, wd, eps):
     return AdamOptimizer(m, alpha, b1, b2, wd, eps)
+
+
+def lamb_create(m, lr, b1, b2, wd, eps, bias_correction=True, exclude_1d=True):
+    return LAMBOptimizer(m, lr, b1, b2, wd, eps, bool(bias_correction), bool(exclude_1d))
 
 
 def model_set_optimizer(m, opt):

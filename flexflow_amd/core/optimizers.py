@@ -123,3 +123,85 @@ class AdamOptimizer(Optimizer):
                       arena.lowp[lo:hi] if arena.lowp is not None else None, self.alpha_t, self.beta1, self.beta2,
                       self.weight_decay, self.epsilon, max_blocks=max_blocks, alpha_dev=self.alpha_dev,
                       gscale_dev=self._gscale_dev())
+
+
+class LAMBOptimizer(Optimizer):
+    """LAMB (You et al., "Large Batch Optimization for Deep Learning", ICLR 2020): Adam moments,
+    decoupled weight decay and a trust ratio |w| / |update| per logical weight, taken over the
+    whole weight on every rank. With exclude_1d, weights of one dimension or fewer (biases,
+    LayerNorm gamma / beta) get no decay and no ratio: plain bias-corrected Adam.
+
+    An update is two passes with the norms in between (Executor._lamb_update): moments(),
+    the per-weight norms and their all-reduce, then apply(). The hyper-parameters live on the
+    device ([lr, 1 / (1 - beta1^t), 1 / (1 - beta2^t)], refreshed by next()), so a captured
+    whole-step hipGraph replays the same launches. State is (m, v) per arena, as Adam's."""
+
+    two_phase = True
+
+    def __init__(self, ffmodel=None, lr=1e-3, beta1=0.9, beta2=0.999, weight_decay=0.01, epsilon=1e-6,
+                 bias_correction=True, exclude_1d=True, clip_norm=None):
+        for name, val, ok in (("lr", lr, lambda x: x >= 0), ("beta1", beta1, lambda x: 0 <= x < 1),
+                              ("beta2", beta2, lambda x: 0 <= x < 1), ("weight_decay", weight_decay, lambda x: x >= 0),
+                              ("epsilon", epsilon, lambda x: x > 0)):
+            try:
+                good = not isinstance(val, (bool, str)) and math.isfinite(float(val)) and ok(float(val))
+            except (TypeError, ValueError):
+                good = False
+            if not good:
+                raise ValueError(f"LAMBOptimizer: invalid {name}={val!r}")
+        super().__init__(ffmodel, float(lr), clip_norm)
+        self.beta1, self.beta2 = float(beta1), float(beta2)
+        self.weight_decay = float(weight_decay)
+        self.epsilon = float(epsilon)
+        self.bias_correction = bool(bias_correction)
+        self.exclude_1d = bool(exclude_1d)
+        self.beta1_t = 1.0
+        self.beta2_t = 1.0
+        self.hyper_dev = None  # fp32 [3] on the arenas' device: lr, 1 / (1 - beta1^t), 1 / (1 - beta2^t)
+
+    def _hyper(self):
+        if not self.bias_correction or self.beta1_t == 1.0:  # before the first next(): no correction yet
+            return self.lr, 1.0, 1.0
+        return self.lr, 1.0 / (1.0 - self.beta1_t), 1.0 / (1.0 - self.beta2_t)
+
+    def _refresh(self):
+        if self.hyper_dev is not None:
+            for i, x in enumerate(self._hyper()):
+                self.hyper_dev[i].fill_(x)
+
+    def use_device_alpha(self, device):
+        """LAMB always reads its hyper-parameters from the device (the hook a captured step calls)."""
+        if self.hyper_dev is None:
+            self.hyper_dev = torch.zeros(3, device=device, dtype=torch.float32)
+            self._refresh()
+
+    def set_learning_rate(self, learning_rate):
+        self.lr = float(learning_rate)
+        self._refresh()
+
+    def weight_rule(self, shape):
+        """(lambda_p, adapt_p) of a weight of this (shard) shape."""
+        if self.exclude_1d and len(shape) <= 1:
+            return 0.0, False
+        return self.weight_decay, True
+
+    def init_state(self, arena):
+        self.state[id(arena)] = (torch.zeros_like(arena.master), torch.zeros_like(arena.master))
+        self.use_device_alpha(arena.master.device)
+
+    def next(self):
+        self.beta1_t *= self.beta1
+        self.beta2_t *= self.beta2
+        self._refresh()
+
+    def moments(self, arena, table, partials):
+        m, v = self.state[id(arena)]
+        K.lamb_moments(arena.master, arena.grad, m, v, table, self.hyper_dev, self._gscale_dev(), self.beta1,
+                       self.beta2, self.epsilon, partials)
+
+    def apply(self, arena, table, norms):
+        m, v = self.state[id(arena)]
+        K.lamb_apply(arena.master, m, v, arena.lowp, table, self.hyper_dev, self.epsilon, norms)
+
+    def step(self, arena):
+        raise RuntimeError("LAMBOptimizer updates in two passes (moments / apply) through Executor.update()")

@@ -1,11 +1,11 @@
-"""Keras optimizers (reference keras/optimizers.py) -> fused HIP SGD / Adam of flexflow_amd.core.
+"""Keras optimizers (reference keras/optimizers.py) -> fused HIP SGD / Adam / LAMB of flexflow_amd.core.
 
 global_clipnorm=C clips the global gradient norm of all trainable weights to C (the core optimizers'
 clip_norm). Keras' clipnorm (per variable) and clipvalue (per element) are not implemented: they
 are accepted and ignored, like every other unknown keyword."""
 from __future__ import annotations
 
-from ..core.optimizers import AdamOptimizer, SGDOptimizer
+from ..core.optimizers import AdamOptimizer, LAMBOptimizer, SGDOptimizer
 
 
 class Optimizer:
@@ -45,7 +45,25 @@ class Adam(Optimizer):
         return self.ffhandle
 
 
+class Lamb(Optimizer):
+    """LAMB with decoupled weight decay (core LAMBOptimizer); exclude_1d leaves biases and
+    LayerNorm vectors out of the decay and the trust ratio."""
+
+    def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-6, weight_decay=0.01,
+                 bias_correction=True, exclude_1d=True, global_clipnorm=None, **kw):
+        self.learning_rate = float(kw.pop("lr", learning_rate))
+        self.beta_1, self.beta_2, self.epsilon, self.weight_decay = beta_1, beta_2, epsilon, weight_decay
+        self.bias_correction, self.exclude_1d = bias_correction, exclude_1d
+        self.global_clipnorm = global_clipnorm
+
+    def create_ffhandle(self, ffmodel):
+        self.ffhandle = LAMBOptimizer(ffmodel, self.learning_rate, self.beta_1, self.beta_2, self.weight_decay,
+                                      self.epsilon, self.bias_correction, self.exclude_1d,
+                                      clip_norm=self.global_clipnorm)
+        return self.ffhandle
+
+
 def get(spec):
     if isinstance(spec, Optimizer):
         return spec
-    return {"sgd": SGD, "adam": Adam}[str(spec).lower()]()
+    return {"sgd": SGD, "adam": Adam, "lamb": Lamb}[str(spec).lower()]()

@@ -1602,6 +1602,151 @@ def adam_update(master, grad, m, v, lowp, alpha_t, b1, b2, wd, eps, gscale=1.0, 
         lowp.copy_(master)
 
 
+# LAMB (csrc/kernels/optimizer.hip): two passes over a chunk table, one trust ratio per weight
+LAMB_CHUNK = 8192  # most elements of one chunk = one workgroup (csrc: lamb_chunk())
+
+
+class LambTable:
+    """The chunk and weight tables of one arena and one set of update ranges, built once on the
+    host (lamb_table) and uploaded once; the launches of a step read them from the device.
+    chunks: int64 [n_chunks, 2] = (start, len | weight << 32); wtab: int32 [n_weights, 4] =
+    (bits of lambda, flags, first chunk, chunk count), flags bit 0 = adapt, bit 1 = owned."""
+
+    def __init__(self, chunks, wtab, size, device):
+        self.chunks_host, self.wtab_host = chunks, wtab
+        self.n_chunks, self.n_weights, self.size = int(chunks.shape[0]), int(wtab.shape[0]), int(size)
+        self.chunks = torch.from_numpy(chunks).to(device)
+        self.wtab = torch.from_numpy(wtab).to(device)
+
+    def rows(self):
+        """[(start, len, weight)] of the chunks, for the CPU fallbacks."""
+        c = self.chunks_host
+        return [(int(s), int(p & 0xFFFFFFFF), int(p >> 32)) for s, p in c]
+
+
+def lamb_table(entries, ranges, n_weights, size, device, owned=()):
+    """entries: [(offset, numel, weight, lambda, adapt)], one per weight of the arena, in arena
+    order; ranges: the [lo, hi) element ranges this rank updates (the whole arena, or its ZeRO
+    chunks). Each piece (entry x range) is cut into chunks of at most LAMB_CHUNK elements whose
+    starts are 16-byte aligned; the padding between entries is in no chunk. Every entry's weight
+    gets a row (with no chunks if no range meets it), and so does every weight index in `owned`
+    (weights this rank holds no shard of: their norms are written as zeros). Misaligned or
+    out-of-range input raises RuntimeError: the kernels trust the table."""
+    import numpy as np
+    size, n_weights = int(size), int(n_weights)
+    rs = sorted((int(lo), int(hi)) for lo, hi in ranges)
+    end = 0
+    for lo, hi in rs:
+        if lo % 4 or lo < end or hi < lo or hi > size:
+            raise RuntimeError(f"lamb_table: range [{lo}, {hi}) is misaligned, overlapping or outside [0, {size})")
+        end = hi
+    wtab = np.zeros((n_weights, 4), dtype=np.int32)
+    seen = set()
+    chunks = []
+    for off, n, wi, lam, adapt in entries:
+        off, n, wi = int(off), int(n), int(wi)
+        if off % 4 or off < 0 or n < 0 or off + n > size:
+            raise RuntimeError(f"lamb_table: entry [{off}, {off + n}) is misaligned or outside [0, {size})")
+        if not 0 <= wi < n_weights or wi in seen:
+            raise RuntimeError(f"lamb_table: weight index {wi} is repeated or outside [0, {n_weights})")
+        seen.add(wi)
+        first = len(chunks)
+        for lo, hi in rs:
+            a, b = max(off, lo), min(off + n, hi)
+            while a < b:
+                ln = min(LAMB_CHUNK, b - a)
+                chunks.append((a, ln | (wi << 32)))
+                a += ln
+        wtab[wi] = (np.float32(lam).view(np.int32), (1 if adapt else 0) | 2, first, len(chunks) - first)
+    for wi in owned:
+        if not 0 <= int(wi) < n_weights or int(wi) in seen:
+            raise RuntimeError(f"lamb_table: weight index {wi} is repeated or outside [0, {n_weights})")
+        seen.add(int(wi))
+        wtab[int(wi)] = (0, 2, 0, 0)
+    return LambTable(np.array(chunks, dtype=np.int64).reshape(-1, 2), wtab, size, device)
+
+
+def _lamb_u(m, v, w, rc1, rc2, eps, lam):
+    return (m * rc1) / ((v * rc2).sqrt() + eps) + lam * w
+
+
+def lamb_moments(master, grad, m, v, table, hyper, gscale_dev, b1, b2, eps, partials):
+    """Stage 1 over the table's chunks: m, v updated in place from gscale_dev * grad, and per chunk
+    (sum w^2, sum u^2) into partials [2 * n_chunks], u = m rc1 / (sqrt(v rc2) + eps) + lambda w.
+    hyper: fp32 [3] = (lr, rc1, rc2) on the tensors' device. grad is never written."""
+    if native(master):
+        ext().lamb_moments(master, grad, m, v, table.chunks, table.wtab, hyper, gscale_dev, b1, b2, eps, partials)
+        return
+    gs = gscale_dev[0] if gscale_dev is not None else 1.0
+    lam = torch.from_numpy(table.wtab_host[:, 0].copy()).view(torch.float32)
+    for i, (s, ln, wi) in enumerate(table.rows()):
+        g = grad[s:s + ln] * gs
+        m[s:s + ln].mul_(b1).add_((1 - b1) * g)
+        v[s:s + ln].mul_(b2).add_((1 - b2) * g * g)
+        w = master[s:s + ln]
+        u = _lamb_u(m[s:s + ln], v[s:s + ln], w, hyper[1], hyper[2], eps, lam[wi])
+        partials[2 * i] = (w * w).sum(dtype=torch.float32)
+        partials[2 * i + 1] = (u * u).sum(dtype=torch.float32)
+
+
+def lamb_norms(partials, table, count, norms):
+    """norms[2p], norms[2p + 1] = each owned weight's chunk partials summed in index order; zeros
+    when count is false (a replica another rank counts) or the weight has no chunk here."""
+    if native(partials):
+        ext().lamb_norms(partials, table.n_chunks, table.wtab, bool(count), norms)
+        return
+    for p, (_, flags, first, cnt) in enumerate(table.wtab_host):
+        if flags & 2:
+            part = partials[2 * first:2 * (first + cnt)].view(-1, 2) if count else partials[:0].view(-1, 2)
+            norms[2 * p] = part[:, 0].sum(dtype=torch.float32)
+            norms[2 * p + 1] = part[:, 1].sum(dtype=torch.float32)
+
+
+def lamb_apply(master, m, v, lowp, table, hyper, eps, norms):
+    """Stage 2: w -= lr * r_p * u with r_p = sqrt(norms[2p] / norms[2p + 1]) formed from the
+    (all-reduced) norms where the weight adapts and both are > 0, else 1; u recomputed from the
+    stored m, v, w; the bf16 copy written in the same pass."""
+    if native(master):
+        ext().lamb_apply(master, m, v, lowp, table.chunks, table.wtab, hyper, eps, norms)
+        return
+    lam = torch.from_numpy(table.wtab_host[:, 0].copy()).view(torch.float32)
+    for s, ln, wi in table.rows():
+        wn, un = norms[2 * wi].sqrt(), norms[2 * wi + 1].sqrt()
+        r = wn / un if (table.wtab_host[wi, 1] & 1) and wn > 0 and un > 0 else 1.0
+        w = master[s:s + ln]
+        w.sub_(hyper[0] * r * _lamb_u(m[s:s + ln], v[s:s + ln], w, hyper[1], hyper[2], eps, lam[wi]))
+        if lowp is not None:
+            lowp[s:s + ln].copy_(w)
+
+
+def lamb_ref(w, g, m, v, entries, t, lr, b1, b2, eps, bias_correction=True, coef=1.0):
+    """The LAMB step in float64, the oracle of the kernels and of the optimizer. w, g, m, v: flat
+    tensors; entries as in lamb_table, several entries may share a weight index (shards of one
+    weight: the norms run over all of them). Returns (w, m, v, norms [n, 2]) as new float64
+    tensors, norms holding (sum w^2, sum u^2) per weight index; elements in no entry are copied."""
+    w, g, m, v = (x.detach().cpu().double().clone() for x in (w, g, m, v))
+    d1 = 1 - b1 ** t if bias_correction else 1.0
+    d2 = 1 - b2 ** t if bias_correction else 1.0
+    n_w = 1 + max((int(e[2]) for e in entries), default=-1)
+    norms = torch.zeros(n_w, 2, dtype=torch.float64)
+    us = []
+    for off, n, wi, lam, adapt in entries:
+        s = slice(int(off), int(off) + int(n))
+        gp = coef * g[s]
+        m[s] = b1 * m[s] + (1 - b1) * gp
+        v[s] = b2 * v[s] + (1 - b2) * gp * gp
+        u = (m[s] / d1) / ((v[s] / d2).sqrt() + eps) + lam * w[s]
+        norms[wi, 0] += (w[s] ** 2).sum()
+        norms[wi, 1] += (u ** 2).sum()
+        us.append(u)
+    for (off, n, wi, lam, adapt), u in zip(entries, us):
+        s = slice(int(off), int(off) + int(n))
+        wn, un = norms[wi, 0].sqrt(), norms[wi, 1].sqrt()
+        r = wn / un if adapt and wn > 0 and un > 0 else 1.0
+        w[s] = w[s] - lr * r * u
+    return w, m, v, norms
+
+
 # ---------------------------------------------------------------------------- initializers
 def _mix64(z):
     M = (1 << 64) - 1

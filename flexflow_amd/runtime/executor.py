@@ -649,8 +649,9 @@ class Executor:
         from ..core.optimizers import Optimizer
         ranged = opt is not None and getattr(type(opt), "step_range", None) not in (None, Optimizer.step_range)
         # clipping by global norm needs every gradient before any weight moves: no overlapped update
+        # (LAMB likewise: its per-weight norms need every gradient; it has no step_range either)
         return (self.training and ranged and not self.zero
-                and not getattr(opt, "clip_norm", None)
+                and not getattr(opt, "clip_norm", None) and not getattr(opt, "two_phase", False)
                 and not self._sparse_plan(opt)
                 and not self.hooks and self.device.type == "cuda"
                 and not torch.cuda.is_current_stream_capturing()
@@ -1151,10 +1152,16 @@ class Executor:
         # so this update runs dense (and zero_gradients then clears the whole table)
         multi_bwd = self._bwd_since_update > 1
         self._bwd_since_update = 0
+        if getattr(optimizer, "two_phase", False):
+            self._lamb_update(optimizer)
         for grp, ar in self.arenas.items():
             if not ar.size:
                 continue
             bs = self.zero_buckets.get(grp)
+            if getattr(optimizer, "two_phase", False):
+                if bs is not None:
+                    self._zero_all_gather(grp, ar, bs)
+                continue
             sparse = self._sparse_plan(optimizer).get(grp) if bs is None and not multi_bwd else None
             if sparse:
                 self._sparse_update(optimizer, grp, ar, sparse)
@@ -1184,6 +1191,74 @@ class Executor:
         self._overlap_active = False
         self._opt_next_done = None
         self.step_idx += 1
+
+    def _zero_all_gather(self, grp, ar, bs):
+        """Sharded optimizer: the updated compute copy (bf16, or the fp32 master itself) of every
+        bucket is gathered from the ranks' own chunks, in place, while the next forward runs."""
+        g = self.comm.group(grp)
+        src = ar.lowp if ar.lowp is not None else ar.master
+        for i, b in enumerate(bs):
+            lo, hi = b["own"]
+            self._ag_pending[(grp, i)] = dist.all_gather_into_tensor(src[b["lo"]:b["hi"]], src[lo:hi], group=g,
+                                                                      async_op=True)
+        self._master_stale |= ar.lowp is not None
+
+    def _lamb_setup(self, optimizer):
+        """LAMB's device tables, built once per optimizer and set of hyper-parameters the tables
+        hold (outside any step or capture): per arena a chunk table over the ranges this rank
+        updates (the whole arena, or its ZeRO chunks) and a workspace of chunk partials, and one
+        [2 P] vector of per-weight norms, P = the model's distinct weights in layer order (the
+        same index on every rank, whatever shard of a weight a rank holds)."""
+        key = (id(optimizer), optimizer.weight_decay, optimizer.exclude_1d)
+        if getattr(self, "_lamb_key", None) == key:
+            return self._lamb
+        slot = {}
+        for L in self.layers:
+            for w in L.weights:
+                slot.setdefault(w.guid, len(slot))
+        P = len(slot)
+        held = set()
+        plan = []
+        for grp, ar in self.arenas.items():
+            if not ar.size:
+                continue
+            entries = []
+            for w, off, n, shape in ar.entries:
+                lam, adapt = optimizer.weight_rule(shape)
+                entries.append((off, n, slot[w.guid], lam, adapt))
+                held.add(slot[w.guid])
+            bs = self.zero_buckets.get(grp)
+            ranges = [b["own"] for b in bs if b["own"][1] > b["own"][0]] if bs is not None else [(0, ar.size)]
+            # a replicated arena counts on the lowest rank of its group, a ZeRO arena by each
+            # rank's own chunks, a private arena whole (the rule of _clip_coefficient)
+            count = bs is not None or len(grp) <= 1 or self.rank == min(grp)
+            plan.append([ar, entries, ranges, count])
+        tabs = []
+        for i, (ar, entries, ranges, count) in enumerate(plan):
+            # weights this rank holds no shard of: the first table writes their zeros
+            owned = [p for p in range(P) if p not in held] if i == 0 else ()
+            tab = K.lamb_table(entries, ranges, P, ar.master.numel(), self.device, owned=owned)
+            partials = torch.zeros(max(2 * tab.n_chunks, 2), dtype=torch.float32, device=self.device)
+            tabs.append((ar, tab, partials, count))
+        norms = torch.zeros(max(2 * P, 2), dtype=torch.float32, device=self.device)
+        self._lamb_key, self._lamb = key, (tabs, norms)
+        return self._lamb
+
+    def _lamb_update(self, optimizer):
+        """The two-pass LAMB update: stage 1 over every arena's ranges, the per-weight norms, one
+        all-reduce of the [2 P] vector over the world on the compute stream, stage 2. Nothing
+        here touches the host, so a captured update replays it."""
+        tabs, norms = self._lamb_setup(optimizer)
+        if not tabs:  # a rank without weights still takes part in the all-reduce, with zeros
+            norms.zero_()
+        for ar, tab, partials, _ in tabs:
+            optimizer.moments(ar, tab, partials)
+        for ar, tab, partials, count in tabs:
+            K.lamb_norms(partials, tab, count, norms)
+        if self.comm.distributed and self.comm.world > 1:
+            dist.all_reduce(norms, group=dist.group.WORLD)
+        for ar, tab, _, _ in tabs:
+            optimizer.apply(ar, tab, norms)
 
     def _sparse_update(self, optimizer, grp, ar, sparse):
         """Dense SGD over the arena minus the sparse tables, then each table's touched rows only
@@ -1258,6 +1333,8 @@ class Executor:
             optimizer.init_state(ar)
         if getattr(optimizer, "clip_norm", None):
             self._clip_setup(optimizer)
+        if getattr(optimizer, "two_phase", False):
+            self._lamb_setup(optimizer)
 
     def _clip_setup(self, optimizer):
         """Gradient clipping's device scalars [sum of squares, norm, coefficient] and grad_sumsq's
