@@ -46,6 +46,16 @@ struct AttnArgs {
   uint32_t drop_thr = 0;
   float drop_scale = 1.f;
   int b0 = 0, h0 = 0, H_total = 0;
+  // score bias, fp32 [Bb][Hb][Sq][Sk] (rows contiguous: row stride Sk), or null: scores are
+  // s = scale q.k + sbias[b][h][q][k] in the forward and in the backward's recompute of P. sbias_sb /
+  // sbias_sh are element strides over batch and head, 0 = broadcast. Selects the BIAS = true
+  // instantiations of attn_fwd_kernel / attn_bwd_kernel (always MASK = true; attn_fwd2_kernel and
+  // attn_bwd1b_kernel have none, so attn_bwd then leaves the fused bias gradient to the caller).
+  // An element of -inf, or one so negative that sbias * log2(e) overflows fp32 (finfo.min masks),
+  // removes that key; a query row with no key left gives o = 0, lse = +inf and zero gradients. +inf
+  // and NaN are the caller's problem. The score bias takes no gradient.
+  const float* sbias = nullptr;
+  int64_t sbias_sb = 0, sbias_sh = 0;
 };
 
 // out[h][q][k] = keep(b, h0 + h, q, k) ? x[h][q][k] * drop_scale : 0 over an fp32 [H][Sq][Sk] slab of

@@ -142,8 +142,15 @@ __device__ __forceinline__ int key_limit(const AttnArgs& a, int b) {
 // lane's row key is derived once, outside the tile loop; a tile costs one 32-bit hash per register
 // quad (4 consecutive keys). The DMA form sits exactly at the 128 registers of 4 workgroups per CU
 // and spilled 3 of them with DROP, so its DROP instantiation is bounded for 3.
-template <int D, bool MASK, bool DMA, bool DROP = false>
-__global__ void __launch_bounds__(256, DMA ? (DROP ? 3 : 4) : 2) attn_fwd_kernel(AttnArgs a) {
+// BIAS (score bias, AttnArgs.sbias; always MASK = true): s = scale q.k + bias, so the scores go to
+// log2 units (sacc * sl2 + bias * LOG2E) before the mask and the running max, and P = exp2(s - m).
+// The lane's 8 key quads of a tile are requested ahead of the S MFMAs: one 16-B load per quad on
+// full tiles of 16-B aligned rows, predicated 4-B loads elsewhere (nothing is read at or past Sk
+// or Sq). The 32 bias registers are live across the MFMAs, so these forms are bounded like DROP.
+template <int D, bool MASK, bool DMA, bool DROP = false, bool BIAS = false>
+__global__ void __launch_bounds__(256, DMA ? (DROP || BIAS ? 3 : 4) : (D == 128 && DROP && BIAS ? 1 : 2))
+    attn_fwd_kernel(AttnArgs a) {
+  static_assert(MASK || !BIAS, "the score bias forms are MASK = true");
   constexpr int KV = 64;
   constexpr int TB = KV * D * 2;  // bytes of one K or V tile
   __shared__ __attribute__((aligned(16))) char smem[4 * TB];
@@ -169,6 +176,13 @@ __global__ void __launch_bounds__(256, DMA ? (DROP ? 3 : 4) : 2) attn_fwd_kernel
   for (int i = 0; i < D / 32; ++i) oacc[i] = f32x16{};
   float m = -INFINITY, lsum = 0.f;
   const float sl2 = a.scale * LOG2E;
+  // BIAS: this lane's bias row; 16-B loads need every row start 16-B aligned (wave-uniform test)
+  const float* brow = nullptr;
+  bool bvec = false;
+  if constexpr (BIAS) {
+    brow = a.sbias + (int64_t)b * a.sbias_sb + (int64_t)hh * a.sbias_sh + (int64_t)min(qrow, a.Sq - 1) * a.Sk;
+    bvec = (((uintptr_t)a.sbias | (uintptr_t)(a.sbias_sb * 4) | (uintptr_t)(a.sbias_sh * 4) | (uintptr_t)(a.Sk * 4)) & 15) == 0;
+  }
   uint32_t rkey = 0;
   if constexpr (DROP) {
     const int64_t step = a.rng_step ? *a.rng_step : 0;  // uniform: one scalar load per workgroup
@@ -237,6 +251,33 @@ __global__ void __launch_bounds__(256, DMA ? (DROP ? 3 : 4) : 2) attn_fwd_kernel
         sv.load(V, a.v_ss, (t + 1) * KV, a.Sk, tid);
       }
     }
+    const int kbase = t * KV;
+    // BIAS: the lane's keys kbase + 32 kt + 8 g + 4 h + 0..3 of its row (a row past Sq reads row
+    // Sq - 1; its scores are never stored)
+    // (D = 128 has no 32 registers to spare across the MFMAs: it loads them behind the MFMAs)
+    constexpr bool BEARLY = BIAS && D == 64;
+    float bv[BIAS ? 2 : 1][16];
+    auto load_bias = [&]() {
+      const float* bp = brow + kbase + 4 * h;
+      if (bvec && kbase + KV <= a.Sk) {
+#pragma unroll
+        for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            const float4 q4 = *reinterpret_cast<const float4*>(bp + 32 * kt + 8 * g);
+            bv[kt][4 * g] = q4.x; bv[kt][4 * g + 1] = q4.y; bv[kt][4 * g + 2] = q4.z; bv[kt][4 * g + 3] = q4.w;
+          }
+      } else {
+#pragma unroll
+        for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int ko2 = 32 * kt + (r & 3) + 8 * (r >> 2);
+            bv[kt][r] = kbase + 4 * h + ko2 < a.Sk ? bp[ko2] : 0.f;
+          }
+      }
+    };
+    if constexpr (BEARLY) load_bias();
     // S^T[key][q] for keys 32kt..32kt+31 of this tile
     f32x16 sacc[2] = {f32x16{}, f32x16{}};
 #pragma unroll
@@ -247,10 +288,16 @@ __global__ void __launch_bounds__(256, DMA ? (DROP ? 3 : 4) : 2) attn_fwd_kernel
         sacc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[s], sacc[kt], 0, 0, 0);
       }
     }
+    if constexpr (BIAS) {  // to log2 units, bias added: a bias of -inf (or one whose product overflows) removes the key
+      if constexpr (!BEARLY) load_bias();
+#pragma unroll
+      for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sacc[kt][r] = __builtin_fmaf(sacc[kt][r], sl2, bv[kt][r] * LOG2E);
+    }
     // mask (only on tiles that cross the sequence end or the causal diagonal: a wave-uniform
     // test), online softmax on the raw scores (lane-local + xor-32 partner), scale folded into
     // one FMA per element: p = exp2(s * sl2 - m * sl2)
-    const int kbase = t * KV;
     const bool need_mask = MASK && ((kbase + KV > klim) || (a.causal && kbase + KV - 1 > q0));
     if (need_mask) {
 #pragma unroll
@@ -267,7 +314,8 @@ __global__ void __launch_bounds__(256, DMA ? (DROP ? 3 : 4) : 2) attn_fwd_kernel
     for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
       for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sacc[kt][r]);
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64)) * sl2;
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    if constexpr (!BIAS) mx *= sl2;
     // deferred max (cdna_hip_programming.md T13): the running max moves (and O / l are rescaled)
     // only when some row's tile max exceeds it by more than a.rescale_thr (log2 units); otherwise P is
     // taken against the old max and stays <= 2^rescale_thr. Decided before this tile's P exists, so
@@ -288,7 +336,7 @@ __global__ void __launch_bounds__(256, DMA ? (DROP ? 3 : 4) : 2) attn_fwd_kernel
     for (int kt = 0; kt < 2; ++kt) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const float p = fast_exp2(__builtin_fmaf(sacc[kt][r], sl2, -msafe));
+        const float p = BIAS ? fast_exp2(sacc[kt][r] - msafe) : fast_exp2(__builtin_fmaf(sacc[kt][r], sl2, -msafe));
         sacc[kt][r] = p;
         if (r & 1) rs1 += p;
         else rs0 += p;
@@ -724,8 +772,13 @@ __device__ __forceinline__ unsigned pack_bf2(float x, float y) {
 //    one premultiplied constant, so an element costs one 32-bit hash. dV takes keep ? P : 0 (its
 //    1 / (1 - p_eff) in the epilogue), dP = keep ? dP_raw / (1 - p_eff) : 0, dS = P (dP - delta)
 //    with the undropped P; delta = rowsum(dO . O) holds because O carries the dropout.
-template <int D, int NW, bool MASK, bool CHAIN, bool DMA = false, bool DROP = false>
+//  * BIAS (score bias, AttnArgs.sbias; always MASK = true): P = exp2(S*sl2 + bias*LOG2E - lse2). The
+//    lane owns one key, so the 16 bias elements of a 32-query block are 4-B loads that the lanes of
+//    a half-wave coalesce along a bias row; they are requested ahead of the block's S / dP MFMAs
+//    and predicated on key < Sk and q < Sq. The bias takes no gradient (dS is not written out).
+template <int D, int NW, bool MASK, bool CHAIN, bool DMA = false, bool DROP = false, bool BIAS = false>
 __global__ void __launch_bounds__(64 * NW, 8 / NW) attn_bwd_kernel(AttnArgs a, int nkb, int pass) {
+  static_assert(MASK || !BIAS, "the score bias forms are MASK = true");
   constexpr int NT = 64 * NW;
   constexpr int QT = 64;       // queries per loop step
   constexpr int KB = 32 * NW;  // keys per workgroup
@@ -758,6 +811,15 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) attn_bwd_kernel(AttnArgs a, i
   const float* LSE = a.lse + (int64_t)bh * a.Sq;
   const float* DL = a.delta + (int64_t)bh * a.Sq;
   const float sl2 = a.scale * LOG2E;
+  // BIAS: the (batch, head)'s bias rows (uniform) and the lane's element offset inside a group of 8
+  // rows: its key column (a key past Sk reads column Sk - 1 and is masked) in row 4 h. One register
+  // addresses all of a block's loads; the row part of every address is scalar.
+  const float* bslab = nullptr;
+  unsigned blane = 0;
+  if constexpr (BIAS) {
+    bslab = a.sbias + (int64_t)b * a.sbias_sb + (int64_t)hh * a.sbias_sh;
+    blane = (unsigned)(4 * h * a.Sk + min(key, a.Sk - 1));
+  }
   uint64_t hkey = 0;  // DROP: this (batch, head)'s stream (wave-uniform)
   uint32_t kmul = 0;  // DROP: the lane's key quad, premultiplied
   int kshift = 0;     // DROP: the lane's byte of the quad's word
@@ -871,15 +933,18 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) attn_bwd_kernel(AttnArgs a, i
     const float* lse_l = reinterpret_cast<const float*>(tb + 2 * QB);
     const float* dl_l = lse_l + QT;
     const bool more = t + 1 < nqt;
+    // D = 64 register staging with DROP and BIAS: the staged tile's registers do not fit beside the
+    // tile's work (2 spilled), so the next tile is fetched right before it is stashed, nothing under it
+    constexpr bool FETCH_LATE = D == 64 && !DMA && DROP && BIAS;
     if (more) {  // in flight during this tile's MFMAs
       if constexpr (DMA) dma_rows(t + 1);  // buffer (t+1)&1: its readers finished before tile t-1's mid barrier
-      else fetch(t + 1);
+      else if constexpr (!FETCH_LATE) fetch(t + 1);
     }
     // chain, key block > 0: the previous launch's dQ running sum for this wave's dQ tile, requested
     // now so its HBM round trip runs under the tile's MFMAs (read at its use below, the load sat on
     // the workgroup's critical path once per query tile)
     float4 prev[4];
-    if constexpr (NW >= 2 * (D / 32) && !DROP) {  // DROP: these 16 registers made the chained forms spill
+    if constexpr (NW >= 2 * (D / 32) && !DROP && !BIAS) {  // DROP, BIAS: these 16 registers made the chained forms spill
       const int tile = wave % (2 * (D / 32));
       const int q = qbase + 32 * (tile / (D / 32)) + (lane & 31);
       if (chain && kblk > 0 && wave < 2 * (D / 32) && (!MASK || q < a.Sq)) {
@@ -892,6 +957,25 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) attn_bwd_kernel(AttnArgs a, i
     for (int qt = 0; qt < 2; ++qt) {
       // S[q][key] and dP[q][key] for 32 queries x this wave's 32 keys
       f32x16 sacc = f32x16{}, pacc = f32x16{};
+      // BIAS: rows q = qbase + 32 qt + (r & 3) + 8 (r >> 2) + 4 h of the lane's key column (a row
+      // past Sq reads as 0)
+      // (with DROP there are no 16 registers to spare across the MFMAs: loaded behind them)
+      constexpr bool BEARLY = BIAS && !DROP;
+      float bv[BIAS ? 16 : 1];
+      auto load_bias = [&]() {
+        const float* bt = bslab + (int64_t)(qbase + 32 * qt) * a.Sk;
+        if (qbase + 32 * qt + 32 <= a.Sq) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) bv[r] = (bt + (int64_t)((r & 3) + 8 * (r >> 2)) * a.Sk)[blane];
+        } else {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int qo = (r & 3) + 8 * (r >> 2);
+            bv[r] = qbase + 32 * qt + 4 * h + qo < a.Sq ? (bt + (int64_t)qo * a.Sk)[blane] : 0.f;
+          }
+        }
+      };
+      if constexpr (BEARLY) load_bias();
 #pragma unroll
       for (int s = 0; s < D / 16; ++s) {
         const int row = 32 * qt + (lane & 31);
@@ -902,12 +986,18 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) attn_bwd_kernel(AttnArgs a, i
       }
       // P = exp2(S*sl2 - lse2), dS = P * (dP - delta); accumulator rows 4g..4g+3 are 4 consecutive
       // queries, so their lse / delta come in as one 16-B LDS read each
+      if constexpr (BIAS && !BEARLY) load_bias();
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4) {
         const float4 L4 = *reinterpret_cast<const float4*>(lse_l + 32 * qt + 8 * g4 + 4 * h);
         const float lv[4] = {L4.x, L4.y, L4.z, L4.w};
 #pragma unroll
-        for (int j = 0; j < 4; ++j) sacc[4 * g4 + j] = fast_exp2(sacc[4 * g4 + j] * sl2 - lv[j]);
+        for (int j = 0; j < 4; ++j) {
+          if constexpr (BIAS)
+            sacc[4 * g4 + j] = fast_exp2(__builtin_fmaf(sacc[4 * g4 + j], sl2, bv[4 * g4 + j] * LOG2E) - lv[j]);
+          else
+            sacc[4 * g4 + j] = fast_exp2(sacc[4 * g4 + j] * sl2 - lv[j]);
+        }
       }
       if (MASK) {
         const bool need = (kb0 + wave * 32 + 31 >= klim) || (a.causal && kb0 + wave * 32 + 31 > qbase + 32 * qt);
@@ -983,7 +1073,7 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) attn_bwd_kernel(AttnArgs a, i
 #pragma unroll
           for (int g = 0; g < 4; ++g) {
             float4 pv;
-            if constexpr (NW >= 2 * (D / 32) && !DROP) pv = prev[g];  // prefetched at the top of the tile
+            if constexpr (NW >= 2 * (D / 32) && !DROP && !BIAS) pv = prev[g];  // prefetched at the top of the tile
             else pv = *reinterpret_cast<const float4*>(prow + 8 * g);
             acc[4 * g] += pv.x; acc[4 * g + 1] += pv.y; acc[4 * g + 2] += pv.z; acc[4 * g + 3] += pv.w;
           }
@@ -1067,6 +1157,9 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) attn_bwd_kernel(AttnArgs a, i
         put_dq(dq_keep, dq_tile, dq_kpart);
       }
     } else {
+      if constexpr (FETCH_LATE) {
+        if (more) fetch(t + 1);
+      }
       if (more) stash(t + 1);  // other buffer: its last readers finished before this tile's first sync
       lds_barrier();           // tile t+1 visible; dS^T reads of tile t done before it is rewritten
     }
@@ -1677,8 +1770,8 @@ static bool dma_rows_ok(const void* p, int64_t ss, int rows) {
 }
 
 // one workgroup per 128 QB query rows of a (batch, head), QB 32-row blocks per wave: QB = 2 is
-// attn_fwd2_kernel (D = 64, LDS-DMA, no dropout form), QB = 1 attn_fwd_kernel, whose DROP
-// instantiations are always MASK = true
+// attn_fwd2_kernel (D = 64, LDS-DMA, no dropout and no score bias form), QB = 1 attn_fwd_kernel,
+// whose DROP and BIAS instantiations are always MASK = true
 template <int D, int QB, bool DMA>
 static void launch_fwd(const AttnArgs& a, bool mask, hipStream_t st) {
   constexpr int ROWS = 128 * QB;
@@ -1687,6 +1780,10 @@ static void launch_fwd(const AttnArgs& a, bool mask, hipStream_t st) {
     static_assert(D == 64 && DMA, "attn_fwd2_kernel is fixed to D = 64 and LDS-DMA staging");
     if (mask) hipLaunchKernelGGL((attn_fwd2_kernel<true>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((attn_fwd2_kernel<false>), grid, dim3(256), 0, st, a);
+  } else if (a.sbias && a.drop_thr > 0) {
+    hipLaunchKernelGGL((attn_fwd_kernel<D, true, DMA, true, true>), grid, dim3(256), 0, st, a);
+  } else if (a.sbias) {
+    hipLaunchKernelGGL((attn_fwd_kernel<D, true, DMA, false, true>), grid, dim3(256), 0, st, a);
   } else if (a.drop_thr > 0) {
     hipLaunchKernelGGL((attn_fwd_kernel<D, true, DMA, true>), grid, dim3(256), 0, st, a);
   } else if (mask) {
@@ -1707,8 +1804,8 @@ void attn_fwd(AttnArgs a, hipStream_t st) {
     // 64 query rows per wave (attn_fwd2_kernel): 2-6 % faster from S = 512 up, slower at S = 256
     // (half the workgroups), profiles/attn_fwd_variants_r4.txt; its DROP form (230 VGPRs, no
     // scratch) measured slower at S = 512 too, 60.1 against 57.8 us at B32 H16 (docs/PERFORMANCE.md
-    // 'Attention dropout'), so it has none
-    if (v == 3 && dma_ok && !drop && a.Sq >= 512) launch_fwd<64, 2, true>(a, mask, st);
+    // 'Attention dropout'), so it has none; nor has it a score bias form
+    if (v == 3 && dma_ok && !drop && !a.sbias && a.Sq >= 512) launch_fwd<64, 2, true>(a, mask, st);
     else if (v >= 1 && dma_ok) launch_fwd<64, 1, true>(a, mask, st);
     else launch_fwd<64, 1, false>(a, mask, st);
   } else if (a.D == 128) {
@@ -1716,24 +1813,26 @@ void attn_fwd(AttnArgs a, hipStream_t st) {
   }
 }
 
-// attn_bwd_kernel, chained (one launch per key block) or as slabs; the DROP instantiations
-// (attention dropout) are always MASK = true
+// attn_bwd_kernel, chained (one launch per key block) or as slabs; the DROP (attention dropout)
+// and BIAS (score bias) instantiations are always MASK = true
 template <int D, int NW, bool DMA = false>
 static void launch_bwd(const AttnArgs& a, int nkb, bool chain, hipStream_t st) {
   const bool mask = a.causal || a.Sk % (32 * NW) != 0 || a.Sq % 64 != 0 || a.key_lens != nullptr;
   const int bh = a.B * a.H;
-  auto go = [&](auto m, auto d) {
-    constexpr bool MASK = decltype(m)::value, DROP = decltype(d)::value;
+  auto go = [&](auto m, auto d, auto sb) {
+    constexpr bool MASK = decltype(m)::value, DROP = decltype(d)::value, BIAS = decltype(sb)::value;
     if (chain) {
       for (int p = 0; p < nkb; ++p)
-        hipLaunchKernelGGL((attn_bwd_kernel<D, NW, MASK, true, DMA, DROP>), dim3(bh), dim3(64 * NW), 0, st, a, nkb, p);
+        hipLaunchKernelGGL((attn_bwd_kernel<D, NW, MASK, true, DMA, DROP, BIAS>), dim3(bh), dim3(64 * NW), 0, st, a, nkb, p);
     } else {
-      hipLaunchKernelGGL((attn_bwd_kernel<D, NW, MASK, false, DMA, DROP>), dim3(bh * nkb), dim3(64 * NW), 0, st, a, nkb, 0);
+      hipLaunchKernelGGL((attn_bwd_kernel<D, NW, MASK, false, DMA, DROP, BIAS>), dim3(bh * nkb), dim3(64 * NW), 0, st, a, nkb, 0);
     }
   };
-  if (a.drop_thr > 0) go(std::true_type{}, std::true_type{});
-  else if (mask) go(std::true_type{}, std::false_type{});
-  else go(std::false_type{}, std::false_type{});
+  if (a.sbias && a.drop_thr > 0) go(std::true_type{}, std::true_type{}, std::true_type{});
+  else if (a.sbias) go(std::true_type{}, std::false_type{}, std::true_type{});
+  else if (a.drop_thr > 0) go(std::true_type{}, std::true_type{}, std::false_type{});
+  else if (mask) go(std::true_type{}, std::false_type{}, std::false_type{});
+  else go(std::false_type{}, std::false_type{}, std::false_type{});
 }
 
 bool attn_bwd(AttnArgs a, hipStream_t st) {
@@ -1756,10 +1855,10 @@ bool attn_bwd(AttnArgs a, hipStream_t st) {
   const bool dma_ok = v == 10 && dma_rows_ok(a.q, a.q_ss, a.Sq) && dma_rows_ok(a.dout, a.do_ss, a.Sq);
   if (a.D == 64) {
     hipLaunchKernelGGL(attn_bwd_pre_kernel<64>, gpre, dim3(256), 0, st, a);
-    // attn_bwd1b_kernel has no DROP instantiation (it uses every VGPR already): with dropout the
-    // generic kernel runs the chained form too, and the fused bias gradient is left to the caller
-    // (returns false)
-    if (chain && dma_ok && !drop) {
+    // attn_bwd1b_kernel has no DROP and no score bias instantiation (it uses every VGPR already):
+    // with dropout or a score bias the generic kernel runs the chained form too, and the fused bias
+    // gradient is left to the caller (returns false)
+    if (chain && dma_ok && !drop && !a.sbias) {
       const bool m = a.causal || a.Sk % 256 != 0 || a.Sq % 64 != 0 || a.key_lens != nullptr;
       const int bh = a.B * a.H;
       // fused bias-gradient sums: non-causal (every query tile's last key block is the last launch)

@@ -637,6 +637,24 @@ void key_len_mask_f32(Tensor s, Tensor key_lens, int64_t b, int64_t Sk, double v
                         cur_stream());
 }
 
+// s [H, Sq, Sk] = scale * s + bias (fp32, rows contiguous, head stride bias_sh elements, 0 = broadcast)
+void score_bias_f32(Tensor s, Tensor bias, int64_t H, int64_t Sq, int64_t Sk, int64_t bias_sh, double scale) {
+  check_dev(s, "s");
+  TORCH_CHECK(s.scalar_type() == at::kFloat && s.is_contiguous() && s.numel() == H * Sq * Sk);
+  TORCH_CHECK(bias.scalar_type() == at::kFloat && bias.device() == s.device() && bias_sh >= 0 &&
+                  (bias.dim() == 0 || bias.stride(-1) == 1) && (bias_sh ? H - 1 : 0) * bias_sh + Sq * Sk <= bias.numel(),
+              "score_bias_f32: bias must be fp32 on the scores' device and cover its strides");
+  ffk::score_bias_f32(s.data_ptr<float>(), bias.data_ptr<float>(), (int)H, (int)Sq, (int)Sk, bias_sh, (float)scale,
+                      cur_stream());
+}
+
+void masked_prob_zero_f32(Tensor p, Tensor s) {
+  check_dev(p, "p");
+  TORCH_CHECK(p.scalar_type() == at::kFloat && s.scalar_type() == at::kFloat && p.is_contiguous() && s.is_contiguous() &&
+              p.numel() == s.numel() && p.device() == s.device());
+  ffk::masked_prob_zero_f32(p.data_ptr<float>(), s.data_ptr<float>(), p.numel(), cur_stream());
+}
+
 void causal_mask_f32(Tensor s, int64_t Sq, int64_t Sk) {
   TORCH_CHECK(s.scalar_type() == at::kFloat && s.is_contiguous() && s.numel() % Sk == 0);
   ffk::causal_mask_f32(s.data_ptr<float>(), s.numel() / Sk, (int)Sq, (int)Sk, cur_stream());
@@ -765,11 +783,30 @@ void attn_drop_args(ffk::AttnArgs& a, const Tensor& q, int64_t drop_thr, const o
   TORCH_CHECK(b0 >= 0 && h0 >= 0 && h0 + H <= a.H_total, "attn: head shard outside H_total");
 }
 
+// score bias (AttnArgs.sbias): fp32 [.., Sq, Sk] on q's device whose last two dims are contiguous;
+// sb / sh are its element strides over batch and head, 0 = broadcast
+void attn_sbias_args(ffk::AttnArgs& a, const Tensor& q, const optional<Tensor>& sbias, int64_t sb, int64_t sh,
+                     int64_t B, int64_t H, int64_t Sq, int64_t Sk) {
+  if (!sbias.has_value() || !sbias->defined()) return;
+  TORCH_CHECK(sbias->scalar_type() == at::kFloat, "attn: the score bias must be fp32");
+  TORCH_CHECK(sbias->device() == q.device(), "attn: the score bias must be on the device of q");
+  TORCH_CHECK(sbias->dim() >= 2 && sbias->size(-1) == Sk && sbias->size(-2) == Sq && sbias->stride(-1) == 1 &&
+                  sbias->stride(-2) == Sk,
+              "attn: the score bias must be [.., Sq, Sk] with contiguous rows (row stride Sk)");
+  TORCH_CHECK(sb >= 0 && sh >= 0, "attn: score bias strides must be >= 0 (0 = broadcast)");
+  const int64_t Bb = sb ? B : 1, Hb = sh ? H : 1;
+  TORCH_CHECK((Bb - 1) * sb + (Hb - 1) * sh + Sq * Sk <= sbias->numel(), "attn: the score bias is too short for its strides");
+  a.sbias = sbias->data_ptr<float>();
+  a.sbias_sb = sb;
+  a.sbias_sh = sh;
+}
+
 // q/k/v/o given with explicit [b,h,s] element strides (d contiguous)
 void attn_fwd(Tensor q, std::vector<int64_t> qs, Tensor k, std::vector<int64_t> ks, Tensor v,
               std::vector<int64_t> vs, Tensor o, std::vector<int64_t> os, Tensor lse, int64_t B, int64_t H,
               int64_t Sq, int64_t Sk, int64_t D, double scale, bool causal, optional<Tensor> key_lens,
-              int64_t drop_thr, optional<Tensor> rng_step, int64_t rng_seed, int64_t b0, int64_t h0, int64_t H_total) {
+              int64_t drop_thr, optional<Tensor> rng_step, int64_t rng_seed, int64_t b0, int64_t h0, int64_t H_total,
+              optional<Tensor> sbias, int64_t sbias_sb, int64_t sbias_sh) {
   TORCH_CHECK(D == 64 || D == 128, "flash attention supports head_dim 64/128");
   TORCH_CHECK(q.scalar_type() == at::kBFloat16 && o.scalar_type() == at::kBFloat16);
   TORCH_CHECK(lse.numel() >= B * H * Sq && lse.scalar_type() == at::kFloat);
@@ -783,6 +820,7 @@ void attn_fwd(Tensor q, std::vector<int64_t> qs, Tensor k, std::vector<int64_t> 
   a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.D = D; a.scale = scale; a.causal = causal;
   a.key_lens = attn_key_lens(key_lens, q, B);
   attn_drop_args(a, q, drop_thr, rng_step, rng_seed, b0, h0, H_total, H);
+  attn_sbias_args(a, q, sbias, sbias_sb, sbias_sh, B, H, Sq, Sk);
   ffk::attn_fwd(a, cur_stream());
 }
 int64_t attn_bwd_ws(int64_t B, int64_t H, int64_t Sq, int64_t Sk, int64_t D) {
@@ -793,7 +831,8 @@ bool attn_bwd(Tensor q, std::vector<int64_t> qs, Tensor k, std::vector<int64_t> 
               Tensor lse, Tensor dq, std::vector<int64_t> dqs, Tensor dk, std::vector<int64_t> dks, Tensor dv,
               std::vector<int64_t> dvs, Tensor ws, int64_t B, int64_t H, int64_t Sq, int64_t Sk, int64_t D,
               double scale, bool causal, optional<Tensor> dbias, optional<Tensor> key_lens, int64_t drop_thr,
-              optional<Tensor> rng_step, int64_t rng_seed, int64_t b0, int64_t h0, int64_t H_total) {
+              optional<Tensor> rng_step, int64_t rng_seed, int64_t b0, int64_t h0, int64_t H_total,
+              optional<Tensor> sbias, int64_t sbias_sb, int64_t sbias_sh) {
   TORCH_CHECK(D == 64 || D == 128, "flash attention supports head_dim 64/128");
   TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.numel() >= ffk::attn_bwd_workspace_floats(B, H, Sq, Sk, D),
               "attn_bwd: workspace too small");
@@ -820,6 +859,7 @@ bool attn_bwd(Tensor q, std::vector<int64_t> qs, Tensor k, std::vector<int64_t> 
   a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.D = D; a.scale = scale; a.causal = causal;
   a.key_lens = attn_key_lens(key_lens, q, B);
   attn_drop_args(a, q, drop_thr, rng_step, rng_seed, b0, h0, H_total, H);
+  attn_sbias_args(a, q, sbias, sbias_sb, sbias_sh, B, H, Sq, Sk);
   return ffk::attn_bwd(a, cur_stream());
 }
 
@@ -1175,6 +1215,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("gemm_f32", &gemm_f32);
   m.def("causal_mask_f32", &causal_mask_f32);
   m.def("key_len_mask_f32", &key_len_mask_f32);
+  m.def("score_bias_f32", &score_bias_f32);
+  m.def("masked_prob_zero_f32", &masked_prob_zero_f32);
   m.def("topk_fwd", &topk_fwd);
   m.def("topk_bwd", &topk_bwd);
   m.def("moe_route_ws_ints", &moe_route_ws_ints);
@@ -1187,14 +1229,15 @@ PYBIND11_MODULE(_C, m) {
         py::arg("o"), py::arg("os"), py::arg("lse"), py::arg("B"), py::arg("H"), py::arg("Sq"), py::arg("Sk"),
         py::arg("D"), py::arg("scale"), py::arg("causal"), py::arg("key_lens") = py::none(),
         py::arg("drop_thr") = 0, py::arg("rng_step") = py::none(), py::arg("rng_seed") = 0, py::arg("b0") = 0,
-        py::arg("h0") = 0, py::arg("H_total") = 0);
+        py::arg("h0") = 0, py::arg("H_total") = 0, py::arg("sbias") = py::none(), py::arg("sbias_sb") = 0,
+        py::arg("sbias_sh") = 0);
   m.def("attn_bwd", &attn_bwd, py::arg("q"), py::arg("qs"), py::arg("k"), py::arg("ks"), py::arg("v"), py::arg("vs"),
         py::arg("o"), py::arg("os"), py::arg("dout"), py::arg("dos"), py::arg("lse"), py::arg("dq"), py::arg("dqs"),
         py::arg("dk"), py::arg("dks"), py::arg("dv"), py::arg("dvs"), py::arg("ws"), py::arg("B"), py::arg("H"),
         py::arg("Sq"), py::arg("Sk"), py::arg("D"), py::arg("scale"), py::arg("causal"),
         py::arg("dbias") = py::none(), py::arg("key_lens") = py::none(), py::arg("drop_thr") = 0,
         py::arg("rng_step") = py::none(), py::arg("rng_seed") = 0, py::arg("b0") = 0, py::arg("h0") = 0,
-        py::arg("H_total") = 0);
+        py::arg("H_total") = 0, py::arg("sbias") = py::none(), py::arg("sbias_sb") = 0, py::arg("sbias_sh") = 0);
   m.def("attn_dropout_f32", &attn_dropout_f32);
   m.def("attn_dropout_mask", &attn_dropout_mask);
   m.def("attn_bwd_ws", &attn_bwd_ws);

@@ -56,6 +56,8 @@ void gemm_f32(const GemmArgs& p, hipStream_t stream);
 // fp32 attention path: -inf above the causal diagonal of [rows][Sk] scores (rows = batch * Sq)
 void causal_mask_f32(float* s, int64_t rows, int Sq, int Sk, hipStream_t st);
 void key_len_mask_f32(float* s, int64_t rows, int Sk, const int* key_len, float value, hipStream_t st);
+void score_bias_f32(float* s, const float* bias, int H, int Sq, int Sk, int64_t bias_sh, float scale, hipStream_t st);
+void masked_prob_zero_f32(float* p, const float* s, int64_t n, hipStream_t st);
 // dgrad GEMM of a consumer Linear fused with the producer Linear's activation backward:
 // C[M,N] bf16 = (A.B) * act'(zin), colpart as above. False when the shape / alignment does not
 // fit the 256-row kernel's coalesced epilogue (the caller then runs GEMM + bias_act_bwd).

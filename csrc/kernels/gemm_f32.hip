@@ -197,4 +197,31 @@ void key_len_mask_f32(float* s, int64_t rows, int Sk, const int* key_len, float 
   hipLaunchKernelGGL(key_len_mask_kernel, dim3(ew_grid(rows * Sk, 256)), dim3(256), 0, st, s, rows, Sk, key_len, value);
 }
 
+// s[h][q][j] = scale * s[h][q][j] + bias[h * bias_sh + q * Sk + j]: the score bias of one sample of
+// the fp32 attention path (its softmax then runs with scale 1). bias_sh = 0 broadcasts over heads.
+__global__ void score_bias_kernel(float* __restrict__ s, const float* __restrict__ bias, int64_t H, int64_t per,
+                                  int64_t bias_sh, float scale) {
+  const int64_t n = H * per;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x)
+    s[e] = scale * s[e] + bias[(e / per) * bias_sh + e % per];
+}
+void score_bias_f32(float* s, const float* bias, int H, int Sq, int Sk, int64_t bias_sh, float scale, hipStream_t st) {
+  const int64_t per = (int64_t)Sq * Sk;
+  if (H <= 0 || per <= 0) return;
+  hipLaunchKernelGGL(score_bias_kernel, dim3(ew_grid(H * per, 256)), dim3(256), 0, st, s, bias, (int64_t)H, per,
+                     bias_sh, scale);
+}
+
+// p[e] = 0 where s[e] == -inf: after the softmax of biased scores this only changes rows whose
+// every score is -inf (their softmax is NaN, as torch's is; such a row's probabilities are defined
+// as 0, the key-length convention)
+__global__ void masked_prob_zero_kernel(float* __restrict__ p, const float* __restrict__ s, int64_t n) {
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x)
+    if (s[e] == -INFINITY) p[e] = 0.f;
+}
+void masked_prob_zero_f32(float* p, const float* s, int64_t n, hipStream_t st) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(masked_prob_zero_kernel, dim3(ew_grid(n, 256)), dim3(256), 0, st, p, s, n);
+}
+
 }  // namespace ffk

@@ -7,7 +7,11 @@ shape by default, `--tiny` for a seconds-long run) and the data is a synthetic c
 the source sequence) in place of the reference's tokenized translation pairs. Inputs are unpadded,
 so attention_mask is all ones (the import folds it; flexflow_amd/torch/export.py).
 
-    python examples/python/pytorch/mt5/mt5_ff.py [--tiny] [-b 8] [-e 1] [--samples 256]
+    python examples/python/pytorch/mt5/mt5_ff.py [--tiny] [--fuse-sdpa] [-b 8] [-e 1] [--samples 256]
+
+--fuse-sdpa maps every attention of the model to one scaled_dot_product_attention op (the flash
+kernels, with T5's relative-position bias and causal mask as their additive score bias) instead of
+batch_matmul / add / softmax / batch_matmul.
 """
 import argparse
 import os
@@ -44,7 +48,7 @@ def synthetic_copy_task(n, src_len, tgt_len, vocab, seed=0):
     return src, dec, tgt.astype(np.int32).reshape(n, tgt_len, 1)
 
 
-def top_level_task(argv, tiny, num_samples, src_len=48, tgt_len=48):
+def top_level_task(argv, tiny, num_samples, src_len=48, tgt_len=48, fuse_sdpa=False):
     from transformers import MT5ForConditionalGeneration
     ffconfig = FFConfig(argv)
     ffmodel = FFModel(ffconfig)
@@ -61,7 +65,7 @@ def top_level_task(argv, tiny, num_samples, src_len=48, tgt_len=48):
     print("Tracing the model...")
     hf_model = PyTorchModel(model, is_hf_model=True,
                             input_names=["input_ids", "attention_mask", "decoder_input_ids"],
-                            batch_size=batch_size, seq_length=(src_len, tgt_len))
+                            batch_size=batch_size, seq_length=(src_len, tgt_len), fuse_sdpa=fuse_sdpa)
     hf_model.torch_to_ff(ffmodel, input_tensors)
     ffoptimizer = SGDOptimizer(ffmodel, lr=0.01)
     print("Compiling the model...")
@@ -82,5 +86,6 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser(add_help=False)
     ap.add_argument("--tiny", action="store_true")
     ap.add_argument("--samples", type=int, default=256)
+    ap.add_argument("--fuse-sdpa", action="store_true")
     args, rest = ap.parse_known_args(sys.argv[1:])
-    top_level_task(rest, args.tiny, args.samples)
+    top_level_task(rest, args.tiny, args.samples, fuse_sdpa=args.fuse_sdpa)

@@ -288,18 +288,41 @@ class FFModel:
 
     def multihead_attention(self, query, key, value, embed_dim, num_heads, kdim=0, vdim=0, dropout=0.0, bias=True,
                             add_bias_kv=False, add_zero_attn=False, kernel_initializer=None, causal=False, name=None,
-                            key_lengths=None):
+                            key_lengths=None, attn_bias=None):
         """key_lengths: optional int32 tensor [batch] (or [batch, 1]) of a right-padded batch: sample b
         attends to its first key_lengths[b] keys only (ops/attention.py).
+        attn_bias: optional float tensor [1|batch, 1|heads, Sq, Sk] added to the scaled scores before the
+        softmax (ALiBi, relative-position biases, 0 / -inf masks); it takes no gradient (ops/attention.py).
         dropout: attention-probability dropout rate in [0, 1), torch's dropout_p semantics; applied in
         training forwards only, at the effective rate round(256 p) / 256 (ops/attention.py)."""
         if not 0.0 <= float(dropout) < 1.0:
             raise ValueError(f"multihead_attention: dropout must be in [0, 1), got {dropout}")
         ins = [query, key, value] + ([key_lengths] if key_lengths is not None else [])
+        kw = {}
+        if attn_bias is not None:  # the last input, marked by the attribute; a graph without it is built as ever
+            ins.append(attn_bias)
+            kw["attn_bias"] = True
         return self._add(OperatorType.OP_MULTIHEAD_ATTENTION, ins, name, embed_dim=int(embed_dim),
                          num_heads=int(num_heads), kdim=int(kdim), vdim=int(vdim), dropout=float(dropout), bias=bias,
                          add_bias_kv=add_bias_kv, add_zero_attn=add_zero_attn, kernel_init=kernel_initializer,
-                         causal=causal, self_attn=(query is key and key is value)).outputs[0]
+                         causal=causal, self_attn=(query is key and key is value), **kw).outputs[0]
+
+    def scaled_dot_product_attention(self, q, k, v, attn_bias=None, key_lengths=None, scale=None, causal=False,
+                                     dropout=0.0, name=None):
+        """softmax(scale * q.k^T + attn_bias) . v on projected heads: q [B, H, Sq, D], k [B, H, Sk, D],
+        v [B, H, Sk, Dv] -> [B, H, Sq, Dv] (extension; ops/sdpa.py). attn_bias, key_lengths, causal and
+        dropout are those of multihead_attention; scale=None means 1 / sqrt(D)."""
+        if not 0.0 <= float(dropout) < 1.0:
+            raise ValueError(f"scaled_dot_product_attention: dropout must be in [0, 1), got {dropout}")
+        ins, kw = [q, k, v], {}
+        if key_lengths is not None:
+            ins.append(key_lengths)
+            kw["key_lengths"] = True
+        if attn_bias is not None:
+            ins.append(attn_bias)
+            kw["attn_bias"] = True
+        return self._add(OperatorType.OP_SDPA, ins, name, scale=None if scale is None else float(scale),
+                         causal=bool(causal), dropout=float(dropout), **kw).outputs[0]
 
     # ---- shape ops
     def concat(self, tensors, axis, name=None):

@@ -1046,21 +1046,50 @@ def _drop_kw(drop):
                 H_total=int(H_total))
 
 
-def flash_attn_fwd(q, qs, k, ks, v, vs, o, os_, B, H, Sq, Sk, D, scale, causal, key_lens=None, drop=None):
+def attn_score_bias(bias, B, H, Sq, Sk, device):
+    """The additive score bias as the kernels take it: fp32 [Bb, Hb, Sq, Sk] with Bb in {1, B} and Hb in
+    {1, H}, contiguous, on `device` (cast / copied once here when it is not), or None. Scores are
+    scale * q.k + bias; -inf (or anything so negative that bias * log2(e) overflows fp32, such as
+    finfo.min) removes the key, a row with no key left gives zero output and zero gradients. The bias
+    takes no gradient."""
+    if bias is None:
+        return None
+    if bias.dim() != 4 or bias.shape[0] not in (1, B) or bias.shape[1] not in (1, H) or \
+            tuple(bias.shape[2:]) != (Sq, Sk):
+        raise ValueError(f"attention score bias: expected [1|{B}, 1|{H}, {Sq}, {Sk}], got {list(bias.shape)}")
+    if not bias.is_floating_point():
+        raise ValueError(f"attention score bias must be a float tensor, got {bias.dtype}")
+    if bias.dtype != torch.float32 or bias.device != device or not bias.is_contiguous():
+        bias = bias.to(device=device, dtype=torch.float32).contiguous()
+    return bias
+
+
+def _sbias_kw(bias, B, H, Sq, Sk, device):
+    """bias (attn_score_bias) -> the bindings' keyword arguments; a dim of extent 1 broadcasts (stride 0)."""
+    bias = attn_score_bias(bias, B, H, Sq, Sk, device)
+    if bias is None:
+        return {}
+    Bb, Hb = bias.shape[:2]
+    return dict(sbias=bias, sbias_sb=Hb * Sq * Sk if Bb > 1 else 0, sbias_sh=Sq * Sk if Hb > 1 else 0)
+
+
+def flash_attn_fwd(q, qs, k, ks, v, vs, o, os_, B, H, Sq, Sk, D, scale, causal, key_lens=None, drop=None, bias=None):
     """key_lens: optional int32 [B] device tensor; key j of sample b is attended iff j < key_lens[b]
     (a length of 0: o = 0, lse = +inf). drop: optional attention dropout (thr, rng_step, rng_seed, b0,
-    h0, H_total), see _drop_kw / attn_dropout_keep_ref; lse is that of the undropped softmax."""
+    h0, H_total), see _drop_kw / attn_dropout_keep_ref; lse is that of the undropped softmax.
+    bias: optional score bias [1|B, 1|H, Sq, Sk] (attn_score_bias)."""
     lse = torch.empty(B * H * Sq, device=q.device, dtype=torch.float32)
     ext().attn_fwd(q, qs, k, ks, v, vs, o, os_, lse, B, H, Sq, Sk, D, scale, causal,
-                   attn_key_lens(key_lens, B, q.device), **_drop_kw(drop))
+                   attn_key_lens(key_lens, B, q.device), **_drop_kw(drop), **_sbias_kw(bias, B, H, Sq, Sk, q.device))
     return lse
 
 
 def flash_attn_bwd(q, qs, k, ks, v, vs, o, os_, do, dos, lse, dq, dqs, dk, dks, dv, dvs, B, H, Sq, Sk, D, scale,
-                   causal, dbias=None, key_lens=None, drop=None):
+                   causal, dbias=None, key_lens=None, drop=None, bias=None):
     """key_lens: as in flash_attn_fwd; dk / dv rows at or past a sample's length are written as zeros.
     drop: as in flash_attn_fwd, with the counter value the forward saw; the dropout kernels never fuse
-    the bias gradient (returns False).
+    the bias gradient (returns False). bias: the forward's score bias; it takes no gradient, and the
+    score bias kernels never fuse the (QKV projection's) bias gradient either.
     dbias: optional contiguous fp32 [3*H*D] bias gradient of a fused [B,S,3,H,D] QKV projection
     (dq/dk/dv inside one dqkv buffer). Returns True when the kernel added the column sums of dq / dk /
     dv into it (attn_bwd1b_kernel, non-causal); False: the caller still owes that bias gradient."""
@@ -1069,7 +1098,8 @@ def flash_attn_bwd(q, qs, k, ks, v, vs, o, os_, do, dos, lse, dq, dqs, dk, dks, 
     # dQ partial slabs + delta: one arena buffer shared (stream-ordered) by every attention layer
     ws = DeviceContext.get(q.device).workspace("attn_bwd", X.attn_bwd_ws(B, H, Sq, Sk, D))
     return bool(X.attn_bwd(q, qs, k, ks, v, vs, o, os_, do, dos, lse, dq, dqs, dk, dks, dv, dvs, ws, B, H, Sq, Sk, D,
-                           scale, causal, dbias, attn_key_lens(key_lens, B, q.device), **_drop_kw(drop)))
+                           scale, causal, dbias, attn_key_lens(key_lens, B, q.device), **_drop_kw(drop),
+                           **_sbias_kw(bias, B, H, Sq, Sk, q.device)))
 
 
 # ---------------------------------------------------------------------------- layer norm
@@ -2303,16 +2333,23 @@ def attn_f32_supported(x) -> bool:
     return native(x) and x.dtype == torch.float32
 
 
-def attn_f32_fwd(q, qs, k, ks, v, vs, o, os_, B, H, Sq, Sk, kd, vd, scale, causal, key_lens=None, drop=None):
+def attn_f32_fwd(q, qs, k, ks, v, vs, o, os_, B, H, Sq, Sk, kd, vd, scale, causal, key_lens=None, drop=None,
+                 bias=None):
     """fp32 attention on our kernels, per sample: S = Q.K^T (f32 MFMA GEMM, heads as the batch),
     causal mask, key-length mask (key_lens: int32 [B] on the device, columns >= key_lens[b] set to
     -inf there), row softmax(scale * S) (softmax.hip), the same columns of P set to 0 (a sample of
     length 0 has P = 0, not the softmax's NaN), O = P.V. q/k/v/o are flat views with [b, h, row] element strides (qs, ks, vs, os_) and contiguous head dims.
     drop (as in flash_attn_fwd): the PV GEMM takes keep ? P / (1 - p_eff) : 0 (attn_dropout_f32 on P[b]);
     the P returned is the undropped one, for softmax_bwd.
+    bias (attn_score_bias): S = scale * S + bias[b] (score_bias_f32) ahead of the masks, the softmax then
+    runs with scale 1; P is set to 0 where S is -inf, so a row with no key left has P = 0.
     Returns P [B, H, Sq, Sk]."""
     X = ext()
     dkw = _drop_kw(drop)
+    bias = attn_score_bias(bias, B, H, Sq, Sk, q.device)
+    if bias is not None:
+        bflat, bsb = bias.reshape(-1), (bias.shape[1] * Sq * Sk if bias.shape[0] > 1 else 0)
+        bsh = Sq * Sk if bias.shape[1] > 1 else 0
     Pd = torch.empty(H, Sq, Sk, device=q.device, dtype=torch.float32) if dkw else None
     key_lens = attn_key_lens(key_lens, B, q.device)
     q, k, v, o = q.reshape(-1), k.reshape(-1), v.reshape(-1), o.reshape(-1)
@@ -2321,11 +2358,15 @@ def attn_f32_fwd(q, qs, k, ks, v, vs, o, os_, B, H, Sq, Sk, kd, vd, scale, causa
     for b in range(B):
         X.gemm_f32(q[b * qs[0]:], k[b * ks[0]:], S, None, None, Sq, Sk, kd, qs[2], ks[2], Sk, qs[1], ks[1], Sq * Sk,
                    H, True, True, 1.0, 0.0, ACT_NONE)
+        if bias is not None:
+            X.score_bias_f32(S, bflat[b * bsb:], H, Sq, Sk, bsh, scale)
         if causal:
             X.causal_mask_f32(S, Sq, Sk)
         if key_lens is not None:
             X.key_len_mask_f32(S, key_lens, b, Sk, float("-inf"))
-        X.softmax_fwd(S, P[b], H * Sq, Sk, scale)
+        X.softmax_fwd(S, P[b], H * Sq, Sk, 1.0 if bias is not None else scale)
+        if bias is not None:
+            X.masked_prob_zero_f32(P[b], S)
         if key_lens is not None:  # a sample without keys: its all -inf rows came out NaN, P is 0 there
             X.key_len_mask_f32(P[b], key_lens, b, Sk, 0.0)
         Pb = P[b]
@@ -2338,12 +2379,15 @@ def attn_f32_fwd(q, qs, k, ks, v, vs, o, os_, B, H, Sq, Sk, kd, vd, scale, causa
     return P
 
 
-def attn_f32_bwd(q, qs, k, ks, v, vs, do, dos, P, dq, dk, dv, B, H, Sq, Sk, kd, vd, scale, key_lens=None, drop=None):
+def attn_f32_bwd(q, qs, k, ks, v, vs, do, dos, P, dq, dk, dv, B, H, Sq, Sk, kd, vd, scale, key_lens=None, drop=None,
+                 bias=None):
     """Backward of attn_f32_fwd: dP = dO.V^T, dS = scale * P * (dP - rowsum(dP * P)), dQ = dS.K,
     dK = dS^T.Q, dV = P^T.dO (dq / dk / dv share q / k / v's strides). key_lens needs no work here:
     the forward left P = 0 in the masked columns, so dS is 0 there and the dK / dV rows at or past a
     sample's length come out as zeros (all of a length-0 sample's gradients do). drop (with the
-    counter value of the forward): dP and the P of the dV GEMM go through attn_dropout_f32."""
+    counter value of the forward): dP and the P of the dV GEMM go through attn_dropout_f32. bias needs
+    no work either: it is inside P, dS = scale * P * (..) stays the gradient of the raw q.k, and the
+    bias itself takes no gradient."""
     X = ext()
     dkw = _drop_kw(drop)
     Pd = torch.empty(H, Sq, Sk, device=q.device, dtype=torch.float32) if dkw else None

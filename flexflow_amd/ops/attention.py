@@ -17,7 +17,19 @@ iff j < L_b (and j <= q with `causal`). Every query row is still computed (as wi
 key_padding_mask); L_b = 0 gives zero output rows and zero gradients. The lengths are read on the
 device only, by every path (flash, zero-padded head dims, fp32 device, reference, CPU), so a step
 that takes them still captures into a graph. The pad positions' labels are left out of the loss by
-`FFModel.compile(ignore_index=...)`. Not covered: arbitrary masks, query-side skipping or packing.
+`FFModel.compile(ignore_index=...)`. Not covered: query-side skipping or packing.
+
+Optional last input `attn_bias` (attribute `attn_bias=True`; after `key_lengths` when both are given):
+a float tensor [1|B, 1|H, Sq, Sk] added to the scaled scores before the softmax, in every path — ALiBi,
+relative-position biases, sliding windows, left padding or block masks as 0 / -inf. The flash kernels
+read it as fp32 (cast once per forward when it is not) while they compute the scores, so no [B, H,
+Sq, Sk] tensor is built. An element of -inf, or one so negative that bias * log2(e) overflows fp32
+(HuggingFace's finfo.min masks), removes that key; a query row with no key left gives a zero output
+row and zero gradients (the key-length convention; torch gives NaN). +inf and NaN are the caller's
+problem. The bias takes no gradient, and with it the flash backward leaves the QKV bias gradient to
+the projection's own backward. It is sharded with the batch where its first extent is B and with the
+heads where its second is H, replicated elsewhere. The same core (attn_core_fwd / attn_core_bwd) serves
+`scaled_dot_product_attention` (ops/sdpa.py).
 
 Attention dropout (`dropout` = p in [0, 1), torch's `dropout_p`): in a training forward every
 attention probability is dropped with the effective rate p_eff = round(256 p) / 256 and the kept ones
@@ -51,16 +63,28 @@ def _pad_heads(t, st, B, S, H, d, Dp):
     return out
 
 
-def _attn_ref(q, k, v, scale, causal, key_lens=None, keep=None, keep_scale=1.0):
+def _attn_ref(q, k, v, scale, causal, key_lens=None, keep=None, keep_scale=1.0, bias=None):
     """keep: optional bool [B, H, Sq, Sk] attention dropout mask (kernels.attn_dropout_keep_ref), the
-    kept probabilities scaled by keep_scale = 1 / (1 - p_eff)."""
+    kept probabilities scaled by keep_scale = 1 / (1 - p_eff). bias: optional score bias [1|B, 1|H, Sq,
+    Sk], added to the scaled scores; a query row it leaves no key gets P = 0 (not the softmax's NaN)."""
     def drop(p):
         return p if keep is None else torch.where(keep, p * keep_scale, torch.zeros_like(p))
 
     s = torch.einsum("bhqd,bhkd->bhqk", q, k) * scale
     Sq, Sk = s.shape[-2:]
+    if bias is not None:
+        s = s + bias.to(device=s.device, dtype=s.dtype)
     if causal:
         s = s.masked_fill(torch.ones(Sq, Sk, dtype=torch.bool, device=s.device).triu(1), float("-inf"))
+    if bias is not None:
+        # the kernels' convention for every removed key and every row without keys, lengths included
+        if key_lens is not None:
+            L = key_lens.reshape(-1).to(s.device).clamp(0, Sk)
+            s = s.masked_fill((torch.arange(Sk, device=s.device)[None, :] >= L[:, None])[:, None, None, :], float("-inf"))
+        dead = (s == float("-inf")).all(-1, keepdim=True)
+        s = torch.where(dead, torch.zeros_like(s), s)
+        p = torch.where(dead, torch.zeros_like(s), torch.softmax(s, -1))
+        return torch.einsum("bhqk,bhkd->bhqd", drop(p), v)
     if key_lens is None:
         return torch.einsum("bhqk,bhkd->bhqd", drop(torch.softmax(s, -1)), v)
     # keys at or past the sample's length leave the softmax; a sample without keys gets P = 0 (its
@@ -75,19 +99,148 @@ def _attn_ref(q, k, v, scale, causal, key_lens=None, keep=None, keep_scale=1.0):
     return torch.einsum("bhqk,bhkd->bhqd", drop(p), v)
 
 
+def _view4(t, st, B, H, S, d):
+    """[B, H, S, d] view of a flat / strided buffer with (batch, head, row) element strides st."""
+    return t.as_strided((B, H, S, d), (st[0], st[1], st[2], 1))
+
+
+def attn_core_fwd(s, name, qv, qs, kv, ks, vv, vs, o, os_, B, Hl, Sq, Sk, kd, vd, scale, causal, kl, drop, bias, keep_ref):
+    """softmax(scale q.k + bias, masks) v of MultiHeadAttention and ScaledDotProductAttention: q / k / v
+    / o are buffers read and written through their (batch, head, row) element strides qs / ks / vs /
+    os_ with contiguous head dims. Picks the path (flash kernels, head dims zero-padded to 64 / 128,
+    fp32 device kernels, fp32 PyTorch reference / CPU) and leaves in `s` what attn_core_bwd needs of
+    it. kl: key lengths (kernels.attn_key_lens) or None; drop: attention dropout as the kernels take it
+    or None; bias: score bias (kernels.attn_score_bias) or None; keep_ref(): the dropout mask for the
+    reference path."""
+    if K.attn_supported(qv, kd) and kd == vd:
+        s["lse"] = K.flash_attn_fwd(qv, qs, kv, ks, vv, vs, o, os_, B, Hl, Sq, Sk, kd, scale, causal, key_lens=kl,
+                                    drop=drop, bias=bias)
+    elif K.attn_padded_dim(qv, kd, vd):
+        # head dims the MFMA kernels have no instance for (e.g. 16, 32, 80, 96): zero-pad Q, K,
+        # V to the next instance (64 / 128). Zero columns add nothing to Q.K^T and give zero
+        # output columns, so the softmax and the sliced output are exact; the scale is the caller's
+        Dp = K.attn_padded_dim(qv, kd, vd)
+        pq, pk, pv = (_pad_heads(t, st, Bq, S_, Hl, kd, Dp) for t, st, Bq, S_ in
+                      ((qv, qs, B, Sq), (kv, ks, B, Sk), (vv, vs, B, Sk)))
+        po = torch.empty(B, Sq, Hl, Dp, device=qv.device, dtype=qv.dtype)
+        pst = [Sq * Hl * Dp, Dp, Hl * Dp]
+        kst = [Sk * Hl * Dp, Dp, Hl * Dp]
+        lse = K.flash_attn_fwd(pq, pst, pk, kst, pv, kst, po, pst, B, Hl, Sq, Sk, Dp, scale, causal, key_lens=kl,
+                               drop=drop, bias=bias)
+        _view4(o, os_, B, Hl, Sq, vd).copy_(po[..., :vd].permute(0, 2, 1, 3))
+        s.update(lse=lse, pad=(Dp, pq, pk, pv, po))
+    elif K.attn_f32_supported(qv) and os.environ.get("FF_ATTN_REF_FALLBACK") != "1":
+        # --dtype fp32 on the device: f32 MFMA GEMMs + causal mask + row softmax, our kernels
+        s["P"] = K.attn_f32_fwd(qv, qs, kv, ks, vv, vs, o.view(-1), os_, B, Hl, Sq, Sk, kd, vd, scale, causal,
+                                key_lens=kl, drop=drop, bias=bias)
+    else:
+        if K.native(qv) and qv.dtype == torch.bfloat16 and os.environ.get("FF_ATTN_REF_FALLBACK") != "1":
+            raise NotImplementedError(
+                f"{name}: no MFMA attention kernel for head dims q/k {kd}, v {vd} (supported: equal "
+                "q/k/v head dims up to 128; FF_ATTN_REF_FALLBACK=1 runs the fp32 PyTorch reference instead)")
+        q4 = _view4(qv, qs, B, Hl, Sq, kd).float()
+        k4 = _view4(kv, ks, B, Hl, Sk, kd).float()
+        v4 = _view4(vv, vs, B, Hl, Sk, vd).float()
+        keep = keep_ref() if drop else None
+        if keep is not None:
+            s["keep"] = keep
+        _view4(o, os_, B, Hl, Sq, vd).copy_(
+            _attn_ref(q4, k4, v4, scale, causal, kl, keep, 256.0 / (256 - drop[0]) if drop else 1.0, bias))
+
+
+def attn_core_bwd(s, qv, qs, kv, ks, vv, vs, o, os_, do, dos, dq, dk, dv, B, Hl, Sq, Sk, kd, vd, scale, causal, kl, drop,
+                  bias, dbq=None):
+    """Backward of attn_core_fwd on the path it took: dq / dk / dv (buffers with q / k / v's strides)
+    from do (strides dos) and what the forward left in `s`. dbq: the fp32 [3*H*D] bias gradient of a fused
+    QKV projection the flash kernel may add into; returns whether it did."""
+    if "pad" in s:
+        Dp, pq, pk, pv, po = s["pad"]
+        pdo = torch.zeros_like(po)
+        pdo[..., :vd] = _view4(do, dos, B, Hl, Sq, vd).permute(0, 2, 1, 3)
+        pdq, pdk, pdv = torch.empty_like(pq), torch.empty_like(pk), torch.empty_like(pv)
+        pst = [Sq * Hl * Dp, Dp, Hl * Dp]
+        kst = [Sk * Hl * Dp, Dp, Hl * Dp]
+        K.flash_attn_bwd(pq, pst, pk, kst, pv, kst, po, pst, pdo, pst, s["lse"], pdq, pst, pdk, kst, pdv, kst,
+                         B, Hl, Sq, Sk, Dp, scale, causal, key_lens=kl, drop=drop, bias=bias)
+        for g, st, pg, S_, d in ((dq, qs, pdq, Sq, kd), (dk, ks, pdk, Sk, kd), (dv, vs, pdv, Sk, vd)):
+            _view4(g, st, B, Hl, S_, d).copy_(pg[..., :d].permute(0, 2, 1, 3))
+    elif "lse" in s:
+        if dbq is not None:
+            return K.flash_attn_bwd(qv, qs, kv, ks, vv, vs, o, os_, do, dos, s["lse"], dq, qs, dk, ks, dv, vs,
+                                    B, Hl, Sq, Sk, kd, scale, causal, dbias=dbq, key_lens=kl, drop=drop, bias=bias)
+        K.flash_attn_bwd(qv, qs, kv, ks, vv, vs, o, os_, do, dos, s["lse"], dq, qs, dk, ks, dv, vs,
+                         B, Hl, Sq, Sk, kd, scale, causal, key_lens=kl, drop=drop, bias=bias)
+    elif "P" in s:
+        K.attn_f32_bwd(qv, qs, kv, ks, vv, vs, do.contiguous().view(-1), dos, s["P"], dq.view(-1), dk.view(-1),
+                       dv.view(-1), B, Hl, Sq, Sk, kd, vd, scale, key_lens=kl, drop=drop, bias=bias)
+    else:
+        q4 = _view4(qv, qs, B, Hl, Sq, kd).detach().float().requires_grad_()
+        k4 = _view4(kv, ks, B, Hl, Sk, kd).detach().float().requires_grad_()
+        v4 = _view4(vv, vs, B, Hl, Sk, vd).detach().float().requires_grad_()
+        with torch.enable_grad():
+            out = _attn_ref(q4, k4, v4, scale, causal, kl, s.get("keep"), 256.0 / (256 - drop[0]) if drop else 1.0, bias)
+        g4 = _view4(do, dos, B, Hl, Sq, vd).float()
+        gq, gk, gv = torch.autograd.grad(out, (q4, k4, v4), g4)
+        _view4(dq, qs, B, Hl, Sq, kd).copy_(gq)
+        _view4(dk, ks, B, Hl, Sk, kd).copy_(gk)
+        _view4(dv, vs, B, Hl, Sk, vd).copy_(gv)
+    return False
+
+
+def attn_drop_args(impl, ctx, B, Hl, h_axis, H_total, device):
+    """Attention dropout of this training forward as the kernels take it: (thr, rng_step, rng_seed,
+    b0, h0, H_total) with the shard's first global batch / head index, or None."""
+    thr = K.attn_dropout_thr(impl.attrs.get("dropout", 0.0))
+    if not (ctx.training and thr):
+        return None
+    step = ctx.rng_step
+    if step is None or step.device != device:  # no executor (cost model, op-level tests): step 0
+        step = ctx.extra.get("rng_step0")
+        if step is None or step.device != device:
+            step = ctx.extra["rng_step0"] = torch.zeros(1, dtype=torch.int64, device=device)
+    seed = K.attn_dropout_seed(ctx.seed, zlib.crc32(impl.layer.name.encode()))
+    return (thr, step, seed, ctx.coord(0) * B, ctx.coord(h_axis) * Hl, int(H_total))
+
+
+def attn_keep_ref(impl, ctx, drop, B, Hl, Sq, Sk, device):
+    """The mirror's mask for the reference / CPU path (the same one the kernels draw)."""
+    thr, step, _, b0, h0, H_total = drop
+    return K.attn_dropout_keep_ref(ctx.seed, zlib.crc32(impl.layer.name.encode()), step, B, Hl, Sq, Sk,
+                                   thr / 256.0, b0=b0, h0=h0, H_total=H_total, device=device)
+
+
+def check_attn_bias_dims(what, dims, B, H, Sq, Sk):
+    d = tuple(dims)
+    if len(d) != 4 or d[0] not in (1, B) or d[1] not in (1, H) or d[2:] != (Sq, Sk):
+        raise ValueError(f"{what}: attn_bias must have shape [1|{B}, 1|{H}, {Sq}, {Sk}], got {list(d)}")
+
+
+def attn_bias_map(dims, B, H, batch_axis, heads_axis):
+    """input_maps entry of a score bias: with the batch where its first extent is B, with the heads
+    where its second is H, replicated elsewhere."""
+    return (batch_axis if dims[0] == B else None, heads_axis if dims[1] == H else None, None, None)
+
+
 @register(OperatorType.OP_MULTIHEAD_ATTENTION)
 class MultiHeadAttention(OpImpl):
     op_type = OperatorType.OP_MULTIHEAD_ATTENTION
 
     @classmethod
     def infer(cls, attrs, in_dims, in_dtypes):
-        if len(in_dims) not in (3, 4):
-            raise ValueError(f"multihead_attention takes query, key, value[, key_lengths]; got {len(in_dims)} inputs")
+        nb = 1 if attrs.get("attn_bias") else 0
+        if len(in_dims) - nb not in (3, 4):
+            raise ValueError("multihead_attention takes query, key, value[, key_lengths][, attn_bias]; got "
+                             f"{len(in_dims)} inputs" + (" with attn_bias=True" if nb else ""))
         q, k, v = in_dims[:3]
-        if len(in_dims) == 4:
+        if len(in_dims) - nb == 4:
             kl = tuple(in_dims[3])
             if kl not in ((q[0],), (q[0], 1)):
                 raise ValueError(f"key_lengths must have shape [{q[0]}] or [{q[0]}, 1], got {list(kl)}")
+        if nb:
+            from ..type import DataType
+            check_attn_bias_dims("multihead_attention", in_dims[-1], q[0], attrs["num_heads"], q[1], k[1])
+            if in_dtypes[-1] not in (DataType.DT_FLOAT, DataType.DT_BF16, DataType.DT_HALF, DataType.DT_DOUBLE):
+                raise ValueError(f"multihead_attention: attn_bias must be a float tensor, got {in_dtypes[-1]}")
         K.attn_dropout_thr(attrs.get("dropout", 0.0))  # ValueError outside [0, 1)
         H = attrs["num_heads"]
         E = attrs["embed_dim"]
@@ -130,9 +283,15 @@ class MultiHeadAttention(OpImpl):
 
     def input_maps(self):
         maps = [(0, 1, None), (0, None, None), (0, None, None)]
-        if len(self.layer.inputs) > 3:  # key lengths: sharded with the batch, replicated over the heads axis
+        if self._has_key_lens():  # key lengths: sharded with the batch, replicated over the heads axis
             maps.append((0,) + (None,) * (len(self.layer.inputs[3].dims) - 1))
+        if self.attrs.get("attn_bias"):
+            maps.append(attn_bias_map(self.layer.inputs[-1].dims, self.layer.inputs[0].dims[0],
+                                      self.attrs["num_heads"], 0, self.H_AXIS))
         return maps
+
+    def _has_key_lens(self):
+        return len(self.layer.inputs) - (1 if self.attrs.get("attn_bias") else 0) > 3
 
     def needs_input_grad(self, i):
         return i < 3
@@ -164,30 +323,17 @@ class MultiHeadAttention(OpImpl):
         return K.attn_dropout_thr(self.attrs.get("dropout", 0.0)) > 0
 
     def _drop(self, ctx, B, Hl, device):
-        """Attention dropout of this training forward as the kernels take it: (thr, rng_step, rng_seed,
-        b0, h0, H_total) with the shard's first global batch / head index, or None."""
-        thr = K.attn_dropout_thr(self.attrs.get("dropout", 0.0))
-        if not (ctx.training and thr):
-            return None
-        step = ctx.rng_step
-        if step is None or step.device != device:  # no executor (cost model, op-level tests): step 0
-            step = ctx.extra.get("rng_step0")
-            if step is None or step.device != device:
-                step = ctx.extra["rng_step0"] = torch.zeros(1, dtype=torch.int64, device=device)
-        seed = K.attn_dropout_seed(ctx.seed, zlib.crc32(self.layer.name.encode()))
-        return (thr, step, seed, ctx.coord(0) * B, ctx.coord(self.H_AXIS) * Hl, int(self.attrs["num_heads"]))
+        return attn_drop_args(self, ctx, B, Hl, self.H_AXIS, self.attrs["num_heads"], device)
 
     def _keep_ref(self, ctx, drop, B, Hl, Sq, Sk, device):
-        """The mirror's mask for the reference / CPU path (the same one the kernels draw)."""
-        thr, step, _, b0, h0, H_total = drop
-        return K.attn_dropout_keep_ref(ctx.seed, zlib.crc32(self.layer.name.encode()), step, B, Hl, Sq, Sk,
-                                       thr / 256.0, b0=b0, h0=h0, H_total=H_total, device=device)
+        return attn_keep_ref(self, ctx, drop, B, Hl, Sq, Sk, device)
 
     def forward(self, ctx, xs, ws):
         q_in, k_in, v_in = xs[:3]
         W = self._w(ws)
         B, Sq, _ = q_in.shape
-        kl = K.attn_key_lens(xs[3], B, q_in.device) if len(xs) > 3 else None
+        has_bias = bool(self.attrs.get("attn_bias"))
+        kl = K.attn_key_lens(xs[3], B, q_in.device) if len(xs) - has_bias > 3 else None
         Sk = k_in.shape[1]
         kd, vd = self.attrs["kdim"], self.attrs["vdim"]
         Hl = W["o_weight"].shape[1]
@@ -227,42 +373,9 @@ class MultiHeadAttention(OpImpl):
             s.update(q=qv, k=kv, v=vv)
         o = torch.empty(B, Sq, Hl, vd, device=q_in.device, dtype=q_in.dtype)
         os_ = [Sq * Hl * vd, vd, Hl * vd]
-        if K.attn_supported(q_in, kd) and kd == vd:
-            lse = K.flash_attn_fwd(qv, qs, kv, ks, vv, vs, o, os_, B, Hl, Sq, Sk, kd, scale, causal, key_lens=kl,
-                                   drop=drop)
-            s["lse"] = lse
-        elif K.attn_padded_dim(q_in, kd, vd):
-            # head dims the MFMA kernels have no instance for (e.g. 16, 32, 80, 96): zero-pad Q, K,
-            # V to the next instance (64 / 128). Zero columns add nothing to Q.K^T and give zero
-            # output columns, so the softmax and the sliced output are exact; the scale stays
-            # 1/sqrt(kd)
-            Dp = K.attn_padded_dim(q_in, kd, vd)
-            pq, pk, pv = (_pad_heads(t, st, Bq, S_, Hl, kd, Dp) for t, st, Bq, S_ in
-                          ((qv, qs, B, Sq), (kv, ks, B, Sk), (vv, vs, B, Sk)))
-            po = torch.empty(B, Sq, Hl, Dp, device=q_in.device, dtype=q_in.dtype)
-            pst = [Sq * Hl * Dp, Dp, Hl * Dp]
-            kst = [Sk * Hl * Dp, Dp, Hl * Dp]
-            lse = K.flash_attn_fwd(pq, pst, pk, kst, pv, kst, po, pst, B, Hl, Sq, Sk, Dp, scale, causal, key_lens=kl,
-                                   drop=drop)
-            o.copy_(po[..., :vd])
-            s.update(lse=lse, pad=(Dp, pq, pk, pv, po))
-        elif K.attn_f32_supported(q_in) and os.environ.get("FF_ATTN_REF_FALLBACK") != "1":
-            # --dtype fp32 on the device: f32 MFMA GEMMs + causal mask + row softmax, our kernels
-            s["P"] = K.attn_f32_fwd(qv, qs, kv, ks, vv, vs, o.view(-1), os_, B, Hl, Sq, Sk, kd, vd, scale, causal,
-                                    key_lens=kl, drop=drop)
-        else:
-            if K.native(q_in) and q_in.dtype == torch.bfloat16 and os.environ.get("FF_ATTN_REF_FALLBACK") != "1":
-                raise NotImplementedError(
-                    f"{self.layer.name}: no MFMA attention kernel for head dims q/k {kd}, v {vd} (supported: equal "
-                    "q/k/v head dims up to 128; FF_ATTN_REF_FALLBACK=1 runs the fp32 PyTorch reference instead)")
-            q4 = qv.as_strided((B, Hl, Sq, kd), (qs[0], qs[1], qs[2], 1)).float()
-            k4 = kv.as_strided((B, Hl, Sk, kd), (ks[0], ks[1], ks[2], 1)).float()
-            v4 = vv.as_strided((B, Hl, Sk, vd), (vs[0], vs[1], vs[2], 1)).float()
-            keep = self._keep_ref(ctx, drop, B, Hl, Sq, Sk, q_in.device) if drop else None
-            if keep is not None:
-                s["keep"] = keep
-            o.copy_(_attn_ref(q4, k4, v4, scale, causal, kl, keep, 256.0 / (256 - drop[0]) if drop else 1.0)
-                    .permute(0, 2, 1, 3))
+        bias = K.attn_score_bias(xs[-1], B, Hl, Sq, Sk, q_in.device) if has_bias else None
+        attn_core_fwd(s, self.layer.name, qv, qs, kv, ks, vv, vs, o, os_, B, Hl, Sq, Sk, kd, vd, scale, causal, kl, drop,
+                      bias, lambda: self._keep_ref(ctx, drop, B, Hl, Sq, Sk, q_in.device))
         o2 = o.view(B * Sq, Hl * vd)
         wo = W["o_weight"].reshape(E, Hl * vd)
         if ctx.training:
@@ -270,7 +383,7 @@ class MultiHeadAttention(OpImpl):
         y, _ = K.linear_fwd(o2, wo, bo, K.ACT_NONE, False)
         if ctx.training:
             s.update(o=o, wo=wo, has_bo=bo is not None, shape=(B, Sq, Sk, Hl, kd, vd, E), fused=fused,
-                     qs=qs, ks=ks, vs=vs, os=os_, scale=scale, causal=causal, key_lens=kl, drop=drop)
+                     qs=qs, ks=ks, vs=vs, os=os_, scale=scale, causal=causal, key_lens=kl, drop=drop, sbias=bias)
         return [y.view(B, Sq, E)]
 
     def overwrites_wgrad(self, i):
@@ -298,8 +411,7 @@ class MultiHeadAttention(OpImpl):
         fused = s["fused"]
         kl = s["key_lens"]
         drop = s["drop"]  # the counter is read on the device again: the next forward advances it, not this backward
-        no_kl_grad = [None] * (len(self.layer.inputs) - 3)  # the lengths take no gradient
-        bias_done = False
+        no_kl_grad = [None] * (len(self.layer.inputs) - 3)  # the lengths and the score bias take no gradient
         if fused:
             qkv = s["qkv"]
             qv, kv, vv = qkv.view(-1), qkv.view(-1)[Hl * kd:], qkv.view(-1)[2 * Hl * kd:]
@@ -308,42 +420,13 @@ class MultiHeadAttention(OpImpl):
         else:
             qv, kv, vv = s["q"], s["k"], s["v"]
             dq, dk, dv = torch.empty_like(qv), torch.empty_like(kv), torch.empty_like(vv)
-        if "pad" in s:
-            Dp, pq, pk, pv, po = s["pad"]
-            pdo = torch.zeros_like(po)
-            pdo[..., :vd] = do
-            pdq, pdk, pdv = torch.empty_like(pq), torch.empty_like(pk), torch.empty_like(pv)
-            pst = [Sq * Hl * Dp, Dp, Hl * Dp]
-            kst = [Sk * Hl * Dp, Dp, Hl * Dp]
-            K.flash_attn_bwd(pq, pst, pk, kst, pv, kst, po, pst, pdo, pst, s["lse"], pdq, pst, pdk, kst, pdv, kst,
-                             B, Hl, Sq, Sk, Dp, scale, causal, key_lens=kl, drop=drop)
-            for g, st, pg, S_, d in ((dq, qs, pdq, Sq, kd), (dk, ks, pdk, Sk, kd), (dv, vs, pdv, Sk, vd)):
-                g.as_strided((B, Hl, S_, d), (st[0], st[1], st[2], 1)).copy_(pg[..., :d].permute(0, 2, 1, 3))
-        elif "lse" in s:
-            # fused projection: the kernel can add the QKV bias gradient (column sums of dq / dk / dv)
-            # itself, sparing linear_bwd a pass over dqkv (bias_act_bwd + fold)
-            dbq = gw("qkv_bias") if (fused and os.environ.get("FF_ATTN_BIAS_FUSION", "1") == "1") else None
-            if dbq is not None and dbq.dtype == torch.float32 and dbq.is_contiguous():
-                bias_done = K.flash_attn_bwd(qv, qs, kv, ks, vv, vs, o, os_, do, os_, s["lse"], dq, qs, dk, ks, dv, vs,
-                                             B, Hl, Sq, Sk, kd, scale, causal, dbias=dbq.view(-1), key_lens=kl,
-                                             drop=drop)
-            else:
-                K.flash_attn_bwd(qv, qs, kv, ks, vv, vs, o, os_, do, os_, s["lse"], dq, qs, dk, ks, dv, vs,
-                                 B, Hl, Sq, Sk, kd, scale, causal, key_lens=kl, drop=drop)
-        elif "P" in s:
-            K.attn_f32_bwd(qv, qs, kv, ks, vv, vs, do.contiguous().view(-1), os_, s["P"], dq.view(-1), dk.view(-1),
-                           dv.view(-1), B, Hl, Sq, Sk, kd, vd, scale, key_lens=kl, drop=drop)
-        else:
-            q4 = qv.as_strided((B, Hl, Sq, kd), (qs[0], qs[1], qs[2], 1)).detach().float().requires_grad_()
-            k4 = kv.as_strided((B, Hl, Sk, kd), (ks[0], ks[1], ks[2], 1)).detach().float().requires_grad_()
-            v4 = vv.as_strided((B, Hl, Sk, vd), (vs[0], vs[1], vs[2], 1)).detach().float().requires_grad_()
-            with torch.enable_grad():
-                out = _attn_ref(q4, k4, v4, scale, causal, kl, s.get("keep"), 256.0 / (256 - drop[0]) if drop else 1.0)
-            g4 = do.permute(0, 2, 1, 3).float()
-            gq, gk, gv = torch.autograd.grad(out, (q4, k4, v4), g4)
-            dq.as_strided((B, Hl, Sq, kd), (qs[0], qs[1], qs[2], 1)).copy_(gq)
-            dk.as_strided((B, Hl, Sk, kd), (ks[0], ks[1], ks[2], 1)).copy_(gk)
-            dv.as_strided((B, Hl, Sk, vd), (vs[0], vs[1], vs[2], 1)).copy_(gv)
+        # fused projection: the flash kernel can add the QKV bias gradient (column sums of dq / dk / dv)
+        # itself, sparing linear_bwd a pass over dqkv (bias_act_bwd + fold); never with a score bias
+        dbq = gw("qkv_bias") if (fused and os.environ.get("FF_ATTN_BIAS_FUSION", "1") == "1") else None
+        if dbq is not None and not (dbq.dtype == torch.float32 and dbq.is_contiguous()):
+            dbq = None
+        bias_done = attn_core_bwd(s, qv, qs, kv, ks, vv, vs, o, os_, do, os_, dq, dk, dv, B, Hl, Sq, Sk, kd, vd, scale,
+                                  causal, kl, drop, s.get("sbias"), dbq.view(-1) if dbq is not None else None)
         if fused:
             dw = gw("qkv_weight")
             db = None if bias_done else gw("qkv_bias")

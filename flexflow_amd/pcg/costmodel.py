@@ -205,12 +205,22 @@ def cost_key(layer, cfg: OpConfig, compute_dtype: DataType) -> tuple:
             tuple(_hot_inputs(layer)[:n_in]), (dact_fusion_partner(layer) or (None,))[0])
 
 
+def is_score_bias_input(layer, i: int) -> bool:
+    """Input i of `layer` is an attention score bias (the last input of an attention layer built with
+    attn_bias): measured as zeros (random values would do, -inf would time an emptier attention) and
+    never given a gradient."""
+    return layer.op_type in (OperatorType.OP_MULTIHEAD_ATTENTION, OperatorType.OP_SDPA) and \
+        bool(layer.attrs.get("attn_bias")) and i == len(layer.inputs) - 1
+
+
 def fabricate_int_input(layer, i: int, shp, cfg: OpConfig, device) -> torch.Tensor:
     """A stand-in for integer input i of `layer` when its cost is measured: embedding indices over
     the local table, an attention layer's key lengths all equal to Sk (a dense batch: random small
     lengths would time a nearly empty attention), otherwise 0 / 1."""
     if layer.op_type == OperatorType.OP_MULTIHEAD_ATTENTION and i == 3:
         return torch.full(tuple(shp), int(layer.inputs[1].dims[1]), device=device, dtype=torch.int32)
+    if layer.op_type == OperatorType.OP_SDPA and i == 3:
+        return torch.full(tuple(shp), int(layer.inputs[1].dims[2]), device=device, dtype=torch.int32)
     hi = 2
     if layer.op_type == OperatorType.OP_EMBEDDING:
         hi = layer.attrs["num_entries"] // max(1, cfg.degrees[-1])
@@ -253,6 +263,8 @@ def measure_cost(layer, cfg: OpConfig, compute_dtype: DataType, device, reps: in
                 continue
             if t.data_type in (DataType.DT_INT32, DataType.DT_INT64):
                 xs.append(fabricate_int_input(layer, i, shp, cfg, device))
+            elif is_score_bias_input(layer, i):
+                xs.append(torch.zeros(shp, device=device, dtype=torch.float32))
             else:
                 xs.append(_step_layout(torch.randn(shp, device=device, dtype=ct)))
             if hot[i]:

@@ -16,7 +16,9 @@ shapes of the given batch / sequence lengths) and the graph is mapped directly:
   weights initialised from the same values.
 * T5 / LLaMA RMS norm (x * rsqrt(mean(x^2) + eps) * w) becomes one rms_norm op; the remaining
   arithmetic (add / mul / pow / tanh ...) maps 1:1; scaled_dot_product_attention becomes
-  batch_matmul -> (+ bias) -> softmax -> batch_matmul.
+  batch_matmul -> (+ bias) -> softmax -> batch_matmul, or with fuse_sdpa=True one
+  scaled_dot_product_attention op (ops/sdpa.py: the flash kernels with the constant mask as their
+  additive score bias, no [B, H, Sq, Sk] scores or probabilities).
 
 The builders are resolved lazily from the graph outputs, so folded or replaced sub-graphs emit
 no dead FF layers.
@@ -57,8 +59,9 @@ def _example_inputs(model, input_names, batch_size, seq_length):
 
 
 class ExportImporter:
-    def __init__(self, model, input_names, batch_size=1, seq_length=None):
+    def __init__(self, model, input_names, batch_size=1, seq_length=None, fuse_sdpa=False):
         self.model = model
+        self.fuse_sdpa = bool(fuse_sdpa)
         self.input_names = list(input_names or ["input_ids"])
         self.batch_size = batch_size
         self.seq_length = seq_length
@@ -312,6 +315,8 @@ class ExportImporter:
         names = ["query", "key", "value", "attn_mask", "dropout_p", "is_causal", "scale"]
         args = dict(zip(names, a))
         args.update(kw)
+        if self.fuse_sdpa:
+            return self._sdpa_fused(n, args)
         if args.get("is_causal"):
             raise NotImplementedError("sdpa is_causal=True (causal masks arrive as attn_mask constants)")
         q, k, v = (self._val(args[x]) for x in ("query", "key", "value"))
@@ -337,3 +342,33 @@ class ExportImporter:
         if dp > 0:
             p = ff.dropout(p, dp)
         return ff.batch_matmul(p, v, name=n.name)
+
+    def _sdpa_fused(self, n, args):
+        """One OP_SDPA: a constant float mask becomes a constant score bias (kept as [1, H, Sq, Sk] when
+        every batch slice is the same), a constant bool mask 0 / -inf; scale, dropout_p and is_causal
+        are passed on."""
+        ff = self._ff
+        q, k, v = (self._val(args[x]) for x in ("query", "key", "value"))
+        if not (len(q.dims) == len(k.dims) == len(v.dims) == 4):
+            raise NotImplementedError(f"fused sdpa needs [B, H, S, D] operands, got {list(q.dims)}")
+        B, H, Sq, Sk = q.dims[0], q.dims[1], q.dims[2], k.dims[2]
+        bias = None
+        m = args.get("attn_mask")
+        if m is not None and self._is_const(m):
+            mv = self._val(m)
+            if mv.dtype == torch.bool:
+                mv = torch.zeros(mv.shape).masked_fill(~mv, float("-inf"))
+            mv = mv.float()
+            mv = mv.reshape((1,) * (4 - mv.dim()) + tuple(mv.shape))
+            mv = mv.expand(mv.shape[0], mv.shape[1], Sq, Sk)
+            if mv.shape[0] not in (1, B) or mv.shape[1] not in (1, H):
+                raise NotImplementedError(f"sdpa attn_mask of shape {list(mv.shape)} for q {list(q.dims)}")
+            if mv.shape[0] > 1 and bool((mv == mv[:1]).all()):
+                mv = mv[:1]
+            bias = self._const_tensor(mv.contiguous(), n.name + "_bias")
+        elif m is not None:
+            bias = self._val(m)
+        scale = args.get("scale")
+        return ff.scaled_dot_product_attention(q, k, v, attn_bias=bias, scale=None if scale is None else float(scale),
+                                               causal=bool(args.get("is_causal")),
+                                               dropout=float(args.get("dropout_p") or 0.0), name=n.name)

@@ -324,7 +324,9 @@ def _build(ff, node: IRNode, ins: list, name: str):
 class PyTorchModel:
     """reference PyTorchModel (python/flexflow/torch/model.py:2408-2607)."""
 
-    def __init__(self, model, is_hf_model=False, input_names=None, batch_size=1, seq_length=None):
+    def __init__(self, model, is_hf_model=False, input_names=None, batch_size=1, seq_length=None, fuse_sdpa=False):
+        """fuse_sdpa (HuggingFace import): map every scaled_dot_product_attention to one fused attention
+        op instead of batch_matmul / softmax / batch_matmul (torch/export.py)."""
         import torch
         assert isinstance(model, torch.nn.Module)
         self.model = model
@@ -332,6 +334,7 @@ class PyTorchModel:
         self.input_names = input_names
         self.batch_size = batch_size
         self.seq_length = seq_length
+        self.fuse_sdpa = bool(fuse_sdpa)
         self._ff_of_module: Dict[str, object] = {}
 
     # ------------------------------------------------------------------ tracing
@@ -391,7 +394,7 @@ class PyTorchModel:
     def torch_to_ff(self, ffmodel, input_tensors, verbose=False):
         if self.is_hf_model and not self._hf_fx_available():
             from .export import ExportImporter
-            imp = ExportImporter(self.model, self.input_names, self.batch_size, self.seq_length)
+            imp = ExportImporter(self.model, self.input_names, self.batch_size, self.seq_length, fuse_sdpa=self.fuse_sdpa)
             return imp.to_ff(ffmodel, input_tensors)
         nodes = self._trace()
         outs, built = PyTorchModel._build_nodes(nodes, ffmodel, input_tensors, verbose)

@@ -167,6 +167,7 @@ class OperatorType(IntEnum):
     OP_INVALID = 89
     OP_LSTM = 100  # extension: LSTM layer (the reference's legacy nmt/ app, outside FFModel)
     OP_RMS_NORM = 101  # extension: RMS norm (T5 / LLaMA), met by the HuggingFace import path
+    OP_SDPA = 102  # extension: scaled dot-product attention on projected heads, with an additive score bias
 
 
 class OpType(Enum):
