@@ -56,7 +56,24 @@ struct AttnArgs {
   // and NaN are the caller's problem. The score bias takes no gradient.
   const float* sbias = nullptr;
   int64_t sbias_sb = 0, sbias_sh = 0;
+  // packed sequences: the run [seg_lo[b][i], seg_hi[b][i]) that position i of row b belongs to,
+  // int32 [B][S] each as attn_seg_bounds writes them (both non-decreasing along a row, an empty run
+  // anchored at i for padding), or null. Query i sees key j iff j lies in i's run; the relation is
+  // symmetric, so it needs Sq == Sk. Selects the SEG = true instantiations of attn_fwd_kernel /
+  // attn_bwd_kernel (always MASK = true, never with sbias or key_lens; attn_fwd2_kernel and
+  // attn_bwd1b_kernel have none, so attn_bwd then leaves the fused bias gradient to the caller).
+  // They bound their mask tests and tile loops by the runs; memory bounds stay on Sq / Sk. A padding
+  // position gives o = 0, lse = +inf and zero dq / dk / dv rows.
+  const int* seg_lo = nullptr;
+  const int* seg_hi = nullptr;
 };
+
+// lo / hi [B][S] (int32) from segment ids [B][S]: a segment is a maximal run of equal ids >= 0 and
+// [lo[i], hi[i]) is the run of position i; a padding position (id < 0) gets lo = hi = i. One
+// workgroup per row, nothing read on the host.
+void attn_seg_bounds(const int* ids, int* lo, int* hi, int B, int S, hipStream_t st);
+// scores [H][Sq][Sk] (fp32) of one sample: -inf outside the query's run (rows lo / hi of that sample)
+void segment_mask_f32(float* s, int H, int Sq, int Sk, const int* lo, const int* hi, hipStream_t st);
 
 // out[h][q][k] = keep(b, h0 + h, q, k) ? x[h][q][k] * drop_scale : 0 over an fp32 [H][Sq][Sk] slab of
 // global sample b (the fp32 device path: P[b] after the softmax, dP in the backward); out may be x

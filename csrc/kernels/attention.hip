@@ -147,10 +147,14 @@ __device__ __forceinline__ int key_limit(const AttnArgs& a, int b) {
 // The lane's 8 key quads of a tile are requested ahead of the S MFMAs: one 16-B load per quad on
 // full tiles of 16-B aligned rows, predicated 4-B loads elsewhere (nothing is read at or past Sk
 // or Sq). The 32 bias registers are live across the MFMAs, so these forms are bounded like DROP.
-template <int D, bool MASK, bool DMA, bool DROP = false, bool BIAS = false>
-__global__ void __launch_bounds__(256, DMA ? (DROP || BIAS ? 3 : 4) : (D == 128 && DROP && BIAS ? 1 : 2))
+// SEG (packed sequences, AttnArgs.seg_lo / seg_hi; always MASK = true, never BIAS): a key outside the
+// lane's row's run is masked, and the tile loop covers the workgroup's runs only (below). Bounded
+// like DROP.
+template <int D, bool MASK, bool DMA, bool DROP = false, bool BIAS = false, bool SEG = false>
+__global__ void __launch_bounds__(256, DMA ? (DROP || BIAS || SEG ? 3 : 4) : (D == 128 && DROP && BIAS ? 1 : 2))
     attn_fwd_kernel(AttnArgs a) {
   static_assert(MASK || !BIAS, "the score bias forms are MASK = true");
+  static_assert((MASK && !BIAS) || !SEG, "the segment forms are MASK = true and take no score bias");
   constexpr int KV = 64;
   constexpr int TB = KV * D * 2;  // bytes of one K or V tile
   __shared__ __attribute__((aligned(16))) char smem[4 * TB];
@@ -215,20 +219,44 @@ __global__ void __launch_bounds__(256, DMA ? (DROP || BIAS ? 3 : 4) : (D == 128 
   const int klim = key_limit<MASK>(a, b);
   int nkv = (klim + KV - 1) / KV;
   if (a.causal) nkv = min(nkv, (min(qblk0 + 128, a.Sq) + KV - 1) / KV);
+  // SEG: the lane's run [slo, shi) and, wave-uniform, the keys every row of the wave sees
+  // [wlo, whi) (lo / hi do not decrease along a row: the largest lo is the last row's, the smallest
+  // hi the first row's). The workgroup runs the tiles from its first row's lo to its last row's hi
+  // only; the double-buffer slot follows the loop index.
+  // The deferred-max decision below is taken per wave; in a wave whose rows are not all of one run
+  // (wmixed) a row moves its max only on its own account, so that no output of a segment depends on
+  // the values of another one (a wave of one run decides as the other forms do: bitwise equal to them).
+  int slo = 0, shi = 0, wlo = 0, whi = 0, t0 = 0;
+  bool wmixed = false;
+  if constexpr (SEG) {
+    const int* lo = a.seg_lo + (int64_t)b * a.Sq;
+    const int* hi = a.seg_hi + (int64_t)b * a.Sq;
+    const int rl = min(qrow, a.Sq - 1);
+    slo = lo[rl];
+    shi = hi[rl];
+    wlo = __builtin_amdgcn_readfirstlane(lo[min(q0 + 31, a.Sq - 1)]);
+    whi = __builtin_amdgcn_readfirstlane(hi[min(q0, a.Sq - 1)]);
+    wmixed = wlo != __builtin_amdgcn_readfirstlane(lo[min(q0, a.Sq - 1)]) ||
+             whi != __builtin_amdgcn_readfirstlane(hi[min(q0 + 31, a.Sq - 1)]);
+    const int glo = __builtin_amdgcn_readfirstlane(lo[qblk0]);
+    const int ghi = __builtin_amdgcn_readfirstlane(hi[min(qblk0 + 127, a.Sq - 1)]);
+    nkv = min(nkv, max((ghi + KV - 1) / KV, 0));
+    t0 = min(max(glo, 0) / KV, nkv);
+  }
 
   TileStage<D, KV, 256> sk, sv;
   const int kb = (int)min((int64_t)0x7fffffff, ((int64_t)(a.Sk - 1) * a.k_ss + D) * 2);
   const int vb = (int)min((int64_t)0x7fffffff, ((int64_t)(a.Sk - 1) * a.v_ss + D) * 2);
   const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc((void*)K, (short)0, kb, 0x00020000);
   const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void*)V, (short)0, vb, 0x00020000);
-  if (nkv > 0) {
+  if (nkv > t0) {
     if (DMA) {
-      dma_tile<D, 4>(rk, smem, a.k_ss, 0, wave, lane);
-      dma_tile<D, 4>(rv, smem + TB, a.v_ss, 0, wave, lane);
+      dma_tile<D, 4>(rk, smem, a.k_ss, t0 * KV, wave, lane);
+      dma_tile<D, 4>(rv, smem + TB, a.v_ss, t0 * KV, wave, lane);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     } else {
-      sk.load(K, a.k_ss, 0, a.Sk, tid);
-      sv.load(V, a.v_ss, 0, a.Sk, tid);
+      sk.load(K, a.k_ss, t0 * KV, a.Sk, tid);
+      sv.load(V, a.v_ss, t0 * KV, a.Sk, tid);
       sk.store(smem, tid);
       sv.store(smem + TB, tid);
     }
@@ -298,14 +326,15 @@ __global__ void __launch_bounds__(256, DMA ? (DROP || BIAS ? 3 : 4) : (D == 128 
     // mask (only on tiles that cross the sequence end or the causal diagonal: a wave-uniform
     // test), online softmax on the raw scores (lane-local + xor-32 partner), scale folded into
     // one FMA per element: p = exp2(s * sl2 - m * sl2)
-    const bool need_mask = MASK && ((kbase + KV > klim) || (a.causal && kbase + KV - 1 > q0));
+    const bool need_mask = MASK && ((kbase + KV > klim) || (a.causal && kbase + KV - 1 > q0) ||
+                                    (SEG && (kbase < wlo || kbase + KV > whi)));
     if (need_mask) {
 #pragma unroll
       for (int kt = 0; kt < 2; ++kt) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int key = kbase + 32 * kt + (r & 3) + 8 * (r >> 2) + 4 * h;
-          if (key >= klim || (a.causal && key > qrow)) sacc[kt][r] = -INFINITY;
+          if (key >= klim || (a.causal && key > qrow) || (SEG && (key < slo || key >= shi))) sacc[kt][r] = -INFINITY;
         }
       }
     }
@@ -321,7 +350,10 @@ __global__ void __launch_bounds__(256, DMA ? (DROP || BIAS ? 3 : 4) : (D == 128 
     // taken against the old max and stays <= 2^rescale_thr. Decided before this tile's P exists, so
     // nothing is ever at two scales.
     if (!__all(mx <= m + a.rescale_thr)) {
-      const float mnew = fmaxf(m, mx);
+      float mnew = fmaxf(m, mx);
+      if constexpr (SEG) {
+        if (wmixed && !(mx > m + a.rescale_thr)) mnew = m;  // alpha = 1: the row is left as it was
+      }
       const float alpha = fast_exp2(m - (mnew == -INFINITY ? 0.f : mnew));
       lsum *= alpha;
 #pragma unroll
@@ -381,7 +413,7 @@ __global__ void __launch_bounds__(256, DMA ? (DROP || BIAS ? 3 : 4) : (D == 128 
     }
     __syncthreads();
   };
-  for (int t = 0; t < nkv; t += 2) {
+  for (int t = t0; t < nkv; t += 2) {
     tile(std::integral_constant<int, 0>{}, t);
     if (t + 1 < nkv) tile(std::integral_constant<int, 1>{}, t + 1);
   }
@@ -776,9 +808,13 @@ __device__ __forceinline__ unsigned pack_bf2(float x, float y) {
 //    lane owns one key, so the 16 bias elements of a 32-query block are 4-B loads that the lanes of
 //    a half-wave coalesce along a bias row; they are requested ahead of the block's S / dP MFMAs
 //    and predicated on key < Sk and q < Sq. The bias takes no gradient (dS is not written out).
-template <int D, int NW, bool MASK, bool CHAIN, bool DMA = false, bool DROP = false, bool BIAS = false>
+//  * SEG (packed sequences, AttnArgs.seg_lo / seg_hi; always MASK = true, never BIAS): the lane tests
+//    the query index against its own key's run, a key block runs only the query tiles whose dQ chain
+//    it is part of, and each tile's chain starts and ends at key blocks of its own (at qt_begin below).
+template <int D, int NW, bool MASK, bool CHAIN, bool DMA = false, bool DROP = false, bool BIAS = false, bool SEG = false>
 __global__ void __launch_bounds__(64 * NW, 8 / NW) attn_bwd_kernel(AttnArgs a, int nkb, int pass) {
   static_assert(MASK || !BIAS, "the score bias forms are MASK = true");
+  static_assert((MASK && !BIAS) || !SEG, "the segment forms are MASK = true and take no score bias");
   constexpr int NT = 64 * NW;
   constexpr int QT = 64;       // queries per loop step
   constexpr int KB = 32 * NW;  // keys per workgroup
@@ -872,7 +908,46 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) attn_bwd_kernel(AttnArgs a, i
 #pragma unroll
   for (int i = 0; i < D / 32; ++i) { dk[i] = f32x16{}; dv[i] = f32x16{}; }
   const int nqt = (a.Sq + QT - 1) / QT;
-  const int qt_begin = !MASK ? 0 : kblk > kb_last() ? nqt : a.causal ? kb0 / QT : 0;
+  // SEG (AttnArgs.seg_lo / seg_hi; Sq == Sk): query q sees this lane's key iff q lies in the key's
+  // own run [klo, klo + klen), since both sides share one segmentation; [wlo, whi) are the queries every key
+  // of the wave sees (lo / hi do not decrease along a row). Query tile t has a chain of key blocks of
+  // its own, seg_first(t) .. seg_last(t), from the lo of its first row and the hi of its last (and
+  // the causal diagonal): exactly those blocks run it, the first starts the fp32 dQ sum without
+  // reading it and the last writes the bf16 dQ, so every tile's dQ is written once, an all-padding
+  // tile's as zeros (first <= last always: no chain is empty). Both ends do not decrease with t, so
+  // a block's tiles are one interval [qt_begin, qt_end), and every query that sees one of its keys
+  // lies in it.
+  const int* seglo = nullptr;
+  const int* seghi = nullptr;
+  int klo = 0, wlo = 0, whi = 0;
+  unsigned klen = 0;
+  auto seg_first = [&](int t) {
+    return min(max(__builtin_amdgcn_readfirstlane(seglo[t * QT]), 0) / KB, nkb - 1);
+  };
+  auto seg_last = [&](int t, int first) {
+    int l = (max(__builtin_amdgcn_readfirstlane(seghi[min(t * QT + QT, a.Sq) - 1]), 1) - 1) / KB;
+    if (a.causal) l = min(l, (t * QT + QT - 1) / KB);
+    return max(min(l, nkb - 1), first);
+  };
+  // the lane's mask test is one unsigned compare, (q - klo) >= klen: the causal bound (q >= key) is
+  // folded into klo and a key past Sk gets klen = 0
+  auto seg_tiles = [&](int& end) {
+    seglo = a.seg_lo + (int64_t)b * a.Sq;
+    seghi = a.seg_hi + (int64_t)b * a.Sq;
+    const int kc = min(key, a.Sk - 1);
+    klo = a.causal ? max(seglo[kc], key) : seglo[kc];
+    klen = key < a.Sk ? (unsigned)max(seghi[kc] - klo, 0) : 0u;
+    wlo = __builtin_amdgcn_readfirstlane(seglo[min(kb0 + wave * 32 + 31, a.Sk - 1)]);
+    whi = __builtin_amdgcn_readfirstlane(seghi[min(kb0 + wave * 32, a.Sk - 1)]);
+    int begin = 0;
+    while (begin < nqt && seg_last(begin, seg_first(begin)) < kblk) ++begin;
+    end = begin;
+    while (end < nqt && seg_first(end) <= kblk) ++end;
+    return begin;
+  };
+  int qt_end_seg = 0;
+  const int qt_begin = SEG ? seg_tiles(qt_end_seg) : !MASK ? 0 : kblk > kb_last() ? nqt : a.causal ? kb0 / QT : 0;
+  const int qt_end = SEG ? qt_end_seg : nqt;
   const int G = lane >> 4, qi = (lane & 15) >> 2, pi = lane & 3;
 
   TileStage<D, QT, NT> sq, sd;
@@ -913,29 +988,33 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) attn_bwd_kernel(AttnArgs a, i
   };
   if constexpr (DMA) {
     __syncthreads();  // every wave has its V fragments: the tile buffers can be overwritten
-    if (qt_begin < nqt) {
+    if (qt_begin < qt_end) {
       dma_rows(qt_begin);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     __syncthreads();
   } else {
-    if (qt_begin < nqt) fetch(qt_begin);
+    if (qt_begin < qt_end) fetch(qt_begin);
     __syncthreads();  // every wave has its V fragments: the tile buffers can be overwritten
-    if (qt_begin < nqt) stash(qt_begin);
+    if (qt_begin < qt_end) stash(qt_begin);
     __syncthreads();
   }
 
-  for (int t = qt_begin; t < nqt; ++t) {
+  for (int t = qt_begin; t < qt_end; ++t) {
     const int qbase = t * QT;
     char* tb = smem + (t & 1) * TILE;
     const char* q_l = tb;
     const char* do_l = tb + QB;
     const float* lse_l = reinterpret_cast<const float*>(tb + 2 * QB);
     const float* dl_l = lse_l + QT;
-    const bool more = t + 1 < nqt;
-    // D = 64 register staging with DROP and BIAS: the staged tile's registers do not fit beside the
-    // tile's work (2 spilled), so the next tile is fetched right before it is stashed, nothing under it
-    constexpr bool FETCH_LATE = D == 64 && !DMA && DROP && BIAS;
+    const bool more = t + 1 < qt_end;
+    // SEG: the tile's own dQ chain (without: key block 0 to kb_last or the causal diagonal's)
+    const int ch_first = SEG ? seg_first(t) : 0;
+    const int ch_last = SEG ? seg_last(t, ch_first) : 0;
+    // D = 64 register staging with DROP and BIAS or SEG: the staged tile's registers do not fit beside
+    // the tile's work (2 spilled; 2 to 16 with SEG), so the next tile is fetched right before it is
+    // stashed, nothing under it
+    constexpr bool FETCH_LATE = D == 64 && !DMA && DROP && (BIAS || SEG);
     if (more) {  // in flight during this tile's MFMAs
       if constexpr (DMA) dma_rows(t + 1);  // buffer (t+1)&1: its readers finished before tile t-1's mid barrier
       else if constexpr (!FETCH_LATE) fetch(t + 1);
@@ -944,10 +1023,10 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) attn_bwd_kernel(AttnArgs a, i
     // now so its HBM round trip runs under the tile's MFMAs (read at its use below, the load sat on
     // the workgroup's critical path once per query tile)
     float4 prev[4];
-    if constexpr (NW >= 2 * (D / 32) && !DROP && !BIAS) {  // DROP, BIAS: these 16 registers made the chained forms spill
+    if constexpr (NW >= 2 * (D / 32) && !DROP && !BIAS && !SEG) {  // DROP, BIAS, SEG: these 16 registers made the chained forms spill
       const int tile = wave % (2 * (D / 32));
       const int q = qbase + 32 * (tile / (D / 32)) + (lane & 31);
-      if (chain && kblk > 0 && wave < 2 * (D / 32) && (!MASK || q < a.Sq)) {
+      if (chain && kblk > ch_first && wave < 2 * (D / 32) && (!MASK || q < a.Sq)) {
         const float* prow = dq_part + (int64_t)q * D + 32 * (tile % (D / 32)) + 4 * h;
 #pragma unroll
         for (int g = 0; g < 4; ++g) prev[g] = *reinterpret_cast<const float4*>(prow + 8 * g);
@@ -1000,12 +1079,17 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) attn_bwd_kernel(AttnArgs a, i
         }
       }
       if (MASK) {
-        const bool need = (kb0 + wave * 32 + 31 >= klim) || (a.causal && kb0 + wave * 32 + 31 > qbase + 32 * qt);
+        const bool need = (kb0 + wave * 32 + 31 >= klim) || (a.causal && kb0 + wave * 32 + 31 > qbase + 32 * qt) ||
+                          (SEG && (qbase + 32 * qt < wlo || qbase + 32 * qt + 32 > whi));
         if (need) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const int q = qbase + 32 * qt + (r & 3) + 8 * (r >> 2) + 4 * h;
-            if (key >= klim || (a.causal && key > q)) sacc[r] = 0.f;
+            if constexpr (SEG) {
+              if ((unsigned)(q - klo) >= klen) sacc[r] = 0.f;
+            } else {
+              if (key >= klim || (a.causal && key > q)) sacc[r] = 0.f;
+            }
           }
         }
       }
@@ -1067,13 +1151,13 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) attn_bwd_kernel(AttnArgs a, i
       const int q = qbase + 32 * qt + (lane & 31);
       if (part == 0 && (!MASK || q < a.Sq)) {
         float* prow = dq_part + (int64_t)q * D + 32 * dt + 4 * h;
-        if (chain && kblk > 0) {
+        if (chain && kblk > ch_first) {
           // the previous launch's running sum (written by this lane of the same wave position);
           // a causal block's query tiles all had key block kblk - 1 contributing too
 #pragma unroll
           for (int g = 0; g < 4; ++g) {
             float4 pv;
-            if constexpr (NW >= 2 * (D / 32) && !DROP && !BIAS) pv = prev[g];  // prefetched at the top of the tile
+            if constexpr (NW >= 2 * (D / 32) && !DROP && !BIAS && !SEG) pv = prev[g];  // prefetched at the top of the tile
             else pv = *reinterpret_cast<const float4*>(prow + 8 * g);
             acc[4 * g] += pv.x; acc[4 * g + 1] += pv.y; acc[4 * g + 2] += pv.z; acc[4 * g + 3] += pv.w;
           }
@@ -1081,6 +1165,7 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) attn_bwd_kernel(AttnArgs a, i
         // last key block contributing to this query tile: the last one, or (causal) the diagonal's
         int last = kb_last();
         if (MASK && a.causal) last = min(last, (qbase + QT - 1) / KB);
+        if constexpr (SEG) last = ch_last;
         if (chain && kblk == last) {
           bf16_t* drow = dQb + (int64_t)q * a.dq_ss + 32 * dt + 4 * h;
 #pragma unroll
@@ -1168,10 +1253,13 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) attn_bwd_kernel(AttnArgs a, i
   // nothing from this key block; zero its rows
   if (MASK && !chain) {
     for (int64_t i = tid; i < (int64_t)min(qt_begin * QT, a.Sq) * D; i += NT) dq_part[i] = 0.f;
+    if constexpr (SEG) {  // and the tiles behind its last one
+      for (int64_t i = (int64_t)min(qt_end * QT, a.Sq) * D + tid; i < (int64_t)a.Sq * D; i += NT) dq_part[i] = 0.f;
+    }
   }
   // dK (K block image) and dV (tile buffers) through LDS, 16-B chunks XOR-swizzled by row & 7;
   // the loop's last barrier retired every read of both regions
-  if (qt_begin >= nqt) __syncthreads();
+  if (qt_begin >= qt_end) __syncthreads();
   {
     char* dv_l = smem;
     const int row = wave * 32 + (lane & 31);
@@ -1763,6 +1851,84 @@ void attn_dropout_mask(uint8_t* out, int B, int H, int Sq, int Sk, int b0, int h
                      H_total, rng_step, rng_seed, drop_thr);
 }
 
+// ------------------------------------------------------------------ packed sequences (segment ids)
+// One workgroup per row, any S: chunks of 256 positions, front to back for lo (inclusive max-scan of
+// "a run starts here ? i : -1", the carry being the last start so far) and back to front for hi
+// (inclusive min-scan of "a run ends behind i ? i + 1 : INT_MAX"). Padding positions (id < 0) get
+// lo = hi = i, which keeps both arrays non-decreasing along the row.
+__global__ void __launch_bounds__(256) attn_seg_bounds_kernel(const int* __restrict__ ids, int* __restrict__ lo,
+                                                              int* __restrict__ hi, int S) {
+  __shared__ int buf[2][256];
+  const int tid = threadIdx.x;
+  const int* row = ids + (int64_t)blockIdx.x * S;
+  int* lor = lo + (int64_t)blockIdx.x * S;
+  int* hir = hi + (int64_t)blockIdx.x * S;
+  int carry = 0;
+  for (int c = 0; c < S; c += 256) {
+    const int i = c + tid;
+    int id = -1, v = -1;
+    if (i < S) {
+      id = row[i];
+      if (i == 0 || row[i - 1] != id) v = i;
+    }
+    int cur = 0;
+    buf[0][tid] = v;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {
+      int x = buf[cur][tid];
+      if (tid >= off) x = max(x, buf[cur][tid - off]);
+      buf[cur ^ 1][tid] = x;
+      cur ^= 1;
+      __syncthreads();
+    }
+    if (i < S) lor[i] = id < 0 ? i : max(buf[cur][tid], carry);
+    carry = max(carry, buf[cur][255]);
+    __syncthreads();
+  }
+  carry = 0x7fffffff;
+  for (int c = (S - 1) / 256 * 256; c >= 0; c -= 256) {
+    const int i = c + tid;
+    int id = -1, v = 0x7fffffff;
+    if (i < S) {
+      id = row[i];
+      if (i + 1 == S || row[i + 1] != id) v = i + 1;
+    }
+    int cur = 0;
+    buf[0][tid] = v;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {
+      int x = buf[cur][tid];
+      if (tid + off < 256) x = min(x, buf[cur][tid + off]);
+      buf[cur ^ 1][tid] = x;
+      cur ^= 1;
+      __syncthreads();
+    }
+    if (i < S) hir[i] = id < 0 ? i : min(buf[cur][tid], carry);
+    carry = min(carry, buf[cur][0]);
+    __syncthreads();
+  }
+}
+
+void attn_seg_bounds(const int* ids, int* lo, int* hi, int B, int S, hipStream_t st) {
+  if (B <= 0 || S <= 0) return;
+  hipLaunchKernelGGL(attn_seg_bounds_kernel, dim3((unsigned)B), dim3(256), 0, st, ids, lo, hi, S);
+}
+
+// the fp32 device path: scores [H][Sq][Sk] of one sample, -inf outside the query's run
+__global__ void segment_mask_kernel(float* __restrict__ s, int64_t n, int Sq, int Sk, const int* __restrict__ lo,
+                                    const int* __restrict__ hi) {
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
+    const int k = (int)(e % Sk), q = (int)((e / Sk) % Sq);
+    if (k < lo[q] || k >= hi[q]) s[e] = -INFINITY;
+  }
+}
+
+void segment_mask_f32(float* s, int H, int Sq, int Sk, const int* lo, const int* hi, hipStream_t st) {
+  const int64_t n = (int64_t)H * Sq * Sk;
+  if (n <= 0) return;
+  hipLaunchKernelGGL(segment_mask_kernel, dim3(ew_grid(n, 256)), dim3(256), 0, st, s, n, Sq, Sk, lo, hi);
+}
+
 // LDS-DMA staging of a [rows][D] operand (row stride ss elements) needs 16-B aligned rows and
 // buffer offsets below 2 GiB, one tile past the last row included
 static bool dma_rows_ok(const void* p, int64_t ss, int rows) {
@@ -1771,7 +1937,7 @@ static bool dma_rows_ok(const void* p, int64_t ss, int rows) {
 
 // one workgroup per 128 QB query rows of a (batch, head), QB 32-row blocks per wave: QB = 2 is
 // attn_fwd2_kernel (D = 64, LDS-DMA, no dropout and no score bias form), QB = 1 attn_fwd_kernel,
-// whose DROP and BIAS instantiations are always MASK = true
+// whose DROP, BIAS and SEG (packed sequences, never with BIAS) instantiations are always MASK = true
 template <int D, int QB, bool DMA>
 static void launch_fwd(const AttnArgs& a, bool mask, hipStream_t st) {
   constexpr int ROWS = 128 * QB;
@@ -1780,6 +1946,10 @@ static void launch_fwd(const AttnArgs& a, bool mask, hipStream_t st) {
     static_assert(D == 64 && DMA, "attn_fwd2_kernel is fixed to D = 64 and LDS-DMA staging");
     if (mask) hipLaunchKernelGGL((attn_fwd2_kernel<true>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((attn_fwd2_kernel<false>), grid, dim3(256), 0, st, a);
+  } else if (a.seg_lo && a.drop_thr > 0) {
+    hipLaunchKernelGGL((attn_fwd_kernel<D, true, DMA, true, false, true>), grid, dim3(256), 0, st, a);
+  } else if (a.seg_lo) {
+    hipLaunchKernelGGL((attn_fwd_kernel<D, true, DMA, false, false, true>), grid, dim3(256), 0, st, a);
   } else if (a.sbias && a.drop_thr > 0) {
     hipLaunchKernelGGL((attn_fwd_kernel<D, true, DMA, true, true>), grid, dim3(256), 0, st, a);
   } else if (a.sbias) {
@@ -1805,7 +1975,7 @@ void attn_fwd(AttnArgs a, hipStream_t st) {
     // (half the workgroups), profiles/attn_fwd_variants_r4.txt; its DROP form (230 VGPRs, no
     // scratch) measured slower at S = 512 too, 60.1 against 57.8 us at B32 H16 (docs/PERFORMANCE.md
     // 'Attention dropout'), so it has none; nor has it a score bias form
-    if (v == 3 && dma_ok && !drop && !a.sbias && a.Sq >= 512) launch_fwd<64, 2, true>(a, mask, st);
+    if (v == 3 && dma_ok && !drop && !a.sbias && !a.seg_lo && a.Sq >= 512) launch_fwd<64, 2, true>(a, mask, st);
     else if (v >= 1 && dma_ok) launch_fwd<64, 1, true>(a, mask, st);
     else launch_fwd<64, 1, false>(a, mask, st);
   } else if (a.D == 128) {
@@ -1813,26 +1983,31 @@ void attn_fwd(AttnArgs a, hipStream_t st) {
   }
 }
 
-// attn_bwd_kernel, chained (one launch per key block) or as slabs; the DROP (attention dropout)
-// and BIAS (score bias) instantiations are always MASK = true
+// attn_bwd_kernel, chained (one launch per key block) or as slabs; the DROP (attention dropout),
+// BIAS (score bias) and SEG (packed sequences, never with BIAS) instantiations are always MASK = true
 template <int D, int NW, bool DMA = false>
 static void launch_bwd(const AttnArgs& a, int nkb, bool chain, hipStream_t st) {
   const bool mask = a.causal || a.Sk % (32 * NW) != 0 || a.Sq % 64 != 0 || a.key_lens != nullptr;
   const int bh = a.B * a.H;
-  auto go = [&](auto m, auto d, auto sb) {
+  auto go = [&](auto m, auto d, auto sb, auto sg) {
     constexpr bool MASK = decltype(m)::value, DROP = decltype(d)::value, BIAS = decltype(sb)::value;
+    constexpr bool SEG = decltype(sg)::value;
     if (chain) {
       for (int p = 0; p < nkb; ++p)
-        hipLaunchKernelGGL((attn_bwd_kernel<D, NW, MASK, true, DMA, DROP, BIAS>), dim3(bh), dim3(64 * NW), 0, st, a, nkb, p);
+        hipLaunchKernelGGL((attn_bwd_kernel<D, NW, MASK, true, DMA, DROP, BIAS, SEG>), dim3(bh), dim3(64 * NW), 0, st, a, nkb, p);
     } else {
-      hipLaunchKernelGGL((attn_bwd_kernel<D, NW, MASK, false, DMA, DROP, BIAS>), dim3(bh * nkb), dim3(64 * NW), 0, st, a, nkb, 0);
+      hipLaunchKernelGGL((attn_bwd_kernel<D, NW, MASK, false, DMA, DROP, BIAS, SEG>), dim3(bh * nkb), dim3(64 * NW), 0, st, a, nkb, 0);
     }
   };
-  if (a.sbias && a.drop_thr > 0) go(std::true_type{}, std::true_type{}, std::true_type{});
-  else if (a.sbias) go(std::true_type{}, std::false_type{}, std::true_type{});
-  else if (a.drop_thr > 0) go(std::true_type{}, std::true_type{}, std::false_type{});
-  else if (mask) go(std::true_type{}, std::false_type{}, std::false_type{});
-  else go(std::false_type{}, std::false_type{}, std::false_type{});
+  const std::true_type T{};
+  const std::false_type F{};
+  if (a.seg_lo && a.drop_thr > 0) go(T, T, F, T);
+  else if (a.seg_lo) go(T, F, F, T);
+  else if (a.sbias && a.drop_thr > 0) go(T, T, T, F);
+  else if (a.sbias) go(T, F, T, F);
+  else if (a.drop_thr > 0) go(T, T, F, F);
+  else if (mask) go(T, F, F, F);
+  else go(F, F, F, F);
 }
 
 bool attn_bwd(AttnArgs a, hipStream_t st) {
@@ -1856,9 +2031,9 @@ bool attn_bwd(AttnArgs a, hipStream_t st) {
   if (a.D == 64) {
     hipLaunchKernelGGL(attn_bwd_pre_kernel<64>, gpre, dim3(256), 0, st, a);
     // attn_bwd1b_kernel has no DROP and no score bias instantiation (it uses every VGPR already):
-    // with dropout or a score bias the generic kernel runs the chained form too, and the fused bias
-    // gradient is left to the caller (returns false)
-    if (chain && dma_ok && !drop && !a.sbias) {
+    // with dropout, a score bias or segments the generic kernel runs the chained form too, and the
+    // fused bias gradient is left to the caller (returns false)
+    if (chain && dma_ok && !drop && !a.sbias && !a.seg_lo) {
       const bool m = a.causal || a.Sk % 256 != 0 || a.Sq % 64 != 0 || a.key_lens != nullptr;
       const int bh = a.B * a.H;
       // fused bias-gradient sums: non-causal (every query tile's last key block is the last launch)

@@ -801,12 +801,56 @@ void attn_sbias_args(ffk::AttnArgs& a, const Tensor& q, const optional<Tensor>& 
   a.sbias_sh = sh;
 }
 
+// packed sequences (AttnArgs.seg_lo / seg_hi): the run bounds attn_seg_bounds wrote, int32 [B, Sq]
+// on q's device; the query and the key side share them, and there is no form with a score bias or
+// key lengths (a padding id says what a length would)
+void attn_seg_args(ffk::AttnArgs& a, const Tensor& q, const optional<Tensor>& lo, const optional<Tensor>& hi,
+                   int64_t B, int64_t Sq, int64_t Sk) {
+  const bool has_lo = lo.has_value() && lo->defined(), has_hi = hi.has_value() && hi->defined();
+  if (!has_lo && !has_hi) return;
+  TORCH_CHECK(has_lo && has_hi, "attn: seg_lo and seg_hi come together");
+  for (const Tensor* t : {&*lo, &*hi}) {
+    TORCH_CHECK(t->scalar_type() == at::kInt && t->is_contiguous() && t->numel() == B * Sq,
+                "attn: seg_lo / seg_hi must be contiguous int32 tensors of B * Sq elements");
+    TORCH_CHECK(t->device() == q.device(), "attn: seg_lo / seg_hi must be on the device of q");
+  }
+  TORCH_CHECK(Sq == Sk, "attn: segments need Sq == Sk (one segmentation for queries and keys)");
+  TORCH_CHECK(a.sbias == nullptr, "attn: segments with a score bias are not supported");
+  TORCH_CHECK(a.key_lens == nullptr, "attn: segments with key lengths are not supported (use a padding id)");
+  a.seg_lo = lo->data_ptr<int>();
+  a.seg_hi = hi->data_ptr<int>();
+}
+
+void attn_seg_bounds(Tensor ids, Tensor lo, Tensor hi) {
+  check_dev(ids, "ids");
+  TORCH_CHECK(ids.dim() == 2, "attn_seg_bounds: ids must be [B, S]");
+  for (const Tensor* t : {&ids, &lo, &hi})
+    TORCH_CHECK(t->scalar_type() == at::kInt && t->is_contiguous() && t->numel() == ids.numel() &&
+                    t->device() == ids.device(),
+                "attn_seg_bounds: ids, lo, hi must be contiguous int32 [B, S] tensors on one device");
+  ffk::attn_seg_bounds(ids.data_ptr<int>(), lo.data_ptr<int>(), hi.data_ptr<int>(), (int)ids.size(0), (int)ids.size(1),
+                       cur_stream());
+}
+
+// s [H, Sq, Sk] (fp32 scores of sample b) = -inf outside the query's run; lo / hi int32 [B, Sq]
+void segment_mask_f32(Tensor s, Tensor lo, Tensor hi, int64_t b, int64_t H, int64_t Sq, int64_t Sk) {
+  check_dev(s, "s");
+  TORCH_CHECK(s.scalar_type() == at::kFloat && s.is_contiguous() && s.numel() == H * Sq * Sk);
+  for (const Tensor* t : {&lo, &hi})
+    TORCH_CHECK(t->scalar_type() == at::kInt && t->is_contiguous() && t->numel() % Sq == 0 && b >= 0 &&
+                    (b + 1) * Sq <= t->numel() && t->device() == s.device(),
+                "segment_mask_f32: lo / hi int32 [B, Sq] on the scores' device");
+  ffk::segment_mask_f32(s.data_ptr<float>(), (int)H, (int)Sq, (int)Sk, lo.data_ptr<int>() + b * Sq,
+                        hi.data_ptr<int>() + b * Sq, cur_stream());
+}
+
 // q/k/v/o given with explicit [b,h,s] element strides (d contiguous)
 void attn_fwd(Tensor q, std::vector<int64_t> qs, Tensor k, std::vector<int64_t> ks, Tensor v,
               std::vector<int64_t> vs, Tensor o, std::vector<int64_t> os, Tensor lse, int64_t B, int64_t H,
               int64_t Sq, int64_t Sk, int64_t D, double scale, bool causal, optional<Tensor> key_lens,
               int64_t drop_thr, optional<Tensor> rng_step, int64_t rng_seed, int64_t b0, int64_t h0, int64_t H_total,
-              optional<Tensor> sbias, int64_t sbias_sb, int64_t sbias_sh) {
+              optional<Tensor> sbias, int64_t sbias_sb, int64_t sbias_sh, optional<Tensor> seg_lo,
+              optional<Tensor> seg_hi) {
   TORCH_CHECK(D == 64 || D == 128, "flash attention supports head_dim 64/128");
   TORCH_CHECK(q.scalar_type() == at::kBFloat16 && o.scalar_type() == at::kBFloat16);
   TORCH_CHECK(lse.numel() >= B * H * Sq && lse.scalar_type() == at::kFloat);
@@ -821,6 +865,7 @@ void attn_fwd(Tensor q, std::vector<int64_t> qs, Tensor k, std::vector<int64_t> 
   a.key_lens = attn_key_lens(key_lens, q, B);
   attn_drop_args(a, q, drop_thr, rng_step, rng_seed, b0, h0, H_total, H);
   attn_sbias_args(a, q, sbias, sbias_sb, sbias_sh, B, H, Sq, Sk);
+  attn_seg_args(a, q, seg_lo, seg_hi, B, Sq, Sk);
   ffk::attn_fwd(a, cur_stream());
 }
 int64_t attn_bwd_ws(int64_t B, int64_t H, int64_t Sq, int64_t Sk, int64_t D) {
@@ -832,7 +877,8 @@ bool attn_bwd(Tensor q, std::vector<int64_t> qs, Tensor k, std::vector<int64_t> 
               std::vector<int64_t> dvs, Tensor ws, int64_t B, int64_t H, int64_t Sq, int64_t Sk, int64_t D,
               double scale, bool causal, optional<Tensor> dbias, optional<Tensor> key_lens, int64_t drop_thr,
               optional<Tensor> rng_step, int64_t rng_seed, int64_t b0, int64_t h0, int64_t H_total,
-              optional<Tensor> sbias, int64_t sbias_sb, int64_t sbias_sh) {
+              optional<Tensor> sbias, int64_t sbias_sb, int64_t sbias_sh, optional<Tensor> seg_lo,
+              optional<Tensor> seg_hi) {
   TORCH_CHECK(D == 64 || D == 128, "flash attention supports head_dim 64/128");
   TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.numel() >= ffk::attn_bwd_workspace_floats(B, H, Sq, Sk, D),
               "attn_bwd: workspace too small");
@@ -860,6 +906,7 @@ bool attn_bwd(Tensor q, std::vector<int64_t> qs, Tensor k, std::vector<int64_t> 
   a.key_lens = attn_key_lens(key_lens, q, B);
   attn_drop_args(a, q, drop_thr, rng_step, rng_seed, b0, h0, H_total, H);
   attn_sbias_args(a, q, sbias, sbias_sb, sbias_sh, B, H, Sq, Sk);
+  attn_seg_args(a, q, seg_lo, seg_hi, B, Sq, Sk);
   return ffk::attn_bwd(a, cur_stream());
 }
 
@@ -1230,14 +1277,17 @@ PYBIND11_MODULE(_C, m) {
         py::arg("D"), py::arg("scale"), py::arg("causal"), py::arg("key_lens") = py::none(),
         py::arg("drop_thr") = 0, py::arg("rng_step") = py::none(), py::arg("rng_seed") = 0, py::arg("b0") = 0,
         py::arg("h0") = 0, py::arg("H_total") = 0, py::arg("sbias") = py::none(), py::arg("sbias_sb") = 0,
-        py::arg("sbias_sh") = 0);
+        py::arg("sbias_sh") = 0, py::arg("seg_lo") = py::none(), py::arg("seg_hi") = py::none());
   m.def("attn_bwd", &attn_bwd, py::arg("q"), py::arg("qs"), py::arg("k"), py::arg("ks"), py::arg("v"), py::arg("vs"),
         py::arg("o"), py::arg("os"), py::arg("dout"), py::arg("dos"), py::arg("lse"), py::arg("dq"), py::arg("dqs"),
         py::arg("dk"), py::arg("dks"), py::arg("dv"), py::arg("dvs"), py::arg("ws"), py::arg("B"), py::arg("H"),
         py::arg("Sq"), py::arg("Sk"), py::arg("D"), py::arg("scale"), py::arg("causal"),
         py::arg("dbias") = py::none(), py::arg("key_lens") = py::none(), py::arg("drop_thr") = 0,
         py::arg("rng_step") = py::none(), py::arg("rng_seed") = 0, py::arg("b0") = 0, py::arg("h0") = 0,
-        py::arg("H_total") = 0, py::arg("sbias") = py::none(), py::arg("sbias_sb") = 0, py::arg("sbias_sh") = 0);
+        py::arg("H_total") = 0, py::arg("sbias") = py::none(), py::arg("sbias_sb") = 0, py::arg("sbias_sh") = 0,
+        py::arg("seg_lo") = py::none(), py::arg("seg_hi") = py::none());
+  m.def("attn_seg_bounds", &attn_seg_bounds);
+  m.def("segment_mask_f32", &segment_mask_f32);
   m.def("attn_dropout_f32", &attn_dropout_f32);
   m.def("attn_dropout_mask", &attn_dropout_mask);
   m.def("attn_bwd_ws", &attn_bwd_ws);

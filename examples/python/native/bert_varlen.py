@@ -8,10 +8,18 @@ mean over the real tokens. `--clip-grad-norm C` is FFConfig's flag: it goes thro
 optimizer, which then clips the global gradient norm to C on the device. `--optimizer lamb` trains
 with LAMB (decoupled weight decay, one trust ratio per weight) in place of Adam.
 
+`--pack` trains the same corpus packed (flexflow_amd/utils/packing.py): the sentences are put back to
+back into rows of `--seq-length` tokens, first-fit-decreasing; the loader feeds per-token
+`segment_ids` and positions that restart at every sentence, attention stays inside a sentence, and the
+tail of a row is padding (label -100, `ignore_index=-100, loss_reduction="valid"`). A step then has
+the same batch of rows but nearly every token in it is real, so the corpus takes about half the steps.
+Both modes print tokens/s over the real tokens.
+
     python examples/python/native/bert_varlen.py -b 8 --seq-length 64 --iterations 20
     python examples/python/native/bert_varlen.py -b 8 --seq-length 64 --iterations 20 --ignore-pad-labels
     python examples/python/native/bert_varlen.py -b 8 --seq-length 64 --ignore-pad-labels --clip-grad-norm 1.0
     python examples/python/native/bert_varlen.py -b 8 --seq-length 64 --ignore-pad-labels --optimizer lamb
+    python examples/python/native/bert_varlen.py -b 8 --seq-length 64 --iterations 20 --pack
 """
 import argparse
 import sys
@@ -30,11 +38,14 @@ def top_level_task(argv=None):
     ap.add_argument("--min-length", type=int, default=8)
     ap.add_argument("--ignore-pad-labels", action="store_true")
     ap.add_argument("--optimizer", choices=["adam", "lamb"], default="adam")
+    ap.add_argument("--pack", action="store_true")
     args, rest = ap.parse_known_args(sys.argv[1:] if argv is None else argv)
     ffconfig = FFConfig(rest)
     ffmodel = FFModel(ffconfig)
     b, s = ffconfig.batch_size, args.seq_length
     bc = BertConfig.tiny(s)
+    if args.pack:
+        return run_packed(args, ffconfig, ffmodel, bc)
     lengths = ffmodel.create_tensor([b], DataType.DT_INT32, name="key_lengths")
     ids, pos, _ = build_bert(ffmodel, b, bc, key_lengths=lengths)
     ffmodel.optimizer = LAMBOptimizer(ffmodel, 1e-3) if args.optimizer == "lamb" else AdamOptimizer(ffmodel, 1e-3)
@@ -65,12 +76,50 @@ def top_level_task(argv=None):
     run_time = 1e-6 * (ffconfig.get_current_time() - ts)
     print("bert-tiny varlen: %d iterations, mean length %.1f of %d, %.4fs, THROUGHPUT = %.2f samples/s, loss %.4f" %
           (args.iterations, lens.mean(), s, run_time, b * args.iterations / run_time, pm.get_loss()))
+    print("padded: %d rows per step, fill ratio %.3f, %.1f tokens/s" %
+          (b, lens.sum() / float(n * s), lens.sum() / run_time))
     if args.ignore_pad_labels:
         print("pad labels ignored: loss is the mean over %d real tokens, accuracy %.2f%%" %
               (pm.train_all, pm.get_accuracy()))
     if ffmodel.optimizer.clip_norm:  # --clip-grad-norm, taken from the config by the optimizer
         print("gradient norm clipped to %g: the last step's norm before clipping was %.4f" %
               (ffmodel.optimizer.clip_norm, ffmodel.get_grad_norm()))
+    return pm
+
+
+def run_packed(args, ffconfig, ffmodel, bc):
+    """The corpus of the padded run (same seed, same sentences and labels), packed into rows."""
+    from flexflow_amd.utils.packing import fill_ratio, pack_sequences, packed_arrays
+    b, s = ffconfig.batch_size, args.seq_length
+    seg = ffmodel.create_tensor([b, s], DataType.DT_INT32, name="segment_ids")
+    ids, pos, _ = build_bert(ffmodel, b, bc, segment_ids=seg)
+    ffmodel.optimizer = LAMBOptimizer(ffmodel, 1e-3) if args.optimizer == "lamb" else AdamOptimizer(ffmodel, 1e-3)
+    ffmodel.compile(loss_type=LossType.LOSS_SPARSE_CATEGORICAL_CROSSENTROPY, metrics=[MetricsType.METRICS_ACCURACY],
+                    ignore_index=-100, loss_reduction="valid")
+    rng = np.random.default_rng(0)
+    n = b * args.iterations
+    lens = rng.integers(min(args.min_length, s), s + 1, n).astype(np.int32)
+    tok = rng.integers(1, bc.vocab, (n, s)).astype(np.int32)
+    toks = [tok[i, :lens[i]] for i in range(n)]
+    labs = [(t + 1) % bc.vocab for t in toks]
+    rows = pack_sequences(lens, s)
+    fill = fill_ratio(rows, lens, s)
+    steps = (len(rows) + b - 1) // b
+    rows += [[] for _ in range(steps * b - len(rows))]  # the last step's spare rows are all padding
+    p_ids, p_pos, p_seg, p_lab = packed_arrays(rows, toks, labs, s)
+    loaders = [ffmodel.create_data_loader(ids, p_ids), ffmodel.create_data_loader(pos, p_pos),
+               ffmodel.create_data_loader(seg, p_seg), ffmodel.create_data_loader(ffmodel.label_tensor, p_lab)]
+    ffmodel.init_layers()
+    ts = ffconfig.get_current_time()
+    for _ in range(steps):
+        for dl in loaders:
+            dl.next_batch(ffmodel)
+        ffmodel.train_step()
+    pm = ffmodel.get_perf_metrics()
+    run_time = 1e-6 * (ffconfig.get_current_time() - ts)
+    print("bert-tiny packed: %d sentences in %d steps, mean length %.1f of %d, %.4fs, THROUGHPUT = %.2f samples/s, "
+          "loss %.4f" % (n, steps, lens.mean(), s, run_time, n / run_time, pm.get_loss()))
+    print("packed: %d rows per step, fill ratio %.3f, %.1f tokens/s" % (b, fill, lens.sum() / run_time))
     return pm
 
 

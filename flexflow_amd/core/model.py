@@ -75,6 +75,13 @@ def _ensure_dist(config: FFConfig):
         torch.cuda.set_device(config.local_rank % torch.cuda.device_count())
 
 
+def _check_segment_args(what, key_lengths, attn_bias):
+    if key_lengths is not None:
+        raise ValueError(f"{what}: segment_ids cannot be combined with key_lengths (mark padding with a negative id)")
+    if attn_bias is not None:
+        raise ValueError(f"{what}: segment_ids cannot be combined with attn_bias")
+
+
 class FFModel:
     def __init__(self, ffconfig: Optional[FFConfig] = None):
         self.config = ffconfig or FFConfig()
@@ -288,8 +295,11 @@ class FFModel:
 
     def multihead_attention(self, query, key, value, embed_dim, num_heads, kdim=0, vdim=0, dropout=0.0, bias=True,
                             add_bias_kv=False, add_zero_attn=False, kernel_initializer=None, causal=False, name=None,
-                            key_lengths=None, attn_bias=None):
-        """key_lengths: optional int32 tensor [batch] (or [batch, 1]) of a right-padded batch: sample b
+                            key_lengths=None, attn_bias=None, segment_ids=None):
+        """segment_ids: optional int32 tensor [batch, seq] of packed rows (several sequences back to back):
+        attention stays inside a run of equal ids >= 0, a negative id marks padding; needs Sq == Sk and
+        goes with neither key_lengths nor attn_bias (ops/attention.py).
+        key_lengths: optional int32 tensor [batch] (or [batch, 1]) of a right-padded batch: sample b
         attends to its first key_lengths[b] keys only (ops/attention.py).
         attn_bias: optional float tensor [1|batch, 1|heads, Sq, Sk] added to the scaled scores before the
         softmax (ALiBi, relative-position biases, 0 / -inf masks); it takes no gradient (ops/attention.py).
@@ -299,6 +309,10 @@ class FFModel:
             raise ValueError(f"multihead_attention: dropout must be in [0, 1), got {dropout}")
         ins = [query, key, value] + ([key_lengths] if key_lengths is not None else [])
         kw = {}
+        if segment_ids is not None:  # where the key lengths would sit, marked by the attribute
+            _check_segment_args("multihead_attention", key_lengths, attn_bias)
+            ins.append(segment_ids)
+            kw["segment_ids"] = True
         if attn_bias is not None:  # the last input, marked by the attribute; a graph without it is built as ever
             ins.append(attn_bias)
             kw["attn_bias"] = True
@@ -308,16 +322,20 @@ class FFModel:
                          causal=causal, self_attn=(query is key and key is value), **kw).outputs[0]
 
     def scaled_dot_product_attention(self, q, k, v, attn_bias=None, key_lengths=None, scale=None, causal=False,
-                                     dropout=0.0, name=None):
+                                     dropout=0.0, name=None, segment_ids=None):
         """softmax(scale * q.k^T + attn_bias) . v on projected heads: q [B, H, Sq, D], k [B, H, Sk, D],
         v [B, H, Sk, Dv] -> [B, H, Sq, Dv] (extension; ops/sdpa.py). attn_bias, key_lengths, causal and
-        dropout are those of multihead_attention; scale=None means 1 / sqrt(D)."""
+        dropout and segment_ids are those of multihead_attention; scale=None means 1 / sqrt(D)."""
         if not 0.0 <= float(dropout) < 1.0:
             raise ValueError(f"scaled_dot_product_attention: dropout must be in [0, 1), got {dropout}")
         ins, kw = [q, k, v], {}
         if key_lengths is not None:
             ins.append(key_lengths)
             kw["key_lengths"] = True
+        if segment_ids is not None:
+            _check_segment_args("scaled_dot_product_attention", key_lengths, attn_bias)
+            ins.append(segment_ids)
+            kw["segment_ids"] = True
         if attn_bias is not None:
             ins.append(attn_bias)
             kw["attn_bias"] = True

@@ -972,6 +972,75 @@ def attn_key_lens(key_lens, B, device):
     return kl
 
 
+# ---- packed sequences: per-token segment ids
+def attn_seg_bounds_ref(ids):
+    """lo, hi (int32, ids' shape) of segment ids [B, S], on ids' device with tensor ops only: a segment
+    is a maximal run of equal ids >= 0 and [lo[b, i], hi[b, i]) is the run position i lies in; a
+    padding position (id < 0) gets the empty run lo = hi = i. What attn_seg_bounds computes on the
+    device (attn_seg_bounds_kernel)."""
+    B, S = ids.shape
+    pos = torch.arange(S, device=ids.device, dtype=torch.int64).expand(B, S)
+    start = torch.ones(B, S, dtype=torch.bool, device=ids.device)
+    start[:, 1:] = ids[:, 1:] != ids[:, :-1]
+    lo = torch.cummax(torch.where(start, pos, torch.zeros_like(pos)), 1).values
+    end = torch.ones(B, S, dtype=torch.bool, device=ids.device)  # a run ends behind position i
+    end[:, :-1] = start[:, 1:]
+    nxt = torch.where(end, pos + 1, torch.full_like(pos, S))
+    hi = torch.flip(torch.cummin(torch.flip(nxt, (1,)), 1).values, (1,))
+    pad = ids < 0
+    return torch.where(pad, pos, lo).to(torch.int32), torch.where(pad, pos, hi).to(torch.int32)
+
+
+def attn_seg_bounds(ids):
+    """lo, hi of segment ids (int32 [B, S]): the bounds kernel on a native device (one launch, nothing
+    read on the host), attn_seg_bounds_ref elsewhere."""
+    if not native(ids):
+        return attn_seg_bounds_ref(ids)
+    if ids.dim() != 2 or ids.dtype != torch.int32:
+        raise ValueError(f"attn_seg_bounds: ids must be int32 [B, S], got {ids.dtype} {list(ids.shape)}")
+    ids = ids.contiguous()
+    lo, hi = torch.empty_like(ids), torch.empty_like(ids)
+    ext().attn_seg_bounds(ids, lo, hi)
+    return lo, hi
+
+
+def attn_segments(segment_ids, B, S, device):
+    """Per-token segment ids of packed rows as the attention paths take them: (ids, lo, hi), ids a
+    contiguous int32 [B, S] on `device`, lo / hi its run bounds (attn_seg_bounds) on a native device
+    and None elsewhere (the reference path builds its mask from ids), or None. Nothing here reads a
+    value on the host."""
+    if segment_ids is None:
+        return None
+    ids = segment_ids.reshape(segment_ids.shape[0], -1) if segment_ids.dim() == 3 else segment_ids
+    if tuple(ids.shape) != (B, S):
+        raise ValueError(f"segment_ids: expected [{B}, {S}] (one id per token), got {list(segment_ids.shape)}")
+    if ids.dtype != torch.int32 or ids.device != device or not ids.is_contiguous():
+        ids = ids.to(device=device, dtype=torch.int32).contiguous()
+    lo, hi = attn_seg_bounds(ids) if native(ids) else (None, None)
+    return ids, lo, hi
+
+
+def segment_mask_ref(ids, causal=False):
+    """bool [B, S, S]: query i sees key j (same run of equal ids >= 0; j <= i with causal)."""
+    lo, hi = attn_seg_bounds_ref(ids)
+    j = torch.arange(ids.shape[1], device=ids.device)[None, None, :]
+    m = (j >= lo[:, :, None]) & (j < hi[:, :, None])
+    if causal:
+        m = m & (j <= torch.arange(ids.shape[1], device=ids.device)[None, :, None])
+    return m
+
+
+def _seg_kw(segments, key_lens, bias, Sq, Sk):
+    """segments (attn_segments) -> the bindings' keyword arguments."""
+    if segments is None:
+        return {}
+    if key_lens is not None or bias is not None:
+        raise ValueError("attention: segment_ids cannot be combined with key_lengths or attn_bias")
+    if segments[1] is None:
+        raise ValueError("attention: the segment bounds are missing (attn_segments on a native device)")
+    return dict(seg_lo=segments[1], seg_hi=segments[2])
+
+
 # ---- attention dropout: csrc/kernels/attn_dropout.h is the device definition, this is its mirror
 _ADROP_GOLD = 0x9E3779B97F4A7C15
 _ADROP_STEP = 0xD1B54A32D192ED03
@@ -1073,20 +1142,25 @@ def _sbias_kw(bias, B, H, Sq, Sk, device):
     return dict(sbias=bias, sbias_sb=Hb * Sq * Sk if Bb > 1 else 0, sbias_sh=Sq * Sk if Hb > 1 else 0)
 
 
-def flash_attn_fwd(q, qs, k, ks, v, vs, o, os_, B, H, Sq, Sk, D, scale, causal, key_lens=None, drop=None, bias=None):
-    """key_lens: optional int32 [B] device tensor; key j of sample b is attended iff j < key_lens[b]
+def flash_attn_fwd(q, qs, k, ks, v, vs, o, os_, B, H, Sq, Sk, D, scale, causal, key_lens=None, drop=None, bias=None,
+                   segments=None):
+    """segments: optional packed-sequence runs (attn_segments): attention stays inside a token's own
+    run, a padding position gives o = 0, lse = +inf. key_lens: optional int32 [B] device tensor; key j of sample b is attended iff j < key_lens[b]
     (a length of 0: o = 0, lse = +inf). drop: optional attention dropout (thr, rng_step, rng_seed, b0,
     h0, H_total), see _drop_kw / attn_dropout_keep_ref; lse is that of the undropped softmax.
     bias: optional score bias [1|B, 1|H, Sq, Sk] (attn_score_bias)."""
     lse = torch.empty(B * H * Sq, device=q.device, dtype=torch.float32)
     ext().attn_fwd(q, qs, k, ks, v, vs, o, os_, lse, B, H, Sq, Sk, D, scale, causal,
-                   attn_key_lens(key_lens, B, q.device), **_drop_kw(drop), **_sbias_kw(bias, B, H, Sq, Sk, q.device))
+                   attn_key_lens(key_lens, B, q.device), **_drop_kw(drop), **_sbias_kw(bias, B, H, Sq, Sk, q.device),
+                   **_seg_kw(segments, key_lens, bias, Sq, Sk))
     return lse
 
 
 def flash_attn_bwd(q, qs, k, ks, v, vs, o, os_, do, dos, lse, dq, dqs, dk, dks, dv, dvs, B, H, Sq, Sk, D, scale,
-                   causal, dbias=None, key_lens=None, drop=None, bias=None):
-    """key_lens: as in flash_attn_fwd; dk / dv rows at or past a sample's length are written as zeros.
+                   causal, dbias=None, key_lens=None, drop=None, bias=None, segments=None):
+    """segments: as in flash_attn_fwd; the dq / dk / dv rows of padding positions are written as zeros,
+    and the segment kernels never fuse the bias gradient (returns False).
+    key_lens: as in flash_attn_fwd; dk / dv rows at or past a sample's length are written as zeros.
     drop: as in flash_attn_fwd, with the counter value the forward saw; the dropout kernels never fuse
     the bias gradient (returns False). bias: the forward's score bias; it takes no gradient, and the
     score bias kernels never fuse the (QKV projection's) bias gradient either.
@@ -1099,7 +1173,7 @@ def flash_attn_bwd(q, qs, k, ks, v, vs, o, os_, do, dos, lse, dq, dqs, dk, dks, 
     ws = DeviceContext.get(q.device).workspace("attn_bwd", X.attn_bwd_ws(B, H, Sq, Sk, D))
     return bool(X.attn_bwd(q, qs, k, ks, v, vs, o, os_, do, dos, lse, dq, dqs, dk, dks, dv, dvs, ws, B, H, Sq, Sk, D,
                            scale, causal, dbias, attn_key_lens(key_lens, B, q.device), **_drop_kw(drop),
-                           **_sbias_kw(bias, B, H, Sq, Sk, q.device)))
+                           **_sbias_kw(bias, B, H, Sq, Sk, q.device), **_seg_kw(segments, key_lens, bias, Sq, Sk)))
 
 
 # ---------------------------------------------------------------------------- layer norm
@@ -2334,7 +2408,7 @@ def attn_f32_supported(x) -> bool:
 
 
 def attn_f32_fwd(q, qs, k, ks, v, vs, o, os_, B, H, Sq, Sk, kd, vd, scale, causal, key_lens=None, drop=None,
-                 bias=None):
+                 bias=None, segments=None):
     """fp32 attention on our kernels, per sample: S = Q.K^T (f32 MFMA GEMM, heads as the batch),
     causal mask, key-length mask (key_lens: int32 [B] on the device, columns >= key_lens[b] set to
     -inf there), row softmax(scale * S) (softmax.hip), the same columns of P set to 0 (a sample of
@@ -2343,9 +2417,12 @@ def attn_f32_fwd(q, qs, k, ks, v, vs, o, os_, B, H, Sq, Sk, kd, vd, scale, causa
     the P returned is the undropped one, for softmax_bwd.
     bias (attn_score_bias): S = scale * S + bias[b] (score_bias_f32) ahead of the masks, the softmax then
     runs with scale 1; P is set to 0 where S is -inf, so a row with no key left has P = 0.
+    segments (attn_segments): S is set to -inf outside the query's run (segment_mask_f32) and P to 0
+    there, so a padding row has P = 0.
     Returns P [B, H, Sq, Sk]."""
     X = ext()
     dkw = _drop_kw(drop)
+    skw = _seg_kw(segments, key_lens, bias, Sq, Sk)
     bias = attn_score_bias(bias, B, H, Sq, Sk, q.device)
     if bias is not None:
         bflat, bsb = bias.reshape(-1), (bias.shape[1] * Sq * Sk if bias.shape[0] > 1 else 0)
@@ -2364,8 +2441,10 @@ def attn_f32_fwd(q, qs, k, ks, v, vs, o, os_, B, H, Sq, Sk, kd, vd, scale, causa
             X.causal_mask_f32(S, Sq, Sk)
         if key_lens is not None:
             X.key_len_mask_f32(S, key_lens, b, Sk, float("-inf"))
+        if skw:
+            X.segment_mask_f32(S, skw["seg_lo"], skw["seg_hi"], b, H, Sq, Sk)
         X.softmax_fwd(S, P[b], H * Sq, Sk, 1.0 if bias is not None else scale)
-        if bias is not None:
+        if bias is not None or skw:
             X.masked_prob_zero_f32(P[b], S)
         if key_lens is not None:  # a sample without keys: its all -inf rows came out NaN, P is 0 there
             X.key_len_mask_f32(P[b], key_lens, b, Sk, 0.0)
@@ -2380,14 +2459,14 @@ def attn_f32_fwd(q, qs, k, ks, v, vs, o, os_, B, H, Sq, Sk, kd, vd, scale, causa
 
 
 def attn_f32_bwd(q, qs, k, ks, v, vs, do, dos, P, dq, dk, dv, B, H, Sq, Sk, kd, vd, scale, key_lens=None, drop=None,
-                 bias=None):
+                 bias=None, segments=None):
     """Backward of attn_f32_fwd: dP = dO.V^T, dS = scale * P * (dP - rowsum(dP * P)), dQ = dS.K,
     dK = dS^T.Q, dV = P^T.dO (dq / dk / dv share q / k / v's strides). key_lens needs no work here:
     the forward left P = 0 in the masked columns, so dS is 0 there and the dK / dV rows at or past a
     sample's length come out as zeros (all of a length-0 sample's gradients do). drop (with the
     counter value of the forward): dP and the P of the dV GEMM go through attn_dropout_f32. bias needs
     no work either: it is inside P, dS = scale * P * (..) stays the gradient of the raw q.k, and the
-    bias itself takes no gradient."""
+    bias itself takes no gradient. segments need none: P is 0 outside the runs."""
     X = ext()
     dkw = _drop_kw(drop)
     Pd = torch.empty(H, Sq, Sk, device=q.device, dtype=torch.float32) if dkw else None

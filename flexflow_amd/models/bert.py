@@ -62,10 +62,12 @@ class BertConfig:
         return 6.0 * mm * S + 3.0 * att
 
 
-def build_bert(ff, batch: int, cfg: BertConfig, key_lengths=None):
+def build_bert(ff, batch: int, cfg: BertConfig, key_lengths=None, segment_ids=None):
     """Returns (ids_tensor, pos_tensor, output). Output: [batch, seq, vocab] probabilities.
     key_lengths: optional int32 [batch] tensor (ff.create_tensor) with the number of real tokens of
-    each right-padded sample; every layer's attention then leaves the pad positions out as keys."""
+    each right-padded sample; every layer's attention then leaves the pad positions out as keys.
+    segment_ids: optional int32 [batch, seq] tensor of packed rows (utils/packing.py): every layer's
+    attention stays inside a token's own sequence; position_ids then restart at each sequence."""
     S, H = cfg.seq, cfg.hidden
     ids = ff.create_tensor([batch, S], DataType.DT_INT32, name="input_ids")
     pos = ff.create_tensor([batch, S], DataType.DT_INT32, name="position_ids")
@@ -75,7 +77,7 @@ def build_bert(ff, batch: int, cfg: BertConfig, key_lengths=None):
     x = ff.layer_norm(x, [-1], name="emb_ln")
     for l in range(cfg.layers):
         a = ff.multihead_attention(x, x, x, H, cfg.heads, dropout=cfg.attn_dropout, name=f"l{l}_attn",
-                                   key_lengths=key_lengths)
+                                   key_lengths=key_lengths, segment_ids=segment_ids)
         if cfg.dropout > 0:
             a = ff.dropout(a, cfg.dropout, l, name=f"l{l}_attn_drop")
         x = ff.layer_norm(ff.add(a, x, name=f"l{l}_res1"), [-1], name=f"l{l}_ln1")

@@ -17,7 +17,7 @@ iff j < L_b (and j <= q with `causal`). Every query row is still computed (as wi
 key_padding_mask); L_b = 0 gives zero output rows and zero gradients. The lengths are read on the
 device only, by every path (flash, zero-padded head dims, fp32 device, reference, CPU), so a step
 that takes them still captures into a graph. The pad positions' labels are left out of the loss by
-`FFModel.compile(ignore_index=...)`. Not covered: query-side skipping or packing.
+`FFModel.compile(ignore_index=...)`. Query-side skipping comes with packing (`segment_ids`, below).
 
 Optional last input `attn_bias` (attribute `attn_bias=True`; after `key_lengths` when both are given):
 a float tensor [1|B, 1|H, Sq, Sk] added to the scaled scores before the softmax, in every path — ALiBi,
@@ -30,6 +30,18 @@ problem. The bias takes no gradient, and with it the flash backward leaves the Q
 the projection's own backward. It is sharded with the batch where its first extent is B and with the
 heads where its second is H, replicated elsewhere. The same core (attn_core_fwd / attn_core_bwd) serves
 `scaled_dot_product_attention` (ops/sdpa.py).
+
+Packed sequences (attribute `segment_ids=True`; the 4th input, where the key lengths would sit): an
+int32 tensor [B, S] with one id per token of rows that hold several sequences back to back. A
+position is padding iff its id is negative; a segment is a maximal run of equal ids >= 0 (two runs
+that reuse an id are two segments; ids need not be sorted; pad runs may sit anywhere). Query i sees key
+j iff both lie in the same run (and j <= i with `causal`), so it needs Sq == Sk. A padding position
+gives a zero attention row (the output row is the output bias) and zero gradients, as a query and as
+a key. The ids are read on the device only, by every path: a bounds kernel (kernels.attn_seg_bounds)
+turns them into the run [lo, hi) of every position once per layer forward, and the flash kernels'
+SEG forms bound their mask tests and their tile loops by it, so tiles outside a workgroup's runs are
+never fetched. Not combined with `key_lengths` (a pad id of -1 says the same) or `attn_bias`. It takes
+no gradient, is sharded with the batch and replicated over the heads axis.
 
 Attention dropout (`dropout` = p in [0, 1), torch's `dropout_p`): in a training forward every
 attention probability is dropped with the effective rate p_eff = round(256 p) / 256 and the kept ones
@@ -63,8 +75,10 @@ def _pad_heads(t, st, B, S, H, d, Dp):
     return out
 
 
-def _attn_ref(q, k, v, scale, causal, key_lens=None, keep=None, keep_scale=1.0, bias=None):
-    """keep: optional bool [B, H, Sq, Sk] attention dropout mask (kernels.attn_dropout_keep_ref), the
+def _attn_ref(q, k, v, scale, causal, key_lens=None, keep=None, keep_scale=1.0, bias=None, segments=None):
+    """segments: optional segment ids [B, S] of packed rows (Sq == Sk == S): query i sees key j iff both
+    lie in one run of equal ids >= 0; the mask is built on the tensor's device from the run boundaries
+    (kernels.segment_mask_ref), and a padding row gets P = 0. keep: optional bool [B, H, Sq, Sk] attention dropout mask (kernels.attn_dropout_keep_ref), the
     kept probabilities scaled by keep_scale = 1 / (1 - p_eff). bias: optional score bias [1|B, 1|H, Sq,
     Sk], added to the scaled scores; a query row it leaves no key gets P = 0 (not the softmax's NaN)."""
     def drop(p):
@@ -76,6 +90,14 @@ def _attn_ref(q, k, v, scale, causal, key_lens=None, keep=None, keep_scale=1.0, 
         s = s + bias.to(device=s.device, dtype=s.dtype)
     if causal:
         s = s.masked_fill(torch.ones(Sq, Sk, dtype=torch.bool, device=s.device).triu(1), float("-inf"))
+    if segments is not None:
+        if key_lens is not None or bias is not None:
+            raise ValueError("attention: segment_ids cannot be combined with key_lengths or attn_bias")
+        see = K.segment_mask_ref(segments.to(s.device))[:, None]  # [B, 1, S, S]
+        dead = ~see.any(-1, keepdim=True)  # padding rows: finite scores first, then P = 0
+        s = torch.where(dead, torch.zeros_like(s), s.masked_fill(~see, float("-inf")))
+        p = torch.where(dead, torch.zeros_like(s), torch.softmax(s, -1))
+        return torch.einsum("bhqk,bhkd->bhqd", drop(p), v)
     if bias is not None:
         # the kernels' convention for every removed key and every row without keys, lengths included
         if key_lens is not None:
@@ -104,17 +126,18 @@ def _view4(t, st, B, H, S, d):
     return t.as_strided((B, H, S, d), (st[0], st[1], st[2], 1))
 
 
-def attn_core_fwd(s, name, qv, qs, kv, ks, vv, vs, o, os_, B, Hl, Sq, Sk, kd, vd, scale, causal, kl, drop, bias, keep_ref):
+def attn_core_fwd(s, name, qv, qs, kv, ks, vv, vs, o, os_, B, Hl, Sq, Sk, kd, vd, scale, causal, kl, drop, bias, keep_ref,
+                  seg=None):
     """softmax(scale q.k + bias, masks) v of MultiHeadAttention and ScaledDotProductAttention: q / k / v
     / o are buffers read and written through their (batch, head, row) element strides qs / ks / vs /
     os_ with contiguous head dims. Picks the path (flash kernels, head dims zero-padded to 64 / 128,
     fp32 device kernels, fp32 PyTorch reference / CPU) and leaves in `s` what attn_core_bwd needs of
     it. kl: key lengths (kernels.attn_key_lens) or None; drop: attention dropout as the kernels take it
     or None; bias: score bias (kernels.attn_score_bias) or None; keep_ref(): the dropout mask for the
-    reference path."""
+    reference path; seg: packed-sequence runs (kernels.attn_segments) or None."""
     if K.attn_supported(qv, kd) and kd == vd:
         s["lse"] = K.flash_attn_fwd(qv, qs, kv, ks, vv, vs, o, os_, B, Hl, Sq, Sk, kd, scale, causal, key_lens=kl,
-                                    drop=drop, bias=bias)
+                                    drop=drop, bias=bias, segments=seg)
     elif K.attn_padded_dim(qv, kd, vd):
         # head dims the MFMA kernels have no instance for (e.g. 16, 32, 80, 96): zero-pad Q, K,
         # V to the next instance (64 / 128). Zero columns add nothing to Q.K^T and give zero
@@ -126,13 +149,13 @@ def attn_core_fwd(s, name, qv, qs, kv, ks, vv, vs, o, os_, B, Hl, Sq, Sk, kd, vd
         pst = [Sq * Hl * Dp, Dp, Hl * Dp]
         kst = [Sk * Hl * Dp, Dp, Hl * Dp]
         lse = K.flash_attn_fwd(pq, pst, pk, kst, pv, kst, po, pst, B, Hl, Sq, Sk, Dp, scale, causal, key_lens=kl,
-                               drop=drop, bias=bias)
+                               drop=drop, bias=bias, segments=seg)
         _view4(o, os_, B, Hl, Sq, vd).copy_(po[..., :vd].permute(0, 2, 1, 3))
         s.update(lse=lse, pad=(Dp, pq, pk, pv, po))
     elif K.attn_f32_supported(qv) and os.environ.get("FF_ATTN_REF_FALLBACK") != "1":
         # --dtype fp32 on the device: f32 MFMA GEMMs + causal mask + row softmax, our kernels
         s["P"] = K.attn_f32_fwd(qv, qs, kv, ks, vv, vs, o.view(-1), os_, B, Hl, Sq, Sk, kd, vd, scale, causal,
-                                key_lens=kl, drop=drop, bias=bias)
+                                key_lens=kl, drop=drop, bias=bias, segments=seg)
     else:
         if K.native(qv) and qv.dtype == torch.bfloat16 and os.environ.get("FF_ATTN_REF_FALLBACK") != "1":
             raise NotImplementedError(
@@ -145,11 +168,12 @@ def attn_core_fwd(s, name, qv, qs, kv, ks, vv, vs, o, os_, B, Hl, Sq, Sk, kd, vd
         if keep is not None:
             s["keep"] = keep
         _view4(o, os_, B, Hl, Sq, vd).copy_(
-            _attn_ref(q4, k4, v4, scale, causal, kl, keep, 256.0 / (256 - drop[0]) if drop else 1.0, bias))
+            _attn_ref(q4, k4, v4, scale, causal, kl, keep, 256.0 / (256 - drop[0]) if drop else 1.0, bias,
+                      seg[0] if seg is not None else None))
 
 
 def attn_core_bwd(s, qv, qs, kv, ks, vv, vs, o, os_, do, dos, dq, dk, dv, B, Hl, Sq, Sk, kd, vd, scale, causal, kl, drop,
-                  bias, dbq=None):
+                  bias, dbq=None, seg=None):
     """Backward of attn_core_fwd on the path it took: dq / dk / dv (buffers with q / k / v's strides)
     from do (strides dos) and what the forward left in `s`. dbq: the fp32 [3*H*D] bias gradient of a fused
     QKV projection the flash kernel may add into; returns whether it did."""
@@ -161,24 +185,26 @@ def attn_core_bwd(s, qv, qs, kv, ks, vv, vs, o, os_, do, dos, dq, dk, dv, B, Hl,
         pst = [Sq * Hl * Dp, Dp, Hl * Dp]
         kst = [Sk * Hl * Dp, Dp, Hl * Dp]
         K.flash_attn_bwd(pq, pst, pk, kst, pv, kst, po, pst, pdo, pst, s["lse"], pdq, pst, pdk, kst, pdv, kst,
-                         B, Hl, Sq, Sk, Dp, scale, causal, key_lens=kl, drop=drop, bias=bias)
+                         B, Hl, Sq, Sk, Dp, scale, causal, key_lens=kl, drop=drop, bias=bias, segments=seg)
         for g, st, pg, S_, d in ((dq, qs, pdq, Sq, kd), (dk, ks, pdk, Sk, kd), (dv, vs, pdv, Sk, vd)):
             _view4(g, st, B, Hl, S_, d).copy_(pg[..., :d].permute(0, 2, 1, 3))
     elif "lse" in s:
         if dbq is not None:
             return K.flash_attn_bwd(qv, qs, kv, ks, vv, vs, o, os_, do, dos, s["lse"], dq, qs, dk, ks, dv, vs,
-                                    B, Hl, Sq, Sk, kd, scale, causal, dbias=dbq, key_lens=kl, drop=drop, bias=bias)
+                                    B, Hl, Sq, Sk, kd, scale, causal, dbias=dbq, key_lens=kl, drop=drop, bias=bias,
+                                    segments=seg)
         K.flash_attn_bwd(qv, qs, kv, ks, vv, vs, o, os_, do, dos, s["lse"], dq, qs, dk, ks, dv, vs,
-                         B, Hl, Sq, Sk, kd, scale, causal, key_lens=kl, drop=drop, bias=bias)
+                         B, Hl, Sq, Sk, kd, scale, causal, key_lens=kl, drop=drop, bias=bias, segments=seg)
     elif "P" in s:
         K.attn_f32_bwd(qv, qs, kv, ks, vv, vs, do.contiguous().view(-1), dos, s["P"], dq.view(-1), dk.view(-1),
-                       dv.view(-1), B, Hl, Sq, Sk, kd, vd, scale, key_lens=kl, drop=drop, bias=bias)
+                       dv.view(-1), B, Hl, Sq, Sk, kd, vd, scale, key_lens=kl, drop=drop, bias=bias, segments=seg)
     else:
         q4 = _view4(qv, qs, B, Hl, Sq, kd).detach().float().requires_grad_()
         k4 = _view4(kv, ks, B, Hl, Sk, kd).detach().float().requires_grad_()
         v4 = _view4(vv, vs, B, Hl, Sk, vd).detach().float().requires_grad_()
         with torch.enable_grad():
-            out = _attn_ref(q4, k4, v4, scale, causal, kl, s.get("keep"), 256.0 / (256 - drop[0]) if drop else 1.0, bias)
+            out = _attn_ref(q4, k4, v4, scale, causal, kl, s.get("keep"), 256.0 / (256 - drop[0]) if drop else 1.0, bias,
+                            seg[0] if seg is not None else None)
         g4 = _view4(do, dos, B, Hl, Sq, vd).float()
         gq, gk, gv = torch.autograd.grad(out, (q4, k4, v4), g4)
         _view4(dq, qs, B, Hl, Sq, kd).copy_(gq)
@@ -215,6 +241,20 @@ def check_attn_bias_dims(what, dims, B, H, Sq, Sk):
         raise ValueError(f"{what}: attn_bias must have shape [1|{B}, 1|{H}, {Sq}, {Sk}], got {list(d)}")
 
 
+def check_segment_ids_dims(what, in_dims, nb, B, Sq, Sk):
+    """infer-time checks of an attention layer built with segment_ids=True: the ids are the 4th input,
+    [B, S] for Sq == Sk == S, and there is neither a score bias nor (the builder's check) key lengths."""
+    if nb:
+        raise ValueError(f"{what}: segment_ids cannot be combined with attn_bias")
+    if len(in_dims) != 4:
+        raise ValueError(f"{what}: segment_ids=True takes query, key, value, segment_ids; got {len(in_dims)} inputs")
+    if Sq != Sk:
+        raise ValueError(f"{what}: segment_ids needs Sq == Sk (one segmentation for queries and keys), "
+                         f"got Sq {Sq}, Sk {Sk}")
+    if tuple(in_dims[3]) != (B, Sq):
+        raise ValueError(f"{what}: segment_ids must have shape [{B}, {Sq}], got {list(in_dims[3])}")
+
+
 def attn_bias_map(dims, B, H, batch_axis, heads_axis):
     """input_maps entry of a score bias: with the batch where its first extent is B, with the heads
     where its second is H, replicated elsewhere."""
@@ -232,7 +272,9 @@ class MultiHeadAttention(OpImpl):
             raise ValueError("multihead_attention takes query, key, value[, key_lengths][, attn_bias]; got "
                              f"{len(in_dims)} inputs" + (" with attn_bias=True" if nb else ""))
         q, k, v = in_dims[:3]
-        if len(in_dims) - nb == 4:
+        if attrs.get("segment_ids"):
+            check_segment_ids_dims("multihead_attention", in_dims, nb, q[0], q[1], k[1])
+        elif len(in_dims) - nb == 4:
             kl = tuple(in_dims[3])
             if kl not in ((q[0],), (q[0], 1)):
                 raise ValueError(f"key_lengths must have shape [{q[0]}] or [{q[0]}, 1], got {list(kl)}")
@@ -290,7 +332,7 @@ class MultiHeadAttention(OpImpl):
                                       self.attrs["num_heads"], 0, self.H_AXIS))
         return maps
 
-    def _has_key_lens(self):
+    def _has_key_lens(self):  # or segment ids: the same place and the same sharding
         return len(self.layer.inputs) - (1 if self.attrs.get("attn_bias") else 0) > 3
 
     def needs_input_grad(self, i):
@@ -333,7 +375,9 @@ class MultiHeadAttention(OpImpl):
         W = self._w(ws)
         B, Sq, _ = q_in.shape
         has_bias = bool(self.attrs.get("attn_bias"))
-        kl = K.attn_key_lens(xs[3], B, q_in.device) if len(xs) - has_bias > 3 else None
+        has_seg = bool(self.attrs.get("segment_ids"))
+        kl = K.attn_key_lens(xs[3], B, q_in.device) if len(xs) - has_bias > 3 and not has_seg else None
+        seg = K.attn_segments(xs[3], B, Sq, q_in.device) if has_seg else None
         Sk = k_in.shape[1]
         kd, vd = self.attrs["kdim"], self.attrs["vdim"]
         Hl = W["o_weight"].shape[1]
@@ -375,7 +419,7 @@ class MultiHeadAttention(OpImpl):
         os_ = [Sq * Hl * vd, vd, Hl * vd]
         bias = K.attn_score_bias(xs[-1], B, Hl, Sq, Sk, q_in.device) if has_bias else None
         attn_core_fwd(s, self.layer.name, qv, qs, kv, ks, vv, vs, o, os_, B, Hl, Sq, Sk, kd, vd, scale, causal, kl, drop,
-                      bias, lambda: self._keep_ref(ctx, drop, B, Hl, Sq, Sk, q_in.device))
+                      bias, lambda: self._keep_ref(ctx, drop, B, Hl, Sq, Sk, q_in.device), seg=seg)
         o2 = o.view(B * Sq, Hl * vd)
         wo = W["o_weight"].reshape(E, Hl * vd)
         if ctx.training:
@@ -383,7 +427,8 @@ class MultiHeadAttention(OpImpl):
         y, _ = K.linear_fwd(o2, wo, bo, K.ACT_NONE, False)
         if ctx.training:
             s.update(o=o, wo=wo, has_bo=bo is not None, shape=(B, Sq, Sk, Hl, kd, vd, E), fused=fused,
-                     qs=qs, ks=ks, vs=vs, os=os_, scale=scale, causal=causal, key_lens=kl, drop=drop, sbias=bias)
+                     qs=qs, ks=ks, vs=vs, os=os_, scale=scale, causal=causal, key_lens=kl, drop=drop, sbias=bias,
+                     seg=seg)
         return [y.view(B, Sq, E)]
 
     def overwrites_wgrad(self, i):
@@ -426,7 +471,8 @@ class MultiHeadAttention(OpImpl):
         if dbq is not None and not (dbq.dtype == torch.float32 and dbq.is_contiguous()):
             dbq = None
         bias_done = attn_core_bwd(s, qv, qs, kv, ks, vv, vs, o, os_, do, os_, dq, dk, dv, B, Hl, Sq, Sk, kd, vd, scale,
-                                  causal, kl, drop, s.get("sbias"), dbq.view(-1) if dbq is not None else None)
+                                  causal, kl, drop, s.get("sbias"), dbq.view(-1) if dbq is not None else None,
+                                  seg=s.get("seg"))
         if fused:
             dw = gw("qkv_weight")
             db = None if bias_done else gw("qkv_bias")

@@ -6,6 +6,8 @@ k [B, H, Sk, D], v [B, H, Sk, Dv] -> [B, H, Sq, Dv]. No weights. Inputs after q,
 (attribute `key_lengths=True`; int32 [B] or [B, 1]) and then `attn_bias` (attribute `attn_bias=True`;
 float [1|B, 1|H, Sq, Sk]), with the semantics of ops/attention.py: a -inf (or overflowing) bias element
 removes a key, a query row with no key left gives zeros, the bias and the lengths take no gradient.
+`segment_ids` (attribute `segment_ids=True`; int32 [B, S], the 4th input, for Sq == Sk == S) packs several
+sequences into a row as in ops/attention.py; not combined with `key_lengths` or `attn_bias`.
 `scale` defaults to 1 / sqrt(D); `causal` and `dropout` are those of multihead_attention (the same
 counter-based mask, drawn from global batch / head indices).
 
@@ -23,7 +25,7 @@ import torch
 from .. import kernels as K
 from ..type import DataType, OperatorType
 from .attention import (attn_bias_map, attn_core_bwd, attn_core_fwd, attn_drop_args, attn_keep_ref,
-                        check_attn_bias_dims)
+                        check_attn_bias_dims, check_segment_ids_dims)
 from .base import OpImpl, register
 
 
@@ -35,7 +37,10 @@ class ScaledDotProductAttention(OpImpl):
     @classmethod
     def infer(cls, attrs, in_dims, in_dtypes):
         nk, nb = (1 if attrs.get("key_lengths") else 0), (1 if attrs.get("attn_bias") else 0)
-        if len(in_dims) != 3 + nk + nb:
+        ns = 1 if attrs.get("segment_ids") else 0
+        if ns and nk:
+            raise ValueError("scaled_dot_product_attention: segment_ids cannot be combined with key_lengths")
+        if len(in_dims) != 3 + nk + nb + ns:
             raise ValueError("scaled_dot_product_attention takes q, k, v[, key_lengths][, attn_bias]; got "
                              f"{len(in_dims)} inputs for key_lengths={bool(nk)}, attn_bias={bool(nb)}")
         q, k, v = (tuple(d) for d in in_dims[:3])
@@ -44,6 +49,8 @@ class ScaledDotProductAttention(OpImpl):
         if q[:2] != k[:2] or q[:2] != v[:2] or q[3] != k[3] or k[2] != v[2]:
             raise ValueError(f"scaled_dot_product_attention: mismatched q {q}, k {k}, v {v} (no GQA / MQA broadcasting)")
         B, H, Sq, _ = q
+        if ns:
+            check_segment_ids_dims("scaled_dot_product_attention", in_dims, nb, B, Sq, k[2])
         if nk:
             kl = tuple(in_dims[3])
             if kl not in ((B,), (B, 1)):
@@ -68,7 +75,7 @@ class ScaledDotProductAttention(OpImpl):
     def input_maps(self):
         maps = [(0, 1, None, None)] * 3
         q = self.layer.inputs[0].dims
-        if self.attrs.get("key_lengths"):
+        if self.attrs.get("key_lengths") or self.attrs.get("segment_ids"):
             maps.append((0,) + (None,) * (len(self.layer.inputs[3].dims) - 1))
         if self.attrs.get("attn_bias"):
             maps.append(attn_bias_map(self.layer.inputs[-1].dims, q[0], q[1], 0, self.H_AXIS))
@@ -87,6 +94,7 @@ class ScaledDotProductAttention(OpImpl):
         has_kl, has_bias = bool(self.attrs.get("key_lengths")), bool(self.attrs.get("attn_bias"))
         kl = K.attn_key_lens(xs[3], B, q.device) if has_kl else None
         bias = K.attn_score_bias(xs[-1], B, Hl, Sq, Sk, q.device) if has_bias else None
+        seg = K.attn_segments(xs[3], B, Sq, q.device) if self.attrs.get("segment_ids") else None
         sc = self.attrs.get("scale")
         scale = 1.0 / math.sqrt(kd) if sc is None else float(sc)
         causal = bool(self.attrs.get("causal", False))
@@ -97,10 +105,10 @@ class ScaledDotProductAttention(OpImpl):
         os_ = [Hl * Sq * vd, Sq * vd, vd]
         o = torch.empty(B, Hl, Sq, vd, device=q.device, dtype=q.dtype)
         attn_core_fwd(s, self.layer.name, q.view(-1), qs, k.view(-1), ks, v.view(-1), vs, o, os_, B, Hl, Sq, Sk, kd, vd,
-                      scale, causal, kl, drop, bias, lambda: attn_keep_ref(self, ctx, drop, B, Hl, Sq, Sk, q.device))
+                      scale, causal, kl, drop, bias, lambda: attn_keep_ref(self, ctx, drop, B, Hl, Sq, Sk, q.device), seg=seg)
         if ctx.training:
             s.update(q=q, k=k, v=v, o=o, shape=(B, Hl, Sq, Sk, kd, vd), st=(qs, ks, vs, os_), scale=scale,
-                     causal=causal, key_lens=kl, drop=drop, sbias=bias)
+                     causal=causal, key_lens=kl, drop=drop, sbias=bias, seg=seg)
         return [o]
 
     def backward(self, ctx, douts):
@@ -111,7 +119,7 @@ class ScaledDotProductAttention(OpImpl):
         do = douts[0].contiguous()
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         attn_core_bwd(s, q.view(-1), qs, k.view(-1), ks, v.view(-1), vs, o, os_, do, os_, dq, dk, dv, B, Hl, Sq, Sk, kd,
-                      vd, s["scale"], s["causal"], s["key_lens"], s["drop"], s["sbias"])
+                      vd, s["scale"], s["causal"], s["key_lens"], s["drop"], s["sbias"], seg=s.get("seg"))
         ctx.saved.clear()
         return [dq, dk, dv] + [None] * (len(self.layer.inputs) - 3)
 

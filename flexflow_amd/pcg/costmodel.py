@@ -217,6 +217,9 @@ def fabricate_int_input(layer, i: int, shp, cfg: OpConfig, device) -> torch.Tens
     """A stand-in for integer input i of `layer` when its cost is measured: embedding indices over
     the local table, an attention layer's key lengths all equal to Sk (a dense batch: random small
     lengths would time a nearly empty attention), otherwise 0 / 1."""
+    if layer.op_type in (OperatorType.OP_MULTIHEAD_ATTENTION, OperatorType.OP_SDPA) and i == 3 and \
+            layer.attrs.get("segment_ids"):  # packed rows: one full-length segment per row
+        return torch.zeros(tuple(shp), device=device, dtype=torch.int32)
     if layer.op_type == OperatorType.OP_MULTIHEAD_ATTENTION and i == 3:
         return torch.full(tuple(shp), int(layer.inputs[1].dims[1]), device=device, dtype=torch.int32)
     if layer.op_type == OperatorType.OP_SDPA and i == 3:
