@@ -66,6 +66,18 @@ struct AttnArgs {
   // position gives o = 0, lse = +inf and zero dq / dk / dv rows.
   const int* seg_lo = nullptr;
   const int* seg_hi = nullptr;
+  // grouped-query / multi-query attention: Hkv key / value heads under H query heads, query head h
+  // reading KV head h / G with G = H / Hkv (torch's enable_gqa, repeat_interleave(G) over heads). 0 or
+  // H: every head has its own K / V, what the kernels did before. With 0 < Hkv < H the strides k_s*,
+  // v_s*, dk_s*, dv_s* run over the Hkv KV heads; everything else (lse, delta, dq, the dropout
+  // stream, the score bias, the dQ workspace) stays indexed by the query head. G is filled in by
+  // attn_fwd / attn_bwd. The backward then has every query head write its dK / dV contribution to
+  // kv_part ([2][B][H][Sk][D] bf16 in the workspace, behind the bias-gradient partials) and
+  // attn_kv_group_sum_kernel adds each group's G rows in fp32 into the caller's dk / dv; the fused
+  // bias gradient (dbp / dbias, laid out for [3][H][D]) is left to the caller.
+  int Hkv = 0;
+  int G = 1;
+  uint16_t* kv_part = nullptr;
 };
 
 // lo / hi [B][S] (int32) from segment ids [B][S]: a segment is a maximal run of equal ids >= 0 and
@@ -85,8 +97,10 @@ void attn_dropout_mask(uint8_t* out, int B, int H, int Sq, int Sk, int b0, int h
 
 void attn_fwd(AttnArgs a, hipStream_t st);
 bool attn_bwd(AttnArgs a, hipStream_t st);
-int64_t attn_bwd_workspace_floats(int B, int H, int Sq, int Sk, int D);
+// Hkv (0 or H: none) adds the two expanded dK / dV buffers of grouped-query attention
+int64_t attn_bwd_workspace_floats(int B, int H, int Sq, int Sk, int D, int Hkv = 0);
 int64_t attn_bwd_slab_floats(int B, int H, int Sq, int Sk, int D);  // offset of delta in the workspace
+int64_t attn_bwd_kv_part_floats(int B, int H, int Sq, int Sk, int D);  // offset of kv_part (16-B aligned)
 int attn_bwd_variant();
 void attn_set_bwd_variant(int v);
 int attn_fwd_variant();

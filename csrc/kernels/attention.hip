@@ -166,8 +166,9 @@ __global__ void __launch_bounds__(256, DMA ? (DROP || BIAS || SEG ? 3 : 4) : (D 
   const int q0 = qblk0 + wave * 32;
   const int qrow = q0 + (lane & 31);
   const bf16_t* Q = a.q + (int64_t)b * a.q_sb + (int64_t)hh * a.q_sh;
-  const bf16_t* K = a.k + (int64_t)b * a.k_sb + (int64_t)hh * a.k_sh;
-  const bf16_t* V = a.v + (int64_t)b * a.v_sb + (int64_t)hh * a.v_sh;
+  const int hk = a.G == 1 ? hh : hh / a.G;  // grouped-query attention: the KV head of query head hh
+  const bf16_t* K = a.k + (int64_t)b * a.k_sb + (int64_t)hk * a.k_sh;
+  const bf16_t* V = a.v + (int64_t)b * a.v_sb + (int64_t)hk * a.v_sh;
 
   bf16x8 qf[D / 16];
 #pragma unroll
@@ -470,8 +471,9 @@ __global__ void __launch_bounds__(256, 2) attn_fwd2_kernel(AttnArgs a) {
   const int qblk0 = (lid % nqb) * ROWS;
   const int q0 = qblk0 + wave * 32 * QB;  // rows q0 + 32 qb + (lane & 31)
   const bf16_t* Q = a.q + (int64_t)b * a.q_sb + (int64_t)hh * a.q_sh;
-  const bf16_t* K = a.k + (int64_t)b * a.k_sb + (int64_t)hh * a.k_sh;
-  const bf16_t* V = a.v + (int64_t)b * a.v_sb + (int64_t)hh * a.v_sh;
+  const int hk = a.G == 1 ? hh : hh / a.G;  // grouped-query attention: the KV head of query head hh
+  const bf16_t* K = a.k + (int64_t)b * a.k_sb + (int64_t)hk * a.k_sh;
+  const bf16_t* V = a.v + (int64_t)b * a.v_sb + (int64_t)hk * a.v_sh;
 
   bf16x8 qf[QB][D / 16];
 #pragma unroll
@@ -841,8 +843,9 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) attn_bwd_kernel(AttnArgs a, i
   const int kb0 = kblk * KB;
   const int key = kb0 + wave * 32 + (lane & 31);
   const bf16_t* Q = a.q + (int64_t)b * a.q_sb + (int64_t)hh * a.q_sh;
-  const bf16_t* K = a.k + (int64_t)b * a.k_sb + (int64_t)hh * a.k_sh;
-  const bf16_t* V = a.v + (int64_t)b * a.v_sb + (int64_t)hh * a.v_sh;
+  const int hk = a.G == 1 ? hh : hh / a.G;  // grouped-query attention: the KV head of query head hh
+  const bf16_t* K = a.k + (int64_t)b * a.k_sb + (int64_t)hk * a.k_sh;
+  const bf16_t* V = a.v + (int64_t)b * a.v_sb + (int64_t)hk * a.v_sh;
   const bf16_t* dO = a.dout + (int64_t)b * a.do_sb + (int64_t)hh * a.do_sh;
   const float* LSE = a.lse + (int64_t)bh * a.Sq;
   const float* DL = a.delta + (int64_t)bh * a.Sq;
@@ -1336,8 +1339,9 @@ __global__ void __launch_bounds__(512, 1) attn_bwd1b_kernel(AttnArgs a, int nkb,
   const int kb0 = kblk * KB;
   const int key = kb0 + wave * 32 + (lane & 31);
   const bf16_t* Q = a.q + (int64_t)b * a.q_sb + (int64_t)hh * a.q_sh;
-  const bf16_t* K = a.k + (int64_t)b * a.k_sb + (int64_t)hh * a.k_sh;
-  const bf16_t* V = a.v + (int64_t)b * a.v_sb + (int64_t)hh * a.v_sh;
+  const int hk = a.G == 1 ? hh : hh / a.G;  // grouped-query attention: the KV head of query head hh
+  const bf16_t* K = a.k + (int64_t)b * a.k_sb + (int64_t)hk * a.k_sh;
+  const bf16_t* V = a.v + (int64_t)b * a.v_sb + (int64_t)hk * a.v_sh;
   const bf16_t* dO = a.dout + (int64_t)b * a.do_sb + (int64_t)hh * a.do_sh;
   const float* DL = a.delta + (int64_t)bh * a.Sq;
   const float sl2 = a.scale * LOG2E;
@@ -1736,6 +1740,61 @@ __global__ void attn_dq_finish_kernel(AttnArgs a, int nkb) {
   }
 }
 
+// Grouped-query attention, G = H / Hkv > 1: dk[b][hkv][row] = sum_g part[0][b][hkv G + g][row] and dv
+// likewise from part[1], where part ([2][B][H][Sk][D] bf16, rows contiguous) holds what the backward
+// kernels stored per query head. The G rows are added in fp32 in ascending g and rounded once to
+// bf16; plain stores, no atomics, so the bits repeat from run to run, and G zero rows (keys past a
+// length, padding positions) give an exact zero row. One thread per 16-B chunk of a destination row,
+// blockIdx.y = 0 for dk, 1 for dv; VEC: 16-B stores (destination base and strides allow them), else
+// eight 2-byte stores.
+template <bool VEC>
+__global__ void __launch_bounds__(256) attn_kv_group_sum_kernel(AttnArgs a, const bf16_t* __restrict__ part, bf16_t* dk,
+                                                                bf16_t* dv, int64_t sb, int64_t sh, int64_t ss,
+                                                                int64_t vsb, int64_t vsh, int64_t vss) {
+  const int cpr = a.D / 8;  // 16-B chunks per row
+  const int64_t head = (int64_t)a.Sk * a.D;  // elements of one (batch, query head) of part
+  const int64_t n = (int64_t)a.B * a.Hkv * a.Sk * cpr;
+  const bool is_v = blockIdx.y != 0;
+  const bf16_t* src = part + (is_v ? (int64_t)a.B * a.H * head : 0);
+  bf16_t* dst = is_v ? dv : dk;
+  if (is_v) { sb = vsb; sh = vsh; ss = vss; }
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int c = (int)(i % cpr);
+    const int64_t r = i / cpr;
+    const int row = (int)(r % a.Sk);
+    const int64_t bk = r / a.Sk;
+    const int b = (int)(bk / a.Hkv), hk = (int)(bk % a.Hkv);
+    const bf16_t* p = src + ((int64_t)b * a.H + (int64_t)hk * a.G) * head + (int64_t)row * a.D + 8 * c;
+    float s[8];
+    {
+      const uint4 w = *reinterpret_cast<const uint4*>(p);
+      const unsigned u[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        s[2 * e] = __uint_as_float(u[e] << 16);
+        s[2 * e + 1] = __uint_as_float(u[e] & 0xffff0000u);
+      }
+    }
+    for (int g = 1; g < a.G; ++g) {
+      const uint4 w = *reinterpret_cast<const uint4*>(p + g * head);
+      const unsigned u[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        s[2 * e] += __uint_as_float(u[e] << 16);
+        s[2 * e + 1] += __uint_as_float(u[e] & 0xffff0000u);
+      }
+    }
+    bf16_t* d = dst + (int64_t)b * sb + (int64_t)hk * sh + (int64_t)row * ss + 8 * c;
+    if constexpr (VEC) {
+      *reinterpret_cast<uint4*>(d) = make_uint4(pack_bf2(s[0], s[1]), pack_bf2(s[2], s[3]), pack_bf2(s[4], s[5]),
+                                                pack_bf2(s[6], s[7]));
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) d[e] = f2bf(s[e]);
+    }
+  }
+}
+
 // Backward variant: 10 (default) = attn_bwd1b_kernel (one barrier per query tile, fenced dQ
 // chunks, LDS-DMA tiles) chained per key block when B*H workgroups fill the chip (>= 256), else
 // attn_bwd_kernel with LDS-DMA Q / dO tiles (one launch with per-key-block dQ slabs + finishing
@@ -1763,10 +1822,20 @@ int64_t attn_bwd_slab_floats(int B, int H, int Sq, int Sk, int D) {
   return (int64_t)nkb * B * H * Sq * D;
 }
 
-int64_t attn_bwd_workspace_floats(int B, int H, int Sq, int Sk, int D) {
+static int64_t bwd_base_floats(int B, int H, int Sq, int Sk, int D) {
   const int nkb = (Sk + bwd_keys(D) - 1) / bwd_keys(D);
   // slabs, delta, lse2, bias-gradient partials (attn_bwd1b_kernel)
   return (int64_t)nkb * B * H * Sq * D + 2 * (int64_t)B * H * Sq + (int64_t)B * H * D * (2 + 2 * nkb);
+}
+
+int64_t attn_bwd_kv_part_floats(int B, int H, int Sq, int Sk, int D) {
+  return (bwd_base_floats(B, H, Sq, Sk, D) + 3) / 4 * 4;
+}
+
+int64_t attn_bwd_workspace_floats(int B, int H, int Sq, int Sk, int D, int Hkv) {
+  if (Hkv <= 0 || Hkv >= H) return bwd_base_floats(B, H, Sq, Sk, D);
+  // grouped-query attention: the expanded dK and dV, bf16 [B][H][Sk][D] each (two per float)
+  return attn_bwd_kv_part_floats(B, H, Sq, Sk, D) + (int64_t)B * H * Sk * D;
 }
 
 // Forward structure: 3 (default) = 64 rows per wave (attn_fwd2_kernel; D = 64, Sq >= 512 and no
@@ -1935,6 +2004,12 @@ static bool dma_rows_ok(const void* p, int64_t ss, int rows) {
   return ((uintptr_t)p & 15) == 0 && ss % 8 == 0 && (int64_t)(rows + 64) * ss * 2 < 0x7fffffffLL;
 }
 
+// AttnArgs.Hkv -> the group size G the kernels divide the query head by (1: every head its own K / V)
+static void kv_groups(AttnArgs& a) {
+  if (a.Hkv <= 0 || a.Hkv >= a.H) a.Hkv = a.H;
+  a.G = a.H / a.Hkv;
+}
+
 // one workgroup per 128 QB query rows of a (batch, head), QB 32-row blocks per wave: QB = 2 is
 // attn_fwd2_kernel (D = 64, LDS-DMA, no dropout and no score bias form), QB = 1 attn_fwd_kernel,
 // whose DROP, BIAS and SEG (packed sequences, never with BIAS) instantiations are always MASK = true
@@ -1965,6 +2040,7 @@ static void launch_fwd(const AttnArgs& a, bool mask, hipStream_t st) {
 
 void attn_fwd(AttnArgs a, hipStream_t st) {
   const bool mask = a.causal || a.Sk % 64 != 0 || a.key_lens != nullptr;
+  kv_groups(a);
   a.rescale_thr = attn_rescale_thr();
   const bool drop = a.drop_thr > 0;
   if (drop && a.H_total <= 0) a.H_total = a.H;
@@ -2014,6 +2090,20 @@ bool attn_bwd(AttnArgs a, hipStream_t st) {
   bool bias_done = false;
   const bool drop = a.drop_thr > 0;
   if (drop && a.H_total <= 0) a.H_total = a.H;
+  kv_groups(a);
+  // grouped-query attention: the kernels store each query head's dK / dV into the expanded buffers
+  // (contiguous rows: the 16-B row stores as they are) and attn_kv_group_sum_kernel folds the groups
+  // into the caller's dk / dv behind them; no fused bias gradient (dbp is laid out for [3][H][D])
+  AttnArgs out = a;
+  if (a.G > 1) {
+    const int64_t head = (int64_t)a.Sk * a.D;
+    a.dk = a.kv_part;
+    a.dv = a.kv_part + (int64_t)a.B * a.H * head;
+    a.dk_sb = a.dv_sb = a.H * head;
+    a.dk_sh = a.dv_sh = head;
+    a.dk_ss = a.dv_ss = a.D;
+    a.dbp = nullptr;
+  }
   a.stagger = attn_stagger();
   const int v = attn_bwd_variant();
   const int nkb = (a.Sk + bwd_keys(a.D) - 1) / bwd_keys(a.D);
@@ -2053,6 +2143,19 @@ bool attn_bwd(AttnArgs a, hipStream_t st) {
     hipLaunchKernelGGL(attn_bwd_pre_kernel<128>, gpre, dim3(256), 0, st, a);
     launch_bwd<128, 4>(a, nkb, chain, st);
     if (finish) hipLaunchKernelGGL(attn_dq_finish_kernel<128>, gfin, dim3(256), 0, st, a, nkb);
+  }
+  if (a.G > 1 && (a.D == 64 || a.D == 128)) {
+    const int64_t n = (int64_t)a.B * a.Hkv * a.Sk * (a.D / 8);
+    const dim3 grid(ew_grid(n, 256), 2);
+    auto vec = [](const void* p, int64_t sb, int64_t sh, int64_t ss) {
+      return ((uintptr_t)p & 15) == 0 && sb % 8 == 0 && sh % 8 == 0 && ss % 8 == 0;
+    };
+    if (vec(out.dk, out.dk_sb, out.dk_sh, out.dk_ss) && vec(out.dv, out.dv_sb, out.dv_sh, out.dv_ss))
+      hipLaunchKernelGGL(attn_kv_group_sum_kernel<true>, grid, dim3(256), 0, st, a, a.kv_part, out.dk, out.dv, out.dk_sb,
+                         out.dk_sh, out.dk_ss, out.dv_sb, out.dv_sh, out.dv_ss);
+    else
+      hipLaunchKernelGGL(attn_kv_group_sum_kernel<false>, grid, dim3(256), 0, st, a, a.kv_part, out.dk, out.dv, out.dk_sb,
+                         out.dk_sh, out.dk_ss, out.dv_sb, out.dv_sh, out.dv_ss);
   }
   if (bias_done)
     hipLaunchKernelGGL(attn_bias_fold_kernel, dim3((unsigned)(3 * a.H)), dim3(1024), 0, st, a.dbp, a.dbias, a.B, a.H,

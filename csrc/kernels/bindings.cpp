@@ -844,13 +844,32 @@ void segment_mask_f32(Tensor s, Tensor lo, Tensor hi, int64_t b, int64_t H, int6
                         hi.data_ptr<int>() + b * Sq, cur_stream());
 }
 
+// grouped-query attention: Hkv (0: H) KV heads under H query heads. Returns the KV head count; with
+// Hkv < H the listed tensors (k, v, and dk, dv in the backward) are addressed through strides over
+// Hkv heads and must hold the last row of the last KV head.
+struct AttnKvView { const Tensor* t; const std::vector<int64_t>* st; const char* name; };
+int attn_kv_heads(int64_t Hkv, int64_t H, int64_t B, int64_t Sk, int64_t D, std::initializer_list<AttnKvView> views) {
+  if (Hkv <= 0) Hkv = H;
+  TORCH_CHECK(Hkv <= H && H % Hkv == 0, "attn: Hkv (", Hkv, ") must divide H (", H, ")");
+  if (Hkv < H && B > 0 && Sk > 0) {
+    for (const AttnKvView& x : views) {
+      const auto& s = *x.st;
+      TORCH_CHECK(s.size() == 3 && s[0] >= 0 && s[1] >= 0 && s[2] >= 0, "attn: ", x.name, " strides");
+      TORCH_CHECK(x.t->scalar_type() == at::kBFloat16, "attn: ", x.name, " must be bf16");
+      TORCH_CHECK((B - 1) * s[0] + (Hkv - 1) * s[1] + (Sk - 1) * s[2] + D <= x.t->numel(), "attn: ", x.name,
+                  " is too short for ", Hkv, " KV heads under its strides");
+    }
+  }
+  return (int)Hkv;
+}
+
 // q/k/v/o given with explicit [b,h,s] element strides (d contiguous)
 void attn_fwd(Tensor q, std::vector<int64_t> qs, Tensor k, std::vector<int64_t> ks, Tensor v,
               std::vector<int64_t> vs, Tensor o, std::vector<int64_t> os, Tensor lse, int64_t B, int64_t H,
               int64_t Sq, int64_t Sk, int64_t D, double scale, bool causal, optional<Tensor> key_lens,
               int64_t drop_thr, optional<Tensor> rng_step, int64_t rng_seed, int64_t b0, int64_t h0, int64_t H_total,
               optional<Tensor> sbias, int64_t sbias_sb, int64_t sbias_sh, optional<Tensor> seg_lo,
-              optional<Tensor> seg_hi) {
+              optional<Tensor> seg_hi, int64_t Hkv) {
   TORCH_CHECK(D == 64 || D == 128, "flash attention supports head_dim 64/128");
   TORCH_CHECK(q.scalar_type() == at::kBFloat16 && o.scalar_type() == at::kBFloat16);
   TORCH_CHECK(lse.numel() >= B * H * Sq && lse.scalar_type() == at::kFloat);
@@ -862,14 +881,15 @@ void attn_fwd(Tensor q, std::vector<int64_t> qs, Tensor k, std::vector<int64_t> 
   a.o = (uint16_t*)o.data_ptr(); a.o_sb = os[0]; a.o_sh = os[1]; a.o_ss = os[2];
   a.lse = lse.data_ptr<float>();
   a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.D = D; a.scale = scale; a.causal = causal;
+  a.Hkv = attn_kv_heads(Hkv, H, B, Sk, D, {{&k, &ks, "k"}, {&v, &vs, "v"}});
   a.key_lens = attn_key_lens(key_lens, q, B);
   attn_drop_args(a, q, drop_thr, rng_step, rng_seed, b0, h0, H_total, H);
   attn_sbias_args(a, q, sbias, sbias_sb, sbias_sh, B, H, Sq, Sk);
   attn_seg_args(a, q, seg_lo, seg_hi, B, Sq, Sk);
   ffk::attn_fwd(a, cur_stream());
 }
-int64_t attn_bwd_ws(int64_t B, int64_t H, int64_t Sq, int64_t Sk, int64_t D) {
-  return ffk::attn_bwd_workspace_floats(B, H, Sq, Sk, D);
+int64_t attn_bwd_ws(int64_t B, int64_t H, int64_t Sq, int64_t Sk, int64_t D, int64_t Hkv) {
+  return ffk::attn_bwd_workspace_floats(B, H, Sq, Sk, D, Hkv <= 0 ? H : Hkv);
 }
 bool attn_bwd(Tensor q, std::vector<int64_t> qs, Tensor k, std::vector<int64_t> ks, Tensor v,
               std::vector<int64_t> vs, Tensor o, std::vector<int64_t> os, Tensor dout, std::vector<int64_t> dos,
@@ -878,11 +898,17 @@ bool attn_bwd(Tensor q, std::vector<int64_t> qs, Tensor k, std::vector<int64_t> 
               double scale, bool causal, optional<Tensor> dbias, optional<Tensor> key_lens, int64_t drop_thr,
               optional<Tensor> rng_step, int64_t rng_seed, int64_t b0, int64_t h0, int64_t H_total,
               optional<Tensor> sbias, int64_t sbias_sb, int64_t sbias_sh, optional<Tensor> seg_lo,
-              optional<Tensor> seg_hi) {
+              optional<Tensor> seg_hi, int64_t Hkv) {
   TORCH_CHECK(D == 64 || D == 128, "flash attention supports head_dim 64/128");
-  TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.numel() >= ffk::attn_bwd_workspace_floats(B, H, Sq, Sk, D),
+  TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.numel() >= ffk::attn_bwd_workspace_floats(B, H, Sq, Sk, D, Hkv),
               "attn_bwd: workspace too small");
   ffk::AttnArgs a;
+  a.Hkv = attn_kv_heads(Hkv, H, B, Sk, D, {{&k, &ks, "k"}, {&v, &vs, "v"}, {&dk, &dks, "dk"}, {&dv, &dvs, "dv"}});
+  if (a.Hkv < H) {
+    TORCH_CHECK(!dbias, "attn_bwd: no fused bias gradient (dbias) with Hkv < H");
+    TORCH_CHECK(((uintptr_t)ws.data_ptr() & 15) == 0, "attn_bwd: the workspace must be 16-B aligned");
+    a.kv_part = (uint16_t*)(ws.data_ptr<float>() + ffk::attn_bwd_kv_part_floats(B, H, Sq, Sk, D));
+  }
   a.q = (const uint16_t*)q.data_ptr(); a.q_sb = qs[0]; a.q_sh = qs[1]; a.q_ss = qs[2];
   a.k = (const uint16_t*)k.data_ptr(); a.k_sb = ks[0]; a.k_sh = ks[1]; a.k_ss = ks[2];
   a.v = (const uint16_t*)v.data_ptr(); a.v_sb = vs[0]; a.v_sh = vs[1]; a.v_ss = vs[2];
@@ -1277,7 +1303,7 @@ PYBIND11_MODULE(_C, m) {
         py::arg("D"), py::arg("scale"), py::arg("causal"), py::arg("key_lens") = py::none(),
         py::arg("drop_thr") = 0, py::arg("rng_step") = py::none(), py::arg("rng_seed") = 0, py::arg("b0") = 0,
         py::arg("h0") = 0, py::arg("H_total") = 0, py::arg("sbias") = py::none(), py::arg("sbias_sb") = 0,
-        py::arg("sbias_sh") = 0, py::arg("seg_lo") = py::none(), py::arg("seg_hi") = py::none());
+        py::arg("sbias_sh") = 0, py::arg("seg_lo") = py::none(), py::arg("seg_hi") = py::none(), py::arg("Hkv") = 0);
   m.def("attn_bwd", &attn_bwd, py::arg("q"), py::arg("qs"), py::arg("k"), py::arg("ks"), py::arg("v"), py::arg("vs"),
         py::arg("o"), py::arg("os"), py::arg("dout"), py::arg("dos"), py::arg("lse"), py::arg("dq"), py::arg("dqs"),
         py::arg("dk"), py::arg("dks"), py::arg("dv"), py::arg("dvs"), py::arg("ws"), py::arg("B"), py::arg("H"),
@@ -1285,12 +1311,13 @@ PYBIND11_MODULE(_C, m) {
         py::arg("dbias") = py::none(), py::arg("key_lens") = py::none(), py::arg("drop_thr") = 0,
         py::arg("rng_step") = py::none(), py::arg("rng_seed") = 0, py::arg("b0") = 0, py::arg("h0") = 0,
         py::arg("H_total") = 0, py::arg("sbias") = py::none(), py::arg("sbias_sb") = 0, py::arg("sbias_sh") = 0,
-        py::arg("seg_lo") = py::none(), py::arg("seg_hi") = py::none());
+        py::arg("seg_lo") = py::none(), py::arg("seg_hi") = py::none(), py::arg("Hkv") = 0);
   m.def("attn_seg_bounds", &attn_seg_bounds);
   m.def("segment_mask_f32", &segment_mask_f32);
   m.def("attn_dropout_f32", &attn_dropout_f32);
   m.def("attn_dropout_mask", &attn_dropout_mask);
-  m.def("attn_bwd_ws", &attn_bwd_ws);
+  m.def("attn_bwd_ws", &attn_bwd_ws, py::arg("B"), py::arg("H"), py::arg("Sq"), py::arg("Sk"), py::arg("D"),
+        py::arg("Hkv") = 0);
   m.def("attn_set_bwd_variant", [](int v) { ffk::attn_set_bwd_variant(v); });
   m.def("attn_fwd_variant", []() { return ffk::attn_fwd_variant(); });
   m.def("attn_set_fwd_variant", [](int v) { ffk::attn_set_fwd_variant(v); });

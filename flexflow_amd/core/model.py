@@ -295,8 +295,11 @@ class FFModel:
 
     def multihead_attention(self, query, key, value, embed_dim, num_heads, kdim=0, vdim=0, dropout=0.0, bias=True,
                             add_bias_kv=False, add_zero_attn=False, kernel_initializer=None, causal=False, name=None,
-                            key_lengths=None, attn_bias=None, segment_ids=None):
-        """segment_ids: optional int32 tensor [batch, seq] of packed rows (several sequences back to back):
+                            key_lengths=None, attn_bias=None, segment_ids=None, num_kv_heads=None):
+        """num_kv_heads: grouped-query (multi-query for 1) attention: that many key / value heads under
+        num_heads query heads, query head h reading KV head h // (num_heads // num_kv_heads); it must
+        divide num_heads. None or num_heads is plain multi-head attention (ops/attention.py).
+        segment_ids: optional int32 tensor [batch, seq] of packed rows (several sequences back to back):
         attention stays inside a run of equal ids >= 0, a negative id marks padding; needs Sq == Sk and
         goes with neither key_lengths nor attn_bias (ops/attention.py).
         key_lengths: optional int32 tensor [batch] (or [batch, 1]) of a right-padded batch: sample b
@@ -309,6 +312,10 @@ class FFModel:
             raise ValueError(f"multihead_attention: dropout must be in [0, 1), got {dropout}")
         ins = [query, key, value] + ([key_lengths] if key_lengths is not None else [])
         kw = {}
+        if num_kv_heads is not None and int(num_kv_heads) != int(num_heads):  # else: the graph built as ever
+            if int(num_kv_heads) <= 0 or int(num_heads) % int(num_kv_heads):
+                raise ValueError(f"multihead_attention: num_kv_heads ({num_kv_heads}) must divide num_heads ({num_heads})")
+            kw["num_kv_heads"] = int(num_kv_heads)
         if segment_ids is not None:  # where the key lengths would sit, marked by the attribute
             _check_segment_args("multihead_attention", key_lengths, attn_bias)
             ins.append(segment_ids)
@@ -322,10 +329,12 @@ class FFModel:
                          causal=causal, self_attn=(query is key and key is value), **kw).outputs[0]
 
     def scaled_dot_product_attention(self, q, k, v, attn_bias=None, key_lengths=None, scale=None, causal=False,
-                                     dropout=0.0, name=None, segment_ids=None):
+                                     dropout=0.0, name=None, segment_ids=None, enable_gqa=False):
         """softmax(scale * q.k^T + attn_bias) . v on projected heads: q [B, H, Sq, D], k [B, H, Sk, D],
         v [B, H, Sk, Dv] -> [B, H, Sq, Dv] (extension; ops/sdpa.py). attn_bias, key_lengths, causal and
-        dropout and segment_ids are those of multihead_attention; scale=None means 1 / sqrt(D)."""
+        dropout and segment_ids are those of multihead_attention; scale=None means 1 / sqrt(D).
+        enable_gqa (torch's): k and v may have Hkv heads, Hkv dividing H; query head h reads KV head
+        h // (H // Hkv)."""
         if not 0.0 <= float(dropout) < 1.0:
             raise ValueError(f"scaled_dot_product_attention: dropout must be in [0, 1), got {dropout}")
         ins, kw = [q, k, v], {}
@@ -339,6 +348,8 @@ class FFModel:
         if attn_bias is not None:
             ins.append(attn_bias)
             kw["attn_bias"] = True
+        if enable_gqa:
+            kw["enable_gqa"] = True
         return self._add(OperatorType.OP_SDPA, ins, name, scale=None if scale is None else float(scale),
                          causal=bool(causal), dropout=float(dropout), **kw).outputs[0]
 

@@ -1142,9 +1142,21 @@ def _sbias_kw(bias, B, H, Sq, Sk, device):
     return dict(sbias=bias, sbias_sb=Hb * Sq * Sk if Bb > 1 else 0, sbias_sh=Sq * Sk if Hb > 1 else 0)
 
 
+def attn_kv_heads(H, Hkv):
+    """The KV head count of grouped-query attention: Hkv (None: H) must divide H; query head h reads KV
+    head h // (H // Hkv), torch's enable_gqa / repeat_interleave convention."""
+    if Hkv is None:
+        return int(H)
+    Hkv = int(Hkv)
+    if Hkv <= 0 or H % Hkv:
+        raise ValueError(f"attention: the KV head count ({Hkv}) must divide the head count ({H})")
+    return Hkv
+
+
 def flash_attn_fwd(q, qs, k, ks, v, vs, o, os_, B, H, Sq, Sk, D, scale, causal, key_lens=None, drop=None, bias=None,
-                   segments=None):
-    """segments: optional packed-sequence runs (attn_segments): attention stays inside a token's own
+                   segments=None, Hkv=None):
+    """Hkv: optional KV head count (attn_kv_heads): k / v and their strides ks / vs then hold Hkv heads.
+    segments: optional packed-sequence runs (attn_segments): attention stays inside a token's own
     run, a padding position gives o = 0, lse = +inf. key_lens: optional int32 [B] device tensor; key j of sample b is attended iff j < key_lens[b]
     (a length of 0: o = 0, lse = +inf). drop: optional attention dropout (thr, rng_step, rng_seed, b0,
     h0, H_total), see _drop_kw / attn_dropout_keep_ref; lse is that of the undropped softmax.
@@ -1152,13 +1164,16 @@ def flash_attn_fwd(q, qs, k, ks, v, vs, o, os_, B, H, Sq, Sk, D, scale, causal, 
     lse = torch.empty(B * H * Sq, device=q.device, dtype=torch.float32)
     ext().attn_fwd(q, qs, k, ks, v, vs, o, os_, lse, B, H, Sq, Sk, D, scale, causal,
                    attn_key_lens(key_lens, B, q.device), **_drop_kw(drop), **_sbias_kw(bias, B, H, Sq, Sk, q.device),
-                   **_seg_kw(segments, key_lens, bias, Sq, Sk))
+                   **_seg_kw(segments, key_lens, bias, Sq, Sk), Hkv=attn_kv_heads(H, Hkv))
     return lse
 
 
 def flash_attn_bwd(q, qs, k, ks, v, vs, o, os_, do, dos, lse, dq, dqs, dk, dks, dv, dvs, B, H, Sq, Sk, D, scale,
-                   causal, dbias=None, key_lens=None, drop=None, bias=None, segments=None):
-    """segments: as in flash_attn_fwd; the dq / dk / dv rows of padding positions are written as zeros,
+                   causal, dbias=None, key_lens=None, drop=None, bias=None, segments=None, Hkv=None):
+    """Hkv: as in flash_attn_fwd; dk / dv and dks / dvs hold Hkv heads, each the sum over its group of
+    query heads (fp32, one rounding, the same bits on every run), and the bias gradient is never fused
+    (a dbias given with Hkv < H is left untouched, returns False).
+    segments: as in flash_attn_fwd; the dq / dk / dv rows of padding positions are written as zeros,
     and the segment kernels never fuse the bias gradient (returns False).
     key_lens: as in flash_attn_fwd; dk / dv rows at or past a sample's length are written as zeros.
     drop: as in flash_attn_fwd, with the counter value the forward saw; the dropout kernels never fuse
@@ -1170,10 +1185,14 @@ def flash_attn_bwd(q, qs, k, ks, v, vs, o, os_, do, dos, lse, dq, dqs, dk, dks, 
     X = ext()
     from ..runtime.device import DeviceContext
     # dQ partial slabs + delta: one arena buffer shared (stream-ordered) by every attention layer
-    ws = DeviceContext.get(q.device).workspace("attn_bwd", X.attn_bwd_ws(B, H, Sq, Sk, D))
+    Hkv = attn_kv_heads(H, Hkv)
+    if Hkv < H:
+        dbias = None  # laid out for [3][H][D]: the caller sums the projection biases, as with dropout
+    ws = DeviceContext.get(q.device).workspace("attn_bwd", X.attn_bwd_ws(B, H, Sq, Sk, D, Hkv))
     return bool(X.attn_bwd(q, qs, k, ks, v, vs, o, os_, do, dos, lse, dq, dqs, dk, dks, dv, dvs, ws, B, H, Sq, Sk, D,
                            scale, causal, dbias, attn_key_lens(key_lens, B, q.device), **_drop_kw(drop),
-                           **_sbias_kw(bias, B, H, Sq, Sk, q.device), **_seg_kw(segments, key_lens, bias, Sq, Sk)))
+                           **_sbias_kw(bias, B, H, Sq, Sk, q.device), **_seg_kw(segments, key_lens, bias, Sq, Sk),
+                           Hkv=Hkv))
 
 
 # ---------------------------------------------------------------------------- layer norm
@@ -2407,8 +2426,15 @@ def attn_f32_supported(x) -> bool:
     return native(x) and x.dtype == torch.float32
 
 
+def _kv_expand(t, st, b, Hkv, G, S, d):
+    """Sample b of a flat K / V buffer of Hkv heads (strides st) with every head repeated G times:
+    flat [Hkv * G, S, d], and its (head, row) strides."""
+    view = t[b * st[0]:].as_strided((Hkv, S, d), (st[1], st[2], 1))
+    return view.repeat_interleave(G, 0).reshape(-1), S * d, d
+
+
 def attn_f32_fwd(q, qs, k, ks, v, vs, o, os_, B, H, Sq, Sk, kd, vd, scale, causal, key_lens=None, drop=None,
-                 bias=None, segments=None):
+                 bias=None, segments=None, Hkv=None):
     """fp32 attention on our kernels, per sample: S = Q.K^T (f32 MFMA GEMM, heads as the batch),
     causal mask, key-length mask (key_lens: int32 [B] on the device, columns >= key_lens[b] set to
     -inf there), row softmax(scale * S) (softmax.hip), the same columns of P set to 0 (a sample of
@@ -2419,8 +2445,11 @@ def attn_f32_fwd(q, qs, k, ks, v, vs, o, os_, B, H, Sq, Sk, kd, vd, scale, causa
     runs with scale 1; P is set to 0 where S is -inf, so a row with no key left has P = 0.
     segments (attn_segments): S is set to -inf outside the query's run (segment_mask_f32) and P to 0
     there, so a padding row has P = 0.
+    Hkv (attn_kv_heads): k / v hold Hkv heads; each sample's K / V are expanded to H heads for the GEMMs.
     Returns P [B, H, Sq, Sk]."""
     X = ext()
+    Hkv = attn_kv_heads(H, Hkv)
+    G = H // Hkv
     dkw = _drop_kw(drop)
     skw = _seg_kw(segments, key_lens, bias, Sq, Sk)
     bias = attn_score_bias(bias, B, H, Sq, Sk, q.device)
@@ -2433,7 +2462,9 @@ def attn_f32_fwd(q, qs, k, ks, v, vs, o, os_, B, H, Sq, Sk, kd, vd, scale, causa
     P = torch.empty(B, H, Sq, Sk, device=q.device, dtype=torch.float32)
     S = torch.empty(H, Sq, Sk, device=q.device, dtype=torch.float32)
     for b in range(B):
-        X.gemm_f32(q[b * qs[0]:], k[b * ks[0]:], S, None, None, Sq, Sk, kd, qs[2], ks[2], Sk, qs[1], ks[1], Sq * Sk,
+        kb, ksh, kss = (k[b * ks[0]:], ks[1], ks[2]) if G == 1 else _kv_expand(k, ks, b, Hkv, G, Sk, kd)
+        vb, vsh, vss = (v[b * vs[0]:], vs[1], vs[2]) if G == 1 else _kv_expand(v, vs, b, Hkv, G, Sk, vd)
+        X.gemm_f32(q[b * qs[0]:], kb, S, None, None, Sq, Sk, kd, qs[2], kss, Sk, qs[1], ksh, Sq * Sk,
                    H, True, True, 1.0, 0.0, ACT_NONE)
         if bias is not None:
             X.score_bias_f32(S, bflat[b * bsb:], H, Sq, Sk, bsh, scale)
@@ -2453,21 +2484,27 @@ def attn_f32_fwd(q, qs, k, ks, v, vs, o, os_, B, H, Sq, Sk, kd, vd, scale, causa
             X.attn_dropout_f32(P[b], Pd, H, Sq, Sk, dkw["b0"] + b, dkw["h0"], dkw["H_total"], dkw["drop_thr"],
                                dkw["rng_step"], dkw["rng_seed"])
             Pb = Pd
-        X.gemm_f32(Pb, v[b * vs[0]:], o[b * os_[0]:], None, None, Sq, vd, Sk, Sk, vs[2], os_[2], Sq * Sk, vs[1],
+        X.gemm_f32(Pb, vb, o[b * os_[0]:], None, None, Sq, vd, Sk, Sk, vss, os_[2], Sq * Sk, vsh,
                    os_[1], H, True, False, 1.0, 0.0, ACT_NONE)
     return P
 
 
 def attn_f32_bwd(q, qs, k, ks, v, vs, do, dos, P, dq, dk, dv, B, H, Sq, Sk, kd, vd, scale, key_lens=None, drop=None,
-                 bias=None, segments=None):
+                 bias=None, segments=None, Hkv=None):
     """Backward of attn_f32_fwd: dP = dO.V^T, dS = scale * P * (dP - rowsum(dP * P)), dQ = dS.K,
     dK = dS^T.Q, dV = P^T.dO (dq / dk / dv share q / k / v's strides). key_lens needs no work here:
     the forward left P = 0 in the masked columns, so dS is 0 there and the dK / dV rows at or past a
     sample's length come out as zeros (all of a length-0 sample's gradients do). drop (with the
     counter value of the forward): dP and the P of the dV GEMM go through attn_dropout_f32. bias needs
     no work either: it is inside P, dS = scale * P * (..) stays the gradient of the raw q.k, and the
-    bias itself takes no gradient. segments need none: P is 0 outside the runs."""
+    bias itself takes no gradient. segments need none: P is 0 outside the runs. Hkv (as in attn_f32_fwd):
+    dK / dV of the H query heads go to a per-sample buffer and each group's sum to dk / dv."""
     X = ext()
+    Hkv = attn_kv_heads(H, Hkv)
+    G = H // Hkv
+    if G > 1:
+        dkx = torch.empty(H, Sk, kd, device=q.device, dtype=torch.float32)
+        dvx = torch.empty(H, Sk, vd, device=q.device, dtype=torch.float32)
     dkw = _drop_kw(drop)
     Pd = torch.empty(H, Sq, Sk, device=q.device, dtype=torch.float32) if dkw else None
     q, k, v, do = q.reshape(-1), k.reshape(-1), v.reshape(-1), do.reshape(-1)
@@ -2475,7 +2512,10 @@ def attn_f32_bwd(q, qs, k, ks, v, vs, do, dos, P, dq, dk, dv, B, H, Sq, Sk, kd, 
     dP = torch.empty(H, Sq, Sk, device=q.device, dtype=torch.float32)
     dS = torch.empty_like(dP)
     for b in range(B):
-        X.gemm_f32(do[b * dos[0]:], v[b * vs[0]:], dP, None, None, Sq, Sk, vd, dos[2], vs[2], Sk, dos[1], vs[1],
+        kb, ksh, kss = (k[b * ks[0]:], ks[1], ks[2]) if G == 1 else _kv_expand(k, ks, b, Hkv, G, Sk, kd)
+        vb, vsh, vss = (v[b * vs[0]:], vs[1], vs[2]) if G == 1 else _kv_expand(v, vs, b, Hkv, G, Sk, vd)
+        dkb, dvb = (dk[b * ks[0]:], dv[b * vs[0]:]) if G == 1 else (dkx.view(-1), dvx.view(-1))
+        X.gemm_f32(do[b * dos[0]:], vb, dP, None, None, Sq, Sk, vd, dos[2], vss, Sk, dos[1], vsh,
                    Sq * Sk, H, True, True, 1.0, 0.0, ACT_NONE)
         Pb = P[b]
         if dkw:
@@ -2484,9 +2524,12 @@ def attn_f32_bwd(q, qs, k, ks, v, vs, do, dos, P, dq, dk, dv, B, H, Sq, Sk, kd, 
             X.attn_dropout_f32(P[b], Pd, *da)
             Pb = Pd
         X.softmax_bwd(P[b], dP, dS, H * Sq, Sk, scale, False)
-        X.gemm_f32(dS, k[b * ks[0]:], dq[b * qs[0]:], None, None, Sq, kd, Sk, Sk, ks[2], qs[2], Sq * Sk, ks[1],
+        X.gemm_f32(dS, kb, dq[b * qs[0]:], None, None, Sq, kd, Sk, Sk, kss, qs[2], Sq * Sk, ksh,
                    qs[1], H, True, False, 1.0, 0.0, ACT_NONE)
-        X.gemm_f32(dS, q[b * qs[0]:], dk[b * ks[0]:], None, None, Sk, kd, Sq, Sk, qs[2], ks[2], Sq * Sk, qs[1],
-                   ks[1], H, False, False, 1.0, 0.0, ACT_NONE)
-        X.gemm_f32(Pb, do[b * dos[0]:], dv[b * vs[0]:], None, None, Sk, vd, Sq, Sk, dos[2], vs[2], Sq * Sk,
-                   dos[1], vs[1], H, False, False, 1.0, 0.0, ACT_NONE)
+        X.gemm_f32(dS, q[b * qs[0]:], dkb, None, None, Sk, kd, Sq, Sk, qs[2], kss, Sq * Sk, qs[1],
+                   ksh, H, False, False, 1.0, 0.0, ACT_NONE)
+        X.gemm_f32(Pb, do[b * dos[0]:], dvb, None, None, Sk, vd, Sq, Sk, dos[2], vss, Sq * Sk,
+                   dos[1], vsh, H, False, False, 1.0, 0.0, ACT_NONE)
+        if G > 1:
+            for g, gx, st, d in ((dk, dkx, ks, kd), (dv, dvx, vs, vd)):
+                g[b * st[0]:].as_strided((Hkv, Sk, d), (st[1], st[2], 1)).copy_(gx.view(Hkv, G, Sk, d).sum(1))

@@ -54,6 +54,15 @@ CRC-32 of the layer name; the step is the executor's device-side counter (`ctx.r
 the kernels on the device, so a captured step draws a new mask at every replay; step 0 without an
 executor). The flash kernels generate the mask themselves, forward and backward, from the same
 counters: P is never materialised.
+
+Grouped-query / multi-query attention (attribute `num_kv_heads` = Hkv < H, dividing H; absent for plain
+multi-head attention, whose graph and launches are unchanged): the K / V projections produce Hkv heads
+(`k_weight` (Hkv, kd, Ek), `v_weight` (Hkv, vd, Ev), always the unfused form) and query head h reads KV
+head h // (H // Hkv), torch's `enable_gqa` / `repeat_interleave` convention. K and V are never
+repeated: the flash kernels index them by the KV head, and in the backward each query head's dK / dV
+contribution is summed per group in fp32 by one kernel (kernels.flash_attn_bwd). The heads axis splits
+dim 0 of every projection weight, so it takes the degrees that divide Hkv. The score bias's head extent
+stays 1 or H (query heads); the QKV bias gradient is summed by the projections' own backward.
 """
 from __future__ import annotations
 
@@ -126,44 +135,53 @@ def _view4(t, st, B, H, S, d):
     return t.as_strided((B, H, S, d), (st[0], st[1], st[2], 1))
 
 
+def _repeat_kv(t, G):
+    """[B, Hkv, S, d] -> [B, Hkv * G, S, d], head h a copy of KV head h // G (grouped-query attention);
+    autograd sums a group's gradients back into its KV head."""
+    return t if G == 1 else t.repeat_interleave(G, dim=1)
+
+
 def attn_core_fwd(s, name, qv, qs, kv, ks, vv, vs, o, os_, B, Hl, Sq, Sk, kd, vd, scale, causal, kl, drop, bias, keep_ref,
-                  seg=None):
+                  seg=None, Hkv=None):
     """softmax(scale q.k + bias, masks) v of MultiHeadAttention and ScaledDotProductAttention: q / k / v
     / o are buffers read and written through their (batch, head, row) element strides qs / ks / vs /
     os_ with contiguous head dims. Picks the path (flash kernels, head dims zero-padded to 64 / 128,
     fp32 device kernels, fp32 PyTorch reference / CPU) and leaves in `s` what attn_core_bwd needs of
     it. kl: key lengths (kernels.attn_key_lens) or None; drop: attention dropout as the kernels take it
     or None; bias: score bias (kernels.attn_score_bias) or None; keep_ref(): the dropout mask for the
-    reference path; seg: packed-sequence runs (kernels.attn_segments) or None."""
+    reference path; seg: packed-sequence runs (kernels.attn_segments) or None; Hkv: the KV head count
+    of grouped-query attention (k / v and ks / vs hold Hkv heads, query head h reads KV head
+    h // (Hl // Hkv)) or None for Hl."""
+    Hkv = K.attn_kv_heads(Hl, Hkv)
     if K.attn_supported(qv, kd) and kd == vd:
         s["lse"] = K.flash_attn_fwd(qv, qs, kv, ks, vv, vs, o, os_, B, Hl, Sq, Sk, kd, scale, causal, key_lens=kl,
-                                    drop=drop, bias=bias, segments=seg)
+                                    drop=drop, bias=bias, segments=seg, Hkv=Hkv)
     elif K.attn_padded_dim(qv, kd, vd):
         # head dims the MFMA kernels have no instance for (e.g. 16, 32, 80, 96): zero-pad Q, K,
         # V to the next instance (64 / 128). Zero columns add nothing to Q.K^T and give zero
         # output columns, so the softmax and the sliced output are exact; the scale is the caller's
         Dp = K.attn_padded_dim(qv, kd, vd)
-        pq, pk, pv = (_pad_heads(t, st, Bq, S_, Hl, kd, Dp) for t, st, Bq, S_ in
-                      ((qv, qs, B, Sq), (kv, ks, B, Sk), (vv, vs, B, Sk)))
+        pq, pk, pv = (_pad_heads(t, st, B, S_, H_, kd, Dp) for t, st, S_, H_ in
+                      ((qv, qs, Sq, Hl), (kv, ks, Sk, Hkv), (vv, vs, Sk, Hkv)))
         po = torch.empty(B, Sq, Hl, Dp, device=qv.device, dtype=qv.dtype)
         pst = [Sq * Hl * Dp, Dp, Hl * Dp]
-        kst = [Sk * Hl * Dp, Dp, Hl * Dp]
+        kst = [Sk * Hkv * Dp, Dp, Hkv * Dp]
         lse = K.flash_attn_fwd(pq, pst, pk, kst, pv, kst, po, pst, B, Hl, Sq, Sk, Dp, scale, causal, key_lens=kl,
-                               drop=drop, bias=bias, segments=seg)
+                               drop=drop, bias=bias, segments=seg, Hkv=Hkv)
         _view4(o, os_, B, Hl, Sq, vd).copy_(po[..., :vd].permute(0, 2, 1, 3))
         s.update(lse=lse, pad=(Dp, pq, pk, pv, po))
     elif K.attn_f32_supported(qv) and os.environ.get("FF_ATTN_REF_FALLBACK") != "1":
         # --dtype fp32 on the device: f32 MFMA GEMMs + causal mask + row softmax, our kernels
         s["P"] = K.attn_f32_fwd(qv, qs, kv, ks, vv, vs, o.view(-1), os_, B, Hl, Sq, Sk, kd, vd, scale, causal,
-                                key_lens=kl, drop=drop, bias=bias, segments=seg)
+                                key_lens=kl, drop=drop, bias=bias, segments=seg, Hkv=Hkv)
     else:
         if K.native(qv) and qv.dtype == torch.bfloat16 and os.environ.get("FF_ATTN_REF_FALLBACK") != "1":
             raise NotImplementedError(
                 f"{name}: no MFMA attention kernel for head dims q/k {kd}, v {vd} (supported: equal "
                 "q/k/v head dims up to 128; FF_ATTN_REF_FALLBACK=1 runs the fp32 PyTorch reference instead)")
         q4 = _view4(qv, qs, B, Hl, Sq, kd).float()
-        k4 = _view4(kv, ks, B, Hl, Sk, kd).float()
-        v4 = _view4(vv, vs, B, Hl, Sk, vd).float()
+        k4 = _repeat_kv(_view4(kv, ks, B, Hkv, Sk, kd).float(), Hl // Hkv)
+        v4 = _repeat_kv(_view4(vv, vs, B, Hkv, Sk, vd).float(), Hl // Hkv)
         keep = keep_ref() if drop else None
         if keep is not None:
             s["keep"] = keep
@@ -173,43 +191,46 @@ def attn_core_fwd(s, name, qv, qs, kv, ks, vv, vs, o, os_, B, Hl, Sq, Sk, kd, vd
 
 
 def attn_core_bwd(s, qv, qs, kv, ks, vv, vs, o, os_, do, dos, dq, dk, dv, B, Hl, Sq, Sk, kd, vd, scale, causal, kl, drop,
-                  bias, dbq=None, seg=None):
+                  bias, dbq=None, seg=None, Hkv=None):
     """Backward of attn_core_fwd on the path it took: dq / dk / dv (buffers with q / k / v's strides)
     from do (strides dos) and what the forward left in `s`. dbq: the fp32 [3*H*D] bias gradient of a fused
-    QKV projection the flash kernel may add into; returns whether it did."""
+    QKV projection the flash kernel may add into; returns whether it did. Hkv: as in attn_core_fwd; dk /
+    dv hold Hkv heads, each the sum over its group of query heads."""
+    Hkv = K.attn_kv_heads(Hl, Hkv)
     if "pad" in s:
         Dp, pq, pk, pv, po = s["pad"]
         pdo = torch.zeros_like(po)
         pdo[..., :vd] = _view4(do, dos, B, Hl, Sq, vd).permute(0, 2, 1, 3)
         pdq, pdk, pdv = torch.empty_like(pq), torch.empty_like(pk), torch.empty_like(pv)
         pst = [Sq * Hl * Dp, Dp, Hl * Dp]
-        kst = [Sk * Hl * Dp, Dp, Hl * Dp]
+        kst = [Sk * Hkv * Dp, Dp, Hkv * Dp]
         K.flash_attn_bwd(pq, pst, pk, kst, pv, kst, po, pst, pdo, pst, s["lse"], pdq, pst, pdk, kst, pdv, kst,
-                         B, Hl, Sq, Sk, Dp, scale, causal, key_lens=kl, drop=drop, bias=bias, segments=seg)
-        for g, st, pg, S_, d in ((dq, qs, pdq, Sq, kd), (dk, ks, pdk, Sk, kd), (dv, vs, pdv, Sk, vd)):
-            _view4(g, st, B, Hl, S_, d).copy_(pg[..., :d].permute(0, 2, 1, 3))
+                         B, Hl, Sq, Sk, Dp, scale, causal, key_lens=kl, drop=drop, bias=bias, segments=seg, Hkv=Hkv)
+        for g, st, pg, S_, d, H_ in ((dq, qs, pdq, Sq, kd, Hl), (dk, ks, pdk, Sk, kd, Hkv), (dv, vs, pdv, Sk, vd, Hkv)):
+            _view4(g, st, B, H_, S_, d).copy_(pg[..., :d].permute(0, 2, 1, 3))
     elif "lse" in s:
-        if dbq is not None:
+        if dbq is not None and Hkv == Hl:
             return K.flash_attn_bwd(qv, qs, kv, ks, vv, vs, o, os_, do, dos, s["lse"], dq, qs, dk, ks, dv, vs,
                                     B, Hl, Sq, Sk, kd, scale, causal, dbias=dbq, key_lens=kl, drop=drop, bias=bias,
                                     segments=seg)
         K.flash_attn_bwd(qv, qs, kv, ks, vv, vs, o, os_, do, dos, s["lse"], dq, qs, dk, ks, dv, vs,
-                         B, Hl, Sq, Sk, kd, scale, causal, key_lens=kl, drop=drop, bias=bias, segments=seg)
+                         B, Hl, Sq, Sk, kd, scale, causal, key_lens=kl, drop=drop, bias=bias, segments=seg, Hkv=Hkv)
     elif "P" in s:
         K.attn_f32_bwd(qv, qs, kv, ks, vv, vs, do.contiguous().view(-1), dos, s["P"], dq.view(-1), dk.view(-1),
-                       dv.view(-1), B, Hl, Sq, Sk, kd, vd, scale, key_lens=kl, drop=drop, bias=bias, segments=seg)
+                       dv.view(-1), B, Hl, Sq, Sk, kd, vd, scale, key_lens=kl, drop=drop, bias=bias, segments=seg,
+                       Hkv=Hkv)
     else:
         q4 = _view4(qv, qs, B, Hl, Sq, kd).detach().float().requires_grad_()
-        k4 = _view4(kv, ks, B, Hl, Sk, kd).detach().float().requires_grad_()
-        v4 = _view4(vv, vs, B, Hl, Sk, vd).detach().float().requires_grad_()
+        k4 = _view4(kv, ks, B, Hkv, Sk, kd).detach().float().requires_grad_()
+        v4 = _view4(vv, vs, B, Hkv, Sk, vd).detach().float().requires_grad_()
         with torch.enable_grad():
-            out = _attn_ref(q4, k4, v4, scale, causal, kl, s.get("keep"), 256.0 / (256 - drop[0]) if drop else 1.0, bias,
-                            seg[0] if seg is not None else None)
+            out = _attn_ref(q4, _repeat_kv(k4, Hl // Hkv), _repeat_kv(v4, Hl // Hkv), scale, causal, kl, s.get("keep"),
+                            256.0 / (256 - drop[0]) if drop else 1.0, bias, seg[0] if seg is not None else None)
         g4 = _view4(do, dos, B, Hl, Sq, vd).float()
         gq, gk, gv = torch.autograd.grad(out, (q4, k4, v4), g4)
         _view4(dq, qs, B, Hl, Sq, kd).copy_(gq)
-        _view4(dk, ks, B, Hl, Sk, kd).copy_(gk)
-        _view4(dv, vs, B, Hl, Sk, vd).copy_(gv)
+        _view4(dk, ks, B, Hkv, Sk, kd).copy_(gk)
+        _view4(dv, vs, B, Hkv, Sk, vd).copy_(gv)
     return False
 
 
@@ -285,6 +306,9 @@ class MultiHeadAttention(OpImpl):
                 raise ValueError(f"multihead_attention: attn_bias must be a float tensor, got {in_dtypes[-1]}")
         K.attn_dropout_thr(attrs.get("dropout", 0.0))  # ValueError outside [0, 1)
         H = attrs["num_heads"]
+        Hkv = attrs.get("num_kv_heads") or H
+        if Hkv <= 0 or H % Hkv:
+            raise ValueError(f"multihead_attention: num_kv_heads ({Hkv}) must divide num_heads ({H})")
         E = attrs["embed_dim"]
         kd = attrs.get("kdim") or E // H
         vd = attrs.get("vdim") or E // H
@@ -293,19 +317,21 @@ class MultiHeadAttention(OpImpl):
         kinit = attrs.get("kernel_init")
         from ..core.initializers import ZeroInitializer
         ws = []
-        if attrs.get("self_attn") and kd == vd and q[-1] == k[-1] == v[-1]:
+        if Hkv == H and attrs.get("self_attn") and kd == vd and q[-1] == k[-1] == v[-1]:
             attrs["fused_qkv"] = True
             ws.append(WeightSpec("qkv_weight", (3, H, kd, q[-1]), dt, kinit))
             if attrs.get("bias", True):
                 ws.append(WeightSpec("qkv_bias", (3, H, kd), dt, ZeroInitializer()))
         else:
             attrs["fused_qkv"] = False
-            ws += [WeightSpec("q_weight", (H, kd, q[-1]), dt, kinit), WeightSpec("k_weight", (H, kd, k[-1]), dt, kinit),
-                   WeightSpec("v_weight", (H, vd, v[-1]), dt, kinit)]
+            # grouped-query attention (Hkv < H): the K / V projections produce Hkv heads; the heads axis
+            # splits dim 0 of every weight (weight_maps), so its degrees are those that divide Hkv
+            ws += [WeightSpec("q_weight", (H, kd, q[-1]), dt, kinit), WeightSpec("k_weight", (Hkv, kd, k[-1]), dt, kinit),
+                   WeightSpec("v_weight", (Hkv, vd, v[-1]), dt, kinit)]
             if attrs.get("bias", True):
                 ws += [WeightSpec("q_bias", (H, kd), dt, ZeroInitializer()),
-                       WeightSpec("k_bias", (H, kd), dt, ZeroInitializer()),
-                       WeightSpec("v_bias", (H, vd), dt, ZeroInitializer())]
+                       WeightSpec("k_bias", (Hkv, kd), dt, ZeroInitializer()),
+                       WeightSpec("v_bias", (Hkv, vd), dt, ZeroInitializer())]
         ws.append(WeightSpec("o_weight", (E, H, vd), dt, kinit))
         if attrs.get("bias", True):
             ws.append(WeightSpec("o_bias", (E,), dt, ZeroInitializer()))
@@ -398,28 +424,30 @@ class MultiHeadAttention(OpImpl):
             st = [Sq * 3 * Hl * kd, kd, 3 * Hl * kd]
             qv, kv, vv = qkv.view(-1), qkv.view(-1)[Hl * kd:], qkv.view(-1)[2 * Hl * kd:]
             qs = ks = vs = st
+            Hkv = Hl
             s.update(x2=x2, wqkv=wq, qkv=qkv)
             if ctx.training and ctx.extra.get("need_dx0", True):  # TN dgrad (kernels.weight_t)
                 s["wqkv_t"] = K.weight_t(ctx.extra.setdefault("wt_store_qkv", {}), wq)
         else:
             outs = []
-            for name, t, d in (("q", q_in, kd), ("k", k_in, kd), ("v", v_in, vd)):
+            Hkv = W["k_weight"].shape[0]  # this part's KV heads: Hl, or fewer with num_kv_heads
+            for name, t, d, H_ in (("q", q_in, kd, Hl), ("k", k_in, kd, Hkv), ("v", v_in, vd, Hkv)):
                 x2 = t.reshape(-1, t.shape[-1])
-                w2 = W[f"{name}_weight"].reshape(Hl * d, -1)
+                w2 = W[f"{name}_weight"].reshape(H_ * d, -1)
                 b2 = W[f"{name}_bias"].reshape(-1) if f"{name}_bias" in W else None
                 y, _ = K.linear_fwd(x2, w2, b2, K.ACT_NONE, False)
                 outs.append(y)
                 s[f"x_{name}"], s[f"w_{name}"] = x2, w2
             qv, kv, vv = outs
             qs = [Sq * Hl * kd, kd, Hl * kd]
-            ks = [Sk * Hl * kd, kd, Hl * kd]
-            vs = [Sk * Hl * vd, vd, Hl * vd]
+            ks = [Sk * Hkv * kd, kd, Hkv * kd]
+            vs = [Sk * Hkv * vd, vd, Hkv * vd]
             s.update(q=qv, k=kv, v=vv)
         o = torch.empty(B, Sq, Hl, vd, device=q_in.device, dtype=q_in.dtype)
         os_ = [Sq * Hl * vd, vd, Hl * vd]
         bias = K.attn_score_bias(xs[-1], B, Hl, Sq, Sk, q_in.device) if has_bias else None
         attn_core_fwd(s, self.layer.name, qv, qs, kv, ks, vv, vs, o, os_, B, Hl, Sq, Sk, kd, vd, scale, causal, kl, drop,
-                      bias, lambda: self._keep_ref(ctx, drop, B, Hl, Sq, Sk, q_in.device), seg=seg)
+                      bias, lambda: self._keep_ref(ctx, drop, B, Hl, Sq, Sk, q_in.device), seg=seg, Hkv=Hkv)
         o2 = o.view(B * Sq, Hl * vd)
         wo = W["o_weight"].reshape(E, Hl * vd)
         if ctx.training:
@@ -428,7 +456,7 @@ class MultiHeadAttention(OpImpl):
         if ctx.training:
             s.update(o=o, wo=wo, has_bo=bo is not None, shape=(B, Sq, Sk, Hl, kd, vd, E), fused=fused,
                      qs=qs, ks=ks, vs=vs, os=os_, scale=scale, causal=causal, key_lens=kl, drop=drop, sbias=bias,
-                     seg=seg)
+                     seg=seg, Hkv=Hkv)
         return [y.view(B, Sq, E)]
 
     def overwrites_wgrad(self, i):
@@ -472,7 +500,7 @@ class MultiHeadAttention(OpImpl):
             dbq = None
         bias_done = attn_core_bwd(s, qv, qs, kv, ks, vv, vs, o, os_, do, os_, dq, dk, dv, B, Hl, Sq, Sk, kd, vd, scale,
                                   causal, kl, drop, s.get("sbias"), dbq.view(-1) if dbq is not None else None,
-                                  seg=s.get("seg"))
+                                  seg=s.get("seg"), Hkv=s.get("Hkv"))
         if fused:
             dw = gw("qkv_weight")
             db = None if bias_done else gw("qkv_bias")
@@ -486,13 +514,14 @@ class MultiHeadAttention(OpImpl):
             return [dx, None, None] + no_kl_grad  # all three inputs are the same tensor: gradient once
         grads = []
         accs = ctx.extra.get("dx_accum") or {}
-        for slot, (name, g, d, S_) in enumerate((("q", dq, kd, Sq), ("k", dk, kd, Sk), ("v", dv, vd, Sk))):
+        Hkv = s.get("Hkv") or Hl
+        for slot, (name, g, d, S_, H_) in enumerate((("q", dq, kd, Sq, Hl), ("k", dk, kd, Sk, Hkv), ("v", dv, vd, Sk, Hkv))):
             acc = accs.get(slot)
             dw = gw(f"{name}_weight")
             db = gw(f"{name}_bias")
             x2 = s[f"x_{name}"]
-            dx2 = K.linear_bwd(g.view(B * S_, Hl * d), x2, s[f"w_{name}"], None, K.ACT_NONE,
-                               dw.view(Hl * d, -1) if dw is not None else None,
+            dx2 = K.linear_bwd(g.view(B * S_, H_ * d), x2, s[f"w_{name}"], None, K.ACT_NONE,
+                               dw.view(H_ * d, -1) if dw is not None else None,
                                db.view(-1) if db is not None else None, dw_beta=wb,
                                dx_out=acc.view(B * S_, -1) if acc is not None else None)
             grads.append(acc if acc is not None else dx2.view(B, S_, -1))
@@ -511,7 +540,9 @@ class MultiHeadAttention(OpImpl):
         kd, vd = self.attrs["kdim"], self.attrs["vdim"]
         Hl = w_shapes[-2][1] if len(w_shapes[-1]) == 1 else w_shapes[-1][1]
         E = self.attrs["embed_dim"]
-        proj = 2.0 * B * (Sq * Hl * kd * Eq + Sk * Hl * kd * Eq + Sk * Hl * vd * Eq + Sq * Hl * vd * E)
+        H = self.attrs["num_heads"]
+        Hkv = Hl * (self.attrs.get("num_kv_heads") or H) // H  # this part's KV heads: the smaller K / V projections
+        proj = 2.0 * B * (Sq * Hl * kd * Eq + Sk * Hkv * kd * Eq + Sk * Hkv * vd * Eq + Sq * Hl * vd * E)
         att = 2.0 * B * Hl * Sq * Sk * (kd + vd)
         return proj + att
 

@@ -10,6 +10,9 @@ removes a key, a query row with no key left gives zeros, the bias and the length
 sequences into a row as in ops/attention.py; not combined with `key_lengths` or `attn_bias`.
 `scale` defaults to 1 / sqrt(D); `causal` and `dropout` are those of multihead_attention (the same
 counter-based mask, drawn from global batch / head indices).
+`enable_gqa` (attribute; torch's): k [B, Hkv, Sk, D] and v [B, Hkv, Sk, Dv] with Hkv dividing H, query head
+h reading KV head h // (H // Hkv); dk / dv come back in those shapes. Without it mismatched head counts
+are a ValueError. The heads axis then takes the degrees that divide Hkv.
 
 Parallel axes: batch (sample) and heads (dim 1; a parameter-style split without a reduction: every
 part owns whole heads of q, k, v and of the output). The kernels read q / k / v and write the output
@@ -46,8 +49,13 @@ class ScaledDotProductAttention(OpImpl):
         q, k, v = (tuple(d) for d in in_dims[:3])
         if not (len(q) == len(k) == len(v) == 4):
             raise ValueError(f"scaled_dot_product_attention: q, k, v must be [B, H, S, D], got {q}, {k}, {v}")
-        if q[:2] != k[:2] or q[:2] != v[:2] or q[3] != k[3] or k[2] != v[2]:
-            raise ValueError(f"scaled_dot_product_attention: mismatched q {q}, k {k}, v {v} (no GQA / MQA broadcasting)")
+        if attrs.get("enable_gqa"):
+            if q[0] != k[0] or q[0] != v[0] or q[3] != k[3] or k[2] != v[2] or k[1] != v[1] or k[1] <= 0 or q[1] % k[1]:
+                raise ValueError(f"scaled_dot_product_attention: mismatched q {q}, k {k}, v {v} (enable_gqa: k and v "
+                                 "have equal head counts that divide q's)")
+        elif q[:2] != k[:2] or q[:2] != v[:2] or q[3] != k[3] or k[2] != v[2]:
+            raise ValueError(f"scaled_dot_product_attention: mismatched q {q}, k {k}, v {v} (GQA / MQA head "
+                             "broadcasting needs enable_gqa=True)")
         B, H, Sq, _ = q
         if ns:
             check_segment_ids_dims("scaled_dot_product_attention", in_dims, nb, B, Sq, k[2])
@@ -90,7 +98,7 @@ class ScaledDotProductAttention(OpImpl):
     def forward(self, ctx, xs, ws):
         q, k, v = (t.contiguous() for t in xs[:3])
         B, Hl, Sq, kd = q.shape
-        Sk, vd = k.shape[2], v.shape[3]
+        Hkv, Sk, vd = k.shape[1], k.shape[2], v.shape[3]  # Hkv < Hl: enable_gqa (this part's heads of both)
         has_kl, has_bias = bool(self.attrs.get("key_lengths")), bool(self.attrs.get("attn_bias"))
         kl = K.attn_key_lens(xs[3], B, q.device) if has_kl else None
         bias = K.attn_score_bias(xs[-1], B, Hl, Sq, Sk, q.device) if has_bias else None
@@ -101,14 +109,15 @@ class ScaledDotProductAttention(OpImpl):
         H_total = self.layer.inputs[0].dims[1]
         drop = attn_drop_args(self, ctx, B, Hl, self.H_AXIS, H_total, q.device)
         s = ctx.saved if ctx.training else {}
-        qs, ks, vs = [Hl * Sq * kd, Sq * kd, kd], [Hl * Sk * kd, Sk * kd, kd], [Hl * Sk * vd, Sk * vd, vd]
+        qs, ks, vs = [Hl * Sq * kd, Sq * kd, kd], [Hkv * Sk * kd, Sk * kd, kd], [Hkv * Sk * vd, Sk * vd, vd]
         os_ = [Hl * Sq * vd, Sq * vd, vd]
         o = torch.empty(B, Hl, Sq, vd, device=q.device, dtype=q.dtype)
         attn_core_fwd(s, self.layer.name, q.view(-1), qs, k.view(-1), ks, v.view(-1), vs, o, os_, B, Hl, Sq, Sk, kd, vd,
-                      scale, causal, kl, drop, bias, lambda: attn_keep_ref(self, ctx, drop, B, Hl, Sq, Sk, q.device), seg=seg)
+                      scale, causal, kl, drop, bias, lambda: attn_keep_ref(self, ctx, drop, B, Hl, Sq, Sk, q.device), seg=seg,
+                      Hkv=Hkv)
         if ctx.training:
             s.update(q=q, k=k, v=v, o=o, shape=(B, Hl, Sq, Sk, kd, vd), st=(qs, ks, vs, os_), scale=scale,
-                     causal=causal, key_lens=kl, drop=drop, sbias=bias, seg=seg)
+                     causal=causal, key_lens=kl, drop=drop, sbias=bias, seg=seg, Hkv=Hkv)
         return [o]
 
     def backward(self, ctx, douts):
@@ -119,7 +128,7 @@ class ScaledDotProductAttention(OpImpl):
         do = douts[0].contiguous()
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         attn_core_bwd(s, q.view(-1), qs, k.view(-1), ks, v.view(-1), vs, o, os_, do, os_, dq, dk, dv, B, Hl, Sq, Sk, kd,
-                      vd, s["scale"], s["causal"], s["key_lens"], s["drop"], s["sbias"], seg=s.get("seg"))
+                      vd, s["scale"], s["causal"], s["key_lens"], s["drop"], s["sbias"], seg=s.get("seg"), Hkv=s.get("Hkv"))
         ctx.saved.clear()
         return [dq, dk, dv] + [None] * (len(self.layer.inputs) - 3)
 

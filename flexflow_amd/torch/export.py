@@ -312,11 +312,14 @@ class ExportImporter:
     def _sdpa(self, n):
         ff = self._ff
         a, kw = list(n.args), dict(n.kwargs)
-        names = ["query", "key", "value", "attn_mask", "dropout_p", "is_causal", "scale"]
+        names = ["query", "key", "value", "attn_mask", "dropout_p", "is_causal", "scale", "enable_gqa"]
         args = dict(zip(names, a))
         args.update(kw)
         if self.fuse_sdpa:
             return self._sdpa_fused(n, args)
+        if args.get("enable_gqa"):
+            raise NotImplementedError("sdpa enable_gqa=True needs fuse_sdpa=True (the unfused batch_matmul form has "
+                                      "no KV head broadcasting)")
         if args.get("is_causal"):
             raise NotImplementedError("sdpa is_causal=True (causal masks arrive as attn_mask constants)")
         q, k, v = (self._val(args[x]) for x in ("query", "key", "value"))
@@ -371,4 +374,5 @@ class ExportImporter:
         scale = args.get("scale")
         return ff.scaled_dot_product_attention(q, k, v, attn_bias=bias, scale=None if scale is None else float(scale),
                                                causal=bool(args.get("is_causal")),
-                                               dropout=float(args.get("dropout_p") or 0.0), name=n.name)
+                                               dropout=float(args.get("dropout_p") or 0.0), name=n.name,
+                                               enable_gqa=bool(args.get("enable_gqa")))
