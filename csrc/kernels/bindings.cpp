@@ -832,6 +832,60 @@ void attn_seg_bounds(Tensor ids, Tensor lo, Tensor hi) {
                        cur_stream());
 }
 
+// Rotary position embedding of q (and k when given) in one launch (ops.h RopeArgs). Every tensor is a
+// flat buffer read as [B][H][S][D] through (batch, head, row) element strides; *_out may be the input
+// (in place) or a buffer of the same dtype addressed by the same strides. table: fp32 [max_pos, rd/2, 2]
+// (cos, sin); pos: int32 [B, S] or None (row s has position s).
+void rope(Tensor q, Tensor q_out, std::vector<int64_t> qs, int64_t Hq, int64_t Sq, optional<Tensor> k,
+          optional<Tensor> k_out, std::vector<int64_t> ks, int64_t Hk, int64_t Sk, int64_t B, int64_t D, int64_t rd,
+          Tensor table, optional<Tensor> pos, bool interleaved, bool inverse) {
+  check_dev(q, "q");
+  const bool has_k = k.has_value() && k->defined();
+  TORCH_CHECK(rd >= 2 && rd % 2 == 0 && rd <= D, "rope: the rotated width (", rd, ") must be even and in [2, ", D, "]");
+  TORCH_CHECK(B >= 0 && B < (1ll << 31) && D < (1ll << 31), "rope: extents out of range");
+  TORCH_CHECK(table.scalar_type() == at::kFloat && table.is_contiguous() && table.dim() == 3 && table.size(0) >= 1 &&
+                  table.size(0) < (1ll << 31) && table.size(1) == rd / 2 && table.size(2) == 2 &&
+                  table.device() == q.device(),
+              "rope: table must be a contiguous fp32 [max_positions, ", rd / 2, ", 2] tensor on q's device");
+  ffk::RopeArgs a;
+  a.dt = dtcode(q);
+  a.B = (int)B, a.D = (int)D, a.rd = (int)rd;
+  a.table = table.data_ptr<float>();
+  a.max_pos = (int)table.size(0);
+  a.interleaved = interleaved, a.inverse = inverse;
+  auto set = [&](ffk::RopeTensor& t, const Tensor& in, const Tensor& out, const std::vector<int64_t>& st, int64_t H,
+                 int64_t S, const char* what) {
+    TORCH_CHECK(st.size() == 3 && st[0] >= 0 && st[1] >= 0 && st[2] >= 0, "rope: ", what, " takes 3 strides >= 0");
+    TORCH_CHECK(H >= 0 && S >= 0 && H < (1ll << 31) && S < (1ll << 31), "rope: ", what, " extents out of range");
+    TORCH_CHECK(out.is_cuda() && out.device() == q.device() && in.device() == q.device() &&
+                    in.scalar_type() == q.scalar_type() && out.scalar_type() == q.scalar_type(),
+                "rope: ", what, " and its output must share q's device and dtype");
+    TORCH_CHECK(in.is_contiguous() && out.is_contiguous(), "rope: ", what, " buffers must be contiguous (flat)");
+    if (B > 0 && H > 0 && S > 0) {  // the last element any lane touches lies inside both buffers
+      const int64_t need = (B - 1) * st[0] + (H - 1) * st[1] + (S - 1) * st[2] + D;
+      TORCH_CHECK(in.numel() >= need && out.numel() >= need, "rope: ", what, " holds ", std::min(in.numel(), out.numel()),
+                  " elements, its strides reach ", need);
+    }
+    t.in = in.data_ptr(), t.out = out.data_ptr();
+    t.sb = st[0], t.sh = st[1], t.ss = st[2];
+    t.H = (int)H, t.S = (int)S;
+  };
+  set(a.t[0], q, q_out, qs, Hq, Sq, "q");
+  if (has_k) {
+    TORCH_CHECK(k_out.has_value() && k_out->defined(), "rope: k needs k_out");
+    set(a.t[1], *k, *k_out, ks, Hk, Sk, "k");
+    a.nt = 2;
+  }
+  if (pos.has_value() && pos->defined()) {
+    TORCH_CHECK(!has_k || Sq == Sk, "rope: position ids need equal query and key lengths, got ", Sq, " and ", Sk);
+    TORCH_CHECK(pos->scalar_type() == at::kInt && pos->is_contiguous() && pos->numel() == B * Sq &&
+                    pos->device() == q.device(),
+                "rope: position ids must be a contiguous int32 [B, S] tensor on q's device");
+    a.pos = pos->data_ptr<int>();
+  }
+  ffk::rope(a, cur_stream());
+}
+
 // s [H, Sq, Sk] (fp32 scores of sample b) = -inf outside the query's run; lo / hi int32 [B, Sq]
 void segment_mask_f32(Tensor s, Tensor lo, Tensor hi, int64_t b, int64_t H, int64_t Sq, int64_t Sk) {
   check_dev(s, "s");
@@ -1313,6 +1367,9 @@ PYBIND11_MODULE(_C, m) {
         py::arg("H_total") = 0, py::arg("sbias") = py::none(), py::arg("sbias_sb") = 0, py::arg("sbias_sh") = 0,
         py::arg("seg_lo") = py::none(), py::arg("seg_hi") = py::none(), py::arg("Hkv") = 0);
   m.def("attn_seg_bounds", &attn_seg_bounds);
+  m.def("rope", &rope, py::arg("q"), py::arg("q_out"), py::arg("qs"), py::arg("Hq"), py::arg("Sq"), py::arg("k"),
+        py::arg("k_out"), py::arg("ks"), py::arg("Hk"), py::arg("Sk"), py::arg("B"), py::arg("D"), py::arg("rd"),
+        py::arg("table"), py::arg("pos") = py::none(), py::arg("interleaved") = false, py::arg("inverse") = false);
   m.def("segment_mask_f32", &segment_mask_f32);
   m.def("attn_dropout_f32", &attn_dropout_f32);
   m.def("attn_dropout_mask", &attn_dropout_mask);

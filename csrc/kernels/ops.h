@@ -51,6 +51,35 @@ void fold_flush(hipStream_t st);
 // out[c] += sum_r part[r][c] queued when recording (true), else nothing done (false)
 bool fold_queue(const float* part, float* out, int R, int C, hipStream_t st);
 
+// rope.hip: rotary position embedding of up to two strided tensors (Q and K) in one launch. Each is a
+// [B][H][S][D] view through element strides (sb, sh, ss) with contiguous D, as in AttnArgs; the two
+// have their own head counts, sequence lengths and strides. Every head row rotates its first rd
+// elements (rd even, 2 <= rd <= D) by the angle of its position p: pairs (i, i + rd/2) (half-split,
+// HF / NeoX rotate_half) or (2i, 2i + 1) (interleaved, GPT-J), y1 = x1 c - x2 s, y2 = x2 c + x1 s
+// with (c, s) = table[p][i]; inverse uses -s (the backward: the Jacobian is orthogonal). fp32
+// arithmetic, one rounding to the storage type. out may be in (in place: elements [rd, D) are
+// neither read nor written) or another buffer with the same strides (they are copied bit for bit).
+struct RopeTensor {
+  const void* in = nullptr;
+  void* out = nullptr;
+  int64_t sb = 0, sh = 0, ss = 0;
+  int H = 0, S = 0;
+};
+struct RopeArgs {
+  RopeTensor t[2];
+  int nt = 1;  // tensors in t
+  int dt = DT_BF16;
+  int B = 0, D = 0, rd = 0;
+  // positions: device int32 [B][S] (then every tensor has that S), clamped to [0, max_pos - 1] where
+  // they are read; null: row s has position s
+  const int* pos = nullptr;
+  // host-built (cos, sin) pairs, fp32 [max_pos][rd / 2][2]; no trigonometry on the device
+  const float* table = nullptr;
+  int max_pos = 0;
+  int interleaved = 0, inverse = 0;
+};
+void rope(const RopeArgs& a, hipStream_t st);
+
 // transfer.hip: one launch over a list of boxes (pack / unpack / local re-layout of activation
 // shards); desc: device int64 [nbox][box_words()] (see transfer.hip), units of vec_bytes (copy)
 // or elements of dt (add: dst += src)

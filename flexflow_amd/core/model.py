@@ -295,8 +295,18 @@ class FFModel:
 
     def multihead_attention(self, query, key, value, embed_dim, num_heads, kdim=0, vdim=0, dropout=0.0, bias=True,
                             add_bias_kv=False, add_zero_attn=False, kernel_initializer=None, causal=False, name=None,
-                            key_lengths=None, attn_bias=None, segment_ids=None, num_kv_heads=None):
-        """num_kv_heads: grouped-query (multi-query for 1) attention: that many key / value heads under
+                            key_lengths=None, attn_bias=None, segment_ids=None, num_kv_heads=None, rotary=None,
+                            rope_position_ids=None):
+        """rotary: rotary position embeddings (RoPE) on the projected query and key heads: None / False
+        (default: the graph built as ever), True, or a dict with `dim` (rotated width, even, default the
+        per-head kdim), `base` (10000.0), `interleaved` (False: HF / NeoX rotate_half pairs (i, i + dim/2);
+        True: GPT-J pairs (2i, 2i + 1)), `scale` (1.0; positions are divided by it), `inv_freq` (None; a
+        list of dim / 2 frequencies that overrides `base`: NTK, llama-3, YaRN tables) and `max_positions`
+        (default max(Sq, Sk)). Query i and key j rotate by positions i and j (ops/attention.py).
+        rope_position_ids: optional int32 tensor [batch, seq] with the position of every token, e.g.
+        utils.packing.pack()'s position_ids of packed rows; needs rotary and Sq == Sk; ids are clamped
+        to [0, max_positions - 1]; it takes no gradient.
+        num_kv_heads: grouped-query (multi-query for 1) attention: that many key / value heads under
         num_heads query heads, query head h reading KV head h // (num_heads // num_kv_heads); it must
         divide num_heads. None or num_heads is plain multi-head attention (ops/attention.py).
         segment_ids: optional int32 tensor [batch, seq] of packed rows (several sequences back to back):
@@ -320,6 +330,17 @@ class FFModel:
             _check_segment_args("multihead_attention", key_lengths, attn_bias)
             ins.append(segment_ids)
             kw["segment_ids"] = True
+        if rotary:
+            kw.update(self._rope_attrs("multihead_attention", rotary, int(kdim) or int(embed_dim) // int(num_heads),
+                                       max(query.dims[1], key.dims[1])))
+        if rope_position_ids is not None:  # behind the lengths / segment ids, in front of the score bias
+            if not rotary:
+                raise ValueError("multihead_attention: rope_position_ids needs rotary")
+            from ..ops.attention import check_rope_ids_dims
+            check_rope_ids_dims("multihead_attention", rope_position_ids.dims, rope_position_ids.data_type,
+                                query.dims[0], query.dims[1], key.dims[1])
+            ins.append(rope_position_ids)
+            kw["rope_positions"] = True
         if attn_bias is not None:  # the last input, marked by the attribute; a graph without it is built as ever
             ins.append(attn_bias)
             kw["attn_bias"] = True
@@ -352,6 +373,30 @@ class FFModel:
             kw["enable_gqa"] = True
         return self._add(OperatorType.OP_SDPA, ins, name, scale=None if scale is None else float(scale),
                          causal=bool(causal), dropout=float(dropout), **kw).outputs[0]
+
+    @staticmethod
+    def _rope_attrs(what, rotary, D, S_max):
+        """The builder's `rotary` argument as plain, hashable layer attributes (the cost key sees them)."""
+        from .. import kernels as K
+        rd, base, inter, scale, inv, maxp = K.rope_config(what, rotary, D, S_max)
+        return dict(rope_dim=rd, rope_base=base, rope_interleaved=inter, rope_scale=scale, rope_inv_freq=inv,
+                    rope_max_positions=maxp)
+
+    def rotary_embedding(self, x, position_ids=None, seq_dim=2, name=None, **rotary_config):
+        """Rotary position embedding of projected heads (extension; ops/rope.py): x [B, H, S, D] (seq_dim=2,
+        in front of scaled_dot_product_attention) or [B, S, H, D] (seq_dim=1) -> the same shape and dtype,
+        every head row rotated by its position. position_ids: optional int32 [B, S] tensor (default: the
+        row index). rotary_config: dim, base, interleaved, scale, inv_freq, max_positions as in
+        multihead_attention's `rotary`."""
+        if seq_dim not in (1, 2) or len(x.dims) != 4:
+            raise ValueError(f"rotary_embedding: x must be [B, H, S, D] (seq_dim=2) or [B, S, H, D] (seq_dim=1), "
+                             f"got {list(x.dims)} with seq_dim={seq_dim}")
+        kw = self._rope_attrs("rotary_embedding", rotary_config or True, x.dims[3], x.dims[seq_dim])
+        ins = [x]
+        if position_ids is not None:
+            ins.append(position_ids)
+            kw["rope_positions"] = True
+        return self._add(OperatorType.OP_ROPE, ins, name, seq_dim=int(seq_dim), **kw).outputs[0]
 
     # ---- shape ops
     def concat(self, tensors, axis, name=None):

@@ -1195,6 +1195,119 @@ def flash_attn_bwd(q, qs, k, ks, v, vs, o, os_, do, dos, lse, dq, dqs, dk, dks, 
                            Hkv=Hkv))
 
 
+# ------------------------------------------------------------------ rotary position embedding (rope.hip)
+_ROPE_TABLES: dict = {}
+
+
+def rope_config(what, rotary, D, S_max):
+    """`rotary` (True or a dict with dim / base / interleaved / scale / inv_freq / max_positions) of head
+    rows of width D, checked and normalised into plain hashable values: (dim, base, interleaved, scale,
+    inv_freq tuple or None, max_positions). max_positions defaults to S_max (the longest sequence)."""
+    cfg = {} if rotary is True else dict(rotary)
+    unknown = set(cfg) - {"dim", "base", "interleaved", "scale", "inv_freq", "max_positions"}
+    if unknown:
+        raise ValueError(f"{what}: unknown rotary keys {sorted(unknown)}")
+    rd = int(cfg.get("dim") or D)
+    if rd < 2 or rd % 2 or rd > D:
+        raise ValueError(f"{what}: the rotary dim must be even and in [2, {D}] (the head dim), got {rd}")
+    base, scale = float(cfg.get("base", 10000.0)), float(cfg.get("scale", 1.0))
+    if not (base > 0 and math.isfinite(base) and scale > 0 and math.isfinite(scale)):
+        raise ValueError(f"{what}: rotary base and scale must be positive and finite, got {base}, {scale}")
+    inv = cfg.get("inv_freq")
+    if inv is not None:
+        inv = tuple(float(f) for f in (inv.tolist() if hasattr(inv, "tolist") else inv))
+        if len(inv) != rd // 2:
+            raise ValueError(f"{what}: rotary inv_freq must hold dim / 2 = {rd // 2} values, got {len(inv)}")
+    maxp = int(cfg.get("max_positions") or S_max)
+    if maxp < S_max:
+        raise ValueError(f"{what}: rotary max_positions ({maxp}) is below the sequence length ({S_max})")
+    return rd, base, bool(cfg.get("interleaved", False)), scale, inv, maxp
+
+
+def rope_table(rd, max_positions, base=10000.0, scale=1.0, inv_freq=None, device="cpu"):
+    """The (cos, sin) table the rotation reads: fp32 [max_positions, rd / 2, 2] on `device`, entry (p, i)
+    the cosine and sine of (p / scale) * inv_freq[i] with inv_freq[i] = base^(-2i / rd) (or the explicit
+    list), computed on the host in float64 and rounded once. Cached per (device, rd, base, scale,
+    inv_freq, max_positions); a cache miss uploads, so call it where an op is set up and not under
+    stream capture."""
+    device = torch.device(device)
+    inv = None if inv_freq is None else tuple(float(f) for f in inv_freq)
+    key = (str(device), int(rd), float(base), float(scale), inv, int(max_positions))
+    t = _ROPE_TABLES.get(key)
+    if t is None:
+        if rd < 2 or rd % 2:
+            raise ValueError(f"rope_table: rd must be even and >= 2, got {rd}")
+        if inv is not None and len(inv) != rd // 2:
+            raise ValueError(f"rope_table: inv_freq must hold rd / 2 = {rd // 2} values, got {len(inv)}")
+        f = (torch.tensor(inv, dtype=torch.float64) if inv is not None
+             else float(base) ** (-torch.arange(0, rd, 2, dtype=torch.float64) / rd))
+        ang = (torch.arange(int(max_positions), dtype=torch.float64) / float(scale))[:, None] * f[None, :]
+        t = torch.stack((torch.cos(ang), torch.sin(ang)), -1).to(torch.float32).contiguous().to(device)
+        _ROPE_TABLES[key] = t
+    return t
+
+
+def rope_ref(x, table, pos=None, rd=None, interleaved=False, inverse=False):
+    """Plain-torch rotation of x [B, H, S, D] (any strides) by the definition rope.hip implements: the
+    first rd columns of every head row rotate by table[p] with p = pos[b, s] clamped to the table (pos
+    None: p = s), pairs (i, i + rd/2) or, interleaved, (2i, 2i + 1); y1 = x1 c - x2 s, y2 = x2 c + x1 s
+    in fp32 with one rounding to x's dtype; inverse takes -s. Columns [rd, D) are returned unchanged."""
+    B, H, S, D = x.shape
+    rd = D if rd is None else int(rd)
+    half = rd // 2
+    maxp = table.shape[0]
+    if pos is None:
+        p = torch.arange(S, device=x.device).clamp(max=maxp - 1)[None, :].expand(B, S)
+    else:
+        p = pos.reshape(B, S).to(device=x.device, dtype=torch.int64).clamp(0, maxp - 1)
+    cs = table.to(x.device)[p]  # [B, S, half, 2]
+    c, s = cs[..., 0][:, None], cs[..., 1][:, None]
+    if inverse:
+        s = -s
+    xf = x[..., :rd].float()
+    x1, x2 = (xf[..., 0::2], xf[..., 1::2]) if interleaved else (xf[..., :half], xf[..., half:])
+    y1, y2 = x1 * c - x2 * s, x2 * c + x1 * s
+    out = x.clone()
+    if interleaved:
+        out[..., 0:rd:2], out[..., 1:rd:2] = y1.to(x.dtype), y2.to(x.dtype)
+    else:
+        out[..., :half], out[..., half:rd] = y1.to(x.dtype), y2.to(x.dtype)
+    return out
+
+
+@torch.no_grad()
+def rope(q, qs, k, ks, B, H, Hkv, Sq, Sk, D, rd, table, pos=None, interleaved=False, inverse=False, q_out=None,
+         k_out=None):
+    """Rotate the head rows of q (and of k unless it is None) by their positions in ONE launch (rope.hip).
+    q / k are flat buffers read as [B, H | Hkv, Sq | Sk, D] through (batch, head, row) element strides qs
+    / ks with contiguous D, e.g. the Q and K thirds of a fused [T, 3, H, D] buffer. In place unless q_out
+    / k_out (buffers addressed by the same strides) are given; out of place, columns [rd, D) are copied.
+    table: rope_table(...) on q's device; pos: int32 [B, S] position ids (then Sq == Sk), read and
+    clamped to the table on the device, or None for position = row index. inverse: the backward (the
+    rotation by the negated angle). Without a native device the same definition runs as rope_ref."""
+    q_out = q if q_out is None else q_out
+    k_out = k if k_out is None else k_out
+    if pos is not None:
+        if k is not None and Sq != Sk:
+            raise ValueError(f"rope: position ids need Sq == Sk, got {Sq} and {Sk}")
+        if tuple(pos.shape) != (B, Sq) or pos.dtype != torch.int32:
+            raise ValueError(f"rope: position ids must be int32 [{B}, {Sq}], got {pos.dtype} {list(pos.shape)}")
+        if pos.device != q.device or not pos.is_contiguous():
+            pos = pos.to(q.device).contiguous()
+    elif table.shape[0] < max(Sq, Sk if k is not None else 0):
+        raise ValueError(f"rope: the table holds {table.shape[0]} positions, the sequence has {max(Sq, Sk)}")
+    if native(q):
+        ext().rope(q, q_out, list(qs), H, Sq, k, k_out, list(ks) if k is not None else [0, 0, 0], Hkv, Sk, B, D, rd,
+                   table, pos, bool(interleaved), bool(inverse))
+        return
+    for t, o, st, H_, S_ in ((q, q_out, qs, H, Sq), (k, k_out, ks, Hkv, Sk)):
+        if t is None:
+            continue
+        view = t.as_strided((B, H_, S_, D), (st[0], st[1], st[2], 1))
+        y = rope_ref(view, table, pos, rd, interleaved, inverse)
+        o.as_strided((B, H_, S_, D), (st[0], st[1], st[2], 1)).copy_(y)
+
+
 # ---------------------------------------------------------------------------- layer norm
 def layernorm_fwd(x2d, res2d, gamma, beta, eps, save_sum):
     """y = LN(x + res). Returns (y, sum_or_x, mean, rstd)."""

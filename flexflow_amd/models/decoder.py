@@ -1,0 +1,51 @@
+"""A small pre-norm causal decoder in the shape of the current open models (LLaMA, Mistral, Qwen): token
+embedding only (no position table), and per block RMSNorm -> rotary grouped-query attention -> residual,
+RMSNorm -> GELU MLP -> residual; a final RMSNorm and a vocabulary projection with softmax. Positions enter
+through the rotation of the query and key heads alone (ops/attention.py, `rotary`).
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+from ..type import ActiMode, AggrMode, DataType
+
+
+@dataclass
+class DecoderConfig:
+    hidden: int = 1024
+    heads: int = 16
+    kv_heads: int = 4
+    layers: int = 8
+    ffn: int = 4096
+    vocab: int = 32000
+    seq: int = 512
+    rope_base: float = 10000.0
+    max_positions: int = 0  # 0: seq
+
+    @staticmethod
+    def tiny(seq=32):
+        return DecoderConfig(hidden=64, heads=4, kv_heads=2, layers=2, ffn=128, vocab=96, seq=seq)
+
+
+def build_rope_decoder(ff, batch: int, cfg: DecoderConfig, segment_ids=None, position_ids=None):
+    """Returns (ids_tensor, output). Output: [batch, seq, vocab] next-token probabilities.
+    segment_ids / position_ids: optional int32 [batch, seq] tensors of packed rows (utils/packing.py):
+    attention stays inside a token's own sequence and its position restarts there."""
+    S, H = cfg.seq, cfg.hidden
+    rotary = dict(base=cfg.rope_base, max_positions=cfg.max_positions or S)
+    ids = ff.create_tensor([batch, S], DataType.DT_INT32, name="input_ids")
+    x = ff.embedding(ids, cfg.vocab, H, AggrMode.AGGR_MODE_NONE, name="tok_emb")
+    for l in range(cfg.layers):
+        n = ff.rms_norm(x, name=f"l{l}_norm1")
+        a = ff.multihead_attention(n, n, n, H, cfg.heads, bias=False, causal=True, name=f"l{l}_attn",
+                                   num_kv_heads=cfg.kv_heads, segment_ids=segment_ids, rotary=rotary,
+                                   rope_position_ids=position_ids)
+        x = ff.add(a, x, name=f"l{l}_res1")
+        n = ff.rms_norm(x, name=f"l{l}_norm2")
+        h = ff.dense(n, cfg.ffn, ActiMode.AC_MODE_GELU, name=f"l{l}_ffn1")
+        h = ff.dense(h, H, name=f"l{l}_ffn2")
+        x = ff.add(h, x, name=f"l{l}_res2")
+    x = ff.rms_norm(x, name="final_norm")
+    t = ff.dense(x, cfg.vocab, use_bias=False, name="lm_head")
+    out = ff.softmax(t, name="lm_softmax")
+    return ids, out

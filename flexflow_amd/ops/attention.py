@@ -63,6 +63,22 @@ repeated: the flash kernels index them by the KV head, and in the backward each 
 contribution is summed per group in fp32 by one kernel (kernels.flash_attn_bwd). The heads axis splits
 dim 0 of every projection weight, so it takes the degrees that divide Hkv. The score bias's head extent
 stays 1 or H (query heads); the QKV bias gradient is summed by the projections' own backward.
+
+Rotary position embeddings (attributes `rope_dim`, `rope_base`, `rope_interleaved`, `rope_scale`,
+`rope_inv_freq`, `rope_max_positions`, set by the builder's `rotary=`; absent otherwise, and then the graph
+and every launch are what they were): after the projection GEMMs ONE launch (kernels.rope, rope.hip)
+rotates the Q and K head rows in place, inside the fused [T, 3, H, D] buffer or in the separate q / k
+buffers, so every path below (flash, zero-padded head dims, fp32 device, reference / CPU) sees rotated
+heads and the tensors saved for the backward are the rotated ones. Query i and key j take positions i
+and j (also for Sq != Sk), or, with the int32 [B, S] input `rope_position_ids` (attribute
+`rope_positions=True`; after key_lengths / segment_ids and before attn_bias; Sq == Sk), the ids of a
+packed row (utils/packing.py), read and clamped to [0, max_positions - 1] on the device. The backward
+rotates dq / dk back with one inverse launch (the Jacobian is orthogonal, nothing is saved for it) before
+the projections' backward; the flash kernel's fused QKV bias gradient is off with rotary, since it would
+sum dq / dk columns before they are rotated back, and linear_bwd sums it instead. The ids take no
+gradient, are sharded with the batch and replicated over the heads axis; the rotation is per head row,
+so a shard needs nothing but its rows. The (cos, sin) table is built on the host in float64
+(kernels.rope_table) when the executor sets the layer up, outside any captured region.
 """
 from __future__ import annotations
 
@@ -276,6 +292,29 @@ def check_segment_ids_dims(what, in_dims, nb, B, Sq, Sk):
         raise ValueError(f"{what}: segment_ids must have shape [{B}, {Sq}], got {list(in_dims[3])}")
 
 
+def rope_attrs(attrs):
+    """(dim, base, interleaved, scale, inv_freq, max_positions) of a layer built with rotary, or None."""
+    if not attrs.get("rope_dim"):
+        return None
+    return (attrs["rope_dim"], attrs.get("rope_base", 10000.0), bool(attrs.get("rope_interleaved", False)),
+            attrs.get("rope_scale", 1.0), attrs.get("rope_inv_freq"), attrs["rope_max_positions"])
+
+
+def rope_table_of(rope, device):
+    rd, base, _, scale, inv, maxp = rope
+    return K.rope_table(rd, maxp, base, scale, inv, device)
+
+
+def check_rope_ids_dims(what, dims, dtype, B, Sq, Sk):
+    from ..type import DataType
+    if Sq != Sk:
+        raise ValueError(f"{what}: rope_position_ids needs Sq == Sk (one id per token), got Sq {Sq}, Sk {Sk}")
+    if tuple(dims) != (B, Sq):
+        raise ValueError(f"{what}: rope_position_ids must have shape [{B}, {Sq}], got {list(dims)}")
+    if dtype != DataType.DT_INT32:
+        raise ValueError(f"{what}: rope_position_ids must be an int32 tensor, got {dtype}")
+
+
 def attn_bias_map(dims, B, H, batch_axis, heads_axis):
     """input_maps entry of a score bias: with the batch where its first extent is B, with the heads
     where its second is H, replicated elsewhere."""
@@ -289,10 +328,18 @@ class MultiHeadAttention(OpImpl):
     @classmethod
     def infer(cls, attrs, in_dims, in_dtypes):
         nb = 1 if attrs.get("attn_bias") else 0
-        if len(in_dims) - nb not in (3, 4):
-            raise ValueError("multihead_attention takes query, key, value[, key_lengths][, attn_bias]; got "
-                             f"{len(in_dims)} inputs" + (" with attn_bias=True" if nb else ""))
+        nr = 1 if attrs.get("rope_positions") else 0
+        if len(in_dims) - nb - nr not in (3, 4):
+            raise ValueError("multihead_attention takes query, key, value[, key_lengths][, rope_position_ids]"
+                             f"[, attn_bias]; got {len(in_dims)} inputs" + (" with attn_bias=True" if nb else "")
+                             + (" with rope_positions=True" if nr else ""))
         q, k, v = in_dims[:3]
+        if nr:  # behind the key lengths / segment ids, in front of the score bias
+            ri = len(in_dims) - nb - 1
+            if not attrs.get("rope_dim"):
+                raise ValueError("multihead_attention: rope_position_ids needs rotary")
+            check_rope_ids_dims("multihead_attention", in_dims[ri], in_dtypes[ri], q[0], q[1], k[1])
+            in_dims = [d for i, d in enumerate(in_dims) if i != ri]
         if attrs.get("segment_ids"):
             check_segment_ids_dims("multihead_attention", in_dims, nb, q[0], q[1], k[1])
         elif len(in_dims) - nb == 4:
@@ -313,6 +360,14 @@ class MultiHeadAttention(OpImpl):
         kd = attrs.get("kdim") or E // H
         vd = attrs.get("vdim") or E // H
         attrs["kdim"], attrs["vdim"] = kd, vd
+        if attrs.get("rope_dim"):
+            rd, maxp = attrs["rope_dim"], attrs["rope_max_positions"]
+            if rd < 2 or rd % 2 or rd > kd:
+                raise ValueError(f"multihead_attention: the rotary dim must be even and in [2, {kd}], got {rd}")
+            if attrs.get("rope_inv_freq") is not None and len(attrs["rope_inv_freq"]) != rd // 2:
+                raise ValueError(f"multihead_attention: rotary inv_freq must hold {rd // 2} values")
+            if not nr and maxp < max(q[1], k[1]):
+                raise ValueError(f"multihead_attention: rotary max_positions ({maxp}) is below the sequence length")
         dt = in_dtypes[0]
         kinit = attrs.get("kernel_init")
         from ..core.initializers import ZeroInitializer
@@ -353,13 +408,28 @@ class MultiHeadAttention(OpImpl):
         maps = [(0, 1, None), (0, None, None), (0, None, None)]
         if self._has_key_lens():  # key lengths: sharded with the batch, replicated over the heads axis
             maps.append((0,) + (None,) * (len(self.layer.inputs[3].dims) - 1))
+        if self.attrs.get("rope_positions"):  # the key lengths' map
+            maps.append((0, None))
         if self.attrs.get("attn_bias"):
             maps.append(attn_bias_map(self.layer.inputs[-1].dims, self.layer.inputs[0].dims[0],
                                       self.attrs["num_heads"], 0, self.H_AXIS))
         return maps
 
     def _has_key_lens(self):  # or segment ids: the same place and the same sharding
-        return len(self.layer.inputs) - (1 if self.attrs.get("attn_bias") else 0) > 3
+        return len(self.layer.inputs) - (1 if self.attrs.get("attn_bias") else 0) - \
+            (1 if self.attrs.get("rope_positions") else 0) > 3
+
+    def setup_device(self, device):
+        """Called once by the executor, outside any captured region: uploads the rotary table."""
+        rope = rope_attrs(self.attrs)
+        if rope is not None:
+            rope_table_of(rope, device)
+
+    def _rope(self, pos, inverse, qb, kb, B, Hl, Hkv, Sq, Sk, kd, qs, ks):
+        """One launch that rotates the Q and K head rows in place (inverse: dq / dk back)."""
+        rope = rope_attrs(self.attrs)
+        K.rope(qb, qs, kb, ks, B, Hl, Hkv, Sq, Sk, kd, rope[0], rope_table_of(rope, qb.device), pos=pos,
+               interleaved=rope[2], inverse=inverse)
 
     def needs_input_grad(self, i):
         return i < 3
@@ -402,7 +472,12 @@ class MultiHeadAttention(OpImpl):
         B, Sq, _ = q_in.shape
         has_bias = bool(self.attrs.get("attn_bias"))
         has_seg = bool(self.attrs.get("segment_ids"))
-        kl = K.attn_key_lens(xs[3], B, q_in.device) if len(xs) - has_bias > 3 and not has_seg else None
+        has_pos = bool(self.attrs.get("rope_positions"))
+        kl = K.attn_key_lens(xs[3], B, q_in.device) if len(xs) - has_bias - has_pos > 3 and not has_seg else None
+        rope = rope_attrs(self.attrs)
+        pos = xs[len(xs) - has_bias - 1] if has_pos else None
+        if pos is not None and (pos.dtype != torch.int32 or pos.device != q_in.device or not pos.is_contiguous()):
+            pos = pos.to(device=q_in.device, dtype=torch.int32).contiguous()
         seg = K.attn_segments(xs[3], B, Sq, q_in.device) if has_seg else None
         Sk = k_in.shape[1]
         kd, vd = self.attrs["kdim"], self.attrs["vdim"]
@@ -443,6 +518,8 @@ class MultiHeadAttention(OpImpl):
             ks = [Sk * Hkv * kd, kd, Hkv * kd]
             vs = [Sk * Hkv * vd, vd, Hkv * vd]
             s.update(q=qv, k=kv, v=vv)
+        if rope is not None:  # q and k are rotated where they lie; what is saved above is the rotated heads
+            self._rope(pos, False, qv, kv, B, Hl, Hkv, Sq, Sk, kd, qs, ks)
         o = torch.empty(B, Sq, Hl, vd, device=q_in.device, dtype=q_in.dtype)
         os_ = [Sq * Hl * vd, vd, Hl * vd]
         bias = K.attn_score_bias(xs[-1], B, Hl, Sq, Sk, q_in.device) if has_bias else None
@@ -456,7 +533,7 @@ class MultiHeadAttention(OpImpl):
         if ctx.training:
             s.update(o=o, wo=wo, has_bo=bo is not None, shape=(B, Sq, Sk, Hl, kd, vd, E), fused=fused,
                      qs=qs, ks=ks, vs=vs, os=os_, scale=scale, causal=causal, key_lens=kl, drop=drop, sbias=bias,
-                     seg=seg, Hkv=Hkv)
+                     seg=seg, Hkv=Hkv, rope_pos=pos)
         return [y.view(B, Sq, E)]
 
     def overwrites_wgrad(self, i):
@@ -495,12 +572,16 @@ class MultiHeadAttention(OpImpl):
             dq, dk, dv = torch.empty_like(qv), torch.empty_like(kv), torch.empty_like(vv)
         # fused projection: the flash kernel can add the QKV bias gradient (column sums of dq / dk / dv)
         # itself, sparing linear_bwd a pass over dqkv (bias_act_bwd + fold); never with a score bias
-        dbq = gw("qkv_bias") if (fused and os.environ.get("FF_ATTN_BIAS_FUSION", "1") == "1") else None
+        # nor with rotary: the kernel would sum dq / dk columns before they are rotated back
+        rope = rope_attrs(self.attrs)
+        dbq = gw("qkv_bias") if (fused and rope is None and os.environ.get("FF_ATTN_BIAS_FUSION", "1") == "1") else None
         if dbq is not None and not (dbq.dtype == torch.float32 and dbq.is_contiguous()):
             dbq = None
         bias_done = attn_core_bwd(s, qv, qs, kv, ks, vv, vs, o, os_, do, os_, dq, dk, dv, B, Hl, Sq, Sk, kd, vd, scale,
                                   causal, kl, drop, s.get("sbias"), dbq.view(-1) if dbq is not None else None,
                                   seg=s.get("seg"), Hkv=s.get("Hkv"))
+        if rope is not None:  # the rotation's backward: dq / dk rotated by the negated angle, in place
+            self._rope(s.get("rope_pos"), True, dq, dk, B, Hl, s.get("Hkv") or Hl, Sq, Sk, kd, qs, ks)
         if fused:
             dw = gw("qkv_weight")
             db = None if bias_done else gw("qkv_bias")

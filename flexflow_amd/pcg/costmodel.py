@@ -198,7 +198,9 @@ def cost_key(layer, cfg: OpConfig, compute_dtype: DataType) -> tuple:
     need_dx0 = bool(layer.inputs) and layer.inputs[0].owner_layer is not None and \
         layer.inputs[0].owner_layer.op_type != OperatorType.OP_INPUT
     # an attention layer's key lengths are timed as a dense batch (fabricate_int_input), so they
-    # are left out of the key: the layer shares the measured entry of the same layer without them
+    # are left out of the key: the layer shares the measured entry of the same layer without them.
+    # Rotary position ids are timed as arange(S), what the layer without them rotates by, and are left
+    # out likewise (the rope_* attributes are in cost_params_key, so the rotation itself is priced)
     n_in = 3 if layer.op_type == OperatorType.OP_MULTIHEAD_ATTENTION else len(lo.inputs)
     return (layer.op_type, cost_params_key(layer), tuple(l.local_shape(0) for l in lo.inputs[:n_in]),
             tuple(l.local_shape(0) for l in lo.weights), cfg.degrees, compute_dtype, need_dx0,
@@ -213,10 +215,25 @@ def is_score_bias_input(layer, i: int) -> bool:
         bool(layer.attrs.get("attn_bias")) and i == len(layer.inputs) - 1
 
 
+def is_rope_ids_input(layer, i: int) -> bool:
+    """Input i of `layer` is the rotary position ids (attribute rope_positions): the last input of a
+    rotary_embedding, the one in front of the score bias (or the last) of an attention layer."""
+    if not layer.attrs.get("rope_positions"):
+        return False
+    if layer.op_type == OperatorType.OP_ROPE:
+        return i == 1
+    return layer.op_type == OperatorType.OP_MULTIHEAD_ATTENTION and \
+        i == len(layer.inputs) - 1 - (1 if layer.attrs.get("attn_bias") else 0)
+
+
 def fabricate_int_input(layer, i: int, shp, cfg: OpConfig, device) -> torch.Tensor:
     """A stand-in for integer input i of `layer` when its cost is measured: embedding indices over
     the local table, an attention layer's key lengths all equal to Sk (a dense batch: random small
-    lengths would time a nearly empty attention), otherwise 0 / 1."""
+    lengths would time a nearly empty attention), rotary position ids arange(S) in every row (what an
+    unpacked batch feeds; they sit behind the key lengths / segment ids, so they are looked for first),
+    otherwise 0 / 1."""
+    if is_rope_ids_input(layer, i):
+        return torch.arange(int(shp[-1]), device=device, dtype=torch.int32).expand(tuple(shp)).contiguous()
     if layer.op_type in (OperatorType.OP_MULTIHEAD_ATTENTION, OperatorType.OP_SDPA) and i == 3 and \
             layer.attrs.get("segment_ids"):  # packed rows: one full-length segment per row
         return torch.zeros(tuple(shp), device=device, dtype=torch.int32)

@@ -121,6 +121,12 @@ class Executor:
             self.rng_step = torch.zeros(1, dtype=torch.int64, device=self.device)
             for c in self.ctx.values():
                 c.rng_step = self.rng_step
+        # per-layer device state that must exist before a step is captured (a rotary layer's cos / sin
+        # table: built on the host and uploaded here, never in a forward)
+        for L in self.layers:
+            setup = getattr(L.impl, "setup_device", None)
+            if setup is not None:
+                setup(self.device)
         self.producer_layout: Dict[int, Layout] = {}
         for L in self.layers:
             for o, lo in zip(L.outputs, self.lay[L.name].outputs):

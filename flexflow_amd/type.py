@@ -168,6 +168,7 @@ class OperatorType(IntEnum):
     OP_LSTM = 100  # extension: LSTM layer (the reference's legacy nmt/ app, outside FFModel)
     OP_RMS_NORM = 101  # extension: RMS norm (T5 / LLaMA), met by the HuggingFace import path
     OP_SDPA = 102  # extension: scaled dot-product attention on projected heads, with an additive score bias
+    OP_ROPE = 103  # extension: rotary position embedding of projected heads (ops/rope.py)
 
 
 class OpType(Enum):
