@@ -886,6 +886,77 @@ void rope(Tensor q, Tensor q_out, std::vector<int64_t> qs, int64_t Hq, int64_t S
   ffk::rope(a, cur_stream());
 }
 
+// Gated linear units (ops.h GluArgs): every tensor is a [rows, F] view with a contiguous last dim and
+// its own row stride (two tensors, the halves of a packed [rows, 2F] buffer, views into wider ones).
+int64_t glu_row_stride(const Tensor& t, const Tensor& g, bool output, const char* fn, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == g.device() && t.scalar_type() == g.scalar_type(), fn, ": ", name,
+              " must share g's device and dtype");
+  TORCH_CHECK(t.dim() == 2 && t.size(0) == g.size(0) && t.size(1) == g.size(1), fn, ": ", name, " must be [",
+              g.size(0), ", ", g.size(1), "], got ", t.sizes());
+  TORCH_CHECK(t.size(1) <= 1 || t.stride(1) == 1, fn, ": ", name, " needs a contiguous last dim, got stride ",
+              t.stride(1));
+  if (t.size(0) <= 1) return t.size(1);
+  TORCH_CHECK(t.stride(0) >= (output ? t.size(1) : 0), fn, ": ", name, " has row stride ", t.stride(0), " for ",
+              t.size(1), " columns");
+  return t.stride(0);
+}
+// An output shares no element with another operand (the kernels' pointers are __restrict__): their
+// byte ranges are disjoint, or both have one row stride and their columns interleave (the halves of a
+// packed buffer). so / sx: the row strides glu_row_stride returned.
+void glu_check_disjoint(const Tensor& out, int64_t so, const Tensor& x, int64_t sx, const char* fn, const char* no,
+                        const char* nx) {
+  const int64_t rows = out.size(0), F = out.size(1), eb = out.element_size();
+  if (rows == 0 || F == 0) return;
+  const int64_t po = (int64_t)(uintptr_t)out.data_ptr(), px = (int64_t)(uintptr_t)x.data_ptr();
+  const int64_t eo = ((rows - 1) * so + F) * eb, ex = ((rows - 1) * sx + F) * eb;
+  if (po + eo <= px || px + ex <= po) return;
+  bool ok = false;
+  if (rows > 1 && so == sx) {
+    const int64_t sb = so * eb, Fb = F * eb;
+    const int64_t m = (((px - po) % sb) + sb) % sb;  // column offset of x's rows inside out's rows
+    ok = m >= Fb && sb - m >= Fb;
+  }
+  TORCH_CHECK(ok, fn, ": ", no, " overlaps ", nx);
+}
+void glu_fwd(Tensor g, Tensor u, Tensor y, int64_t act, int64_t max_blocks) {
+  check_dev(g, "g");
+  TORCH_CHECK(g.dim() == 2, "glu_fwd: g must be 2-D");
+  TORCH_CHECK(act >= 0 && act < 5, "glu_fwd: unknown activation code ", act);
+  ffk::GluArgs a;
+  a.dt = dtcode(g), a.act = (int)act;
+  a.rows = g.size(0), a.F = g.size(1);
+  a.sg = glu_row_stride(g, g, false, "glu_fwd", "g");
+  a.su = glu_row_stride(u, g, false, "glu_fwd", "u");
+  a.sy = glu_row_stride(y, g, true, "glu_fwd", "y");
+  glu_check_disjoint(y, a.sy, g, a.sg, "glu_fwd", "y", "g");
+  glu_check_disjoint(y, a.sy, u, a.su, "glu_fwd", "y", "u");
+  a.g = g.data_ptr(), a.u = u.data_ptr(), a.y = y.data_ptr();
+  ffk::glu_fwd(a, cur_stream(), (int)std::max<int64_t>(0, std::min<int64_t>(max_blocks, 1 << 20)));
+}
+void glu_bwd(Tensor g, Tensor u, Tensor dy, Tensor dg, Tensor du, int64_t act, int64_t max_blocks) {
+  check_dev(g, "g");
+  TORCH_CHECK(g.dim() == 2, "glu_bwd: g must be 2-D");
+  TORCH_CHECK(act >= 0 && act < 5, "glu_bwd: unknown activation code ", act);
+  ffk::GluArgs a;
+  a.dt = dtcode(g), a.act = (int)act;
+  a.rows = g.size(0), a.F = g.size(1);
+  a.sg = glu_row_stride(g, g, false, "glu_bwd", "g");
+  a.su = glu_row_stride(u, g, false, "glu_bwd", "u");
+  a.sdy = glu_row_stride(dy, g, false, "glu_bwd", "dy");
+  a.sdg = glu_row_stride(dg, g, true, "glu_bwd", "dg");
+  a.sdu = glu_row_stride(du, g, true, "glu_bwd", "du");
+  glu_check_disjoint(dg, a.sdg, du, a.sdu, "glu_bwd", "dg", "du");
+  for (const Tensor* o : {&dg, &du}) {
+    const int64_t so = o == &dg ? a.sdg : a.sdu;
+    const char* no = o == &dg ? "dg" : "du";
+    glu_check_disjoint(*o, so, g, a.sg, "glu_bwd", no, "g");
+    glu_check_disjoint(*o, so, u, a.su, "glu_bwd", no, "u");
+    glu_check_disjoint(*o, so, dy, a.sdy, "glu_bwd", no, "dy");
+  }
+  a.g = g.data_ptr(), a.u = u.data_ptr(), a.dy = dy.data_ptr(), a.dg = dg.data_ptr(), a.du = du.data_ptr();
+  ffk::glu_bwd(a, cur_stream(), (int)std::max<int64_t>(0, std::min<int64_t>(max_blocks, 1 << 20)));
+}
+
 // s [H, Sq, Sk] (fp32 scores of sample b) = -inf outside the query's run; lo / hi int32 [B, Sq]
 void segment_mask_f32(Tensor s, Tensor lo, Tensor hi, int64_t b, int64_t H, int64_t Sq, int64_t Sk) {
   check_dev(s, "s");
@@ -1370,6 +1441,9 @@ PYBIND11_MODULE(_C, m) {
   m.def("rope", &rope, py::arg("q"), py::arg("q_out"), py::arg("qs"), py::arg("Hq"), py::arg("Sq"), py::arg("k"),
         py::arg("k_out"), py::arg("ks"), py::arg("Hk"), py::arg("Sk"), py::arg("B"), py::arg("D"), py::arg("rd"),
         py::arg("table"), py::arg("pos") = py::none(), py::arg("interleaved") = false, py::arg("inverse") = false);
+  m.def("glu_fwd", &glu_fwd, py::arg("g"), py::arg("u"), py::arg("y"), py::arg("act"), py::arg("max_blocks") = 0);
+  m.def("glu_bwd", &glu_bwd, py::arg("g"), py::arg("u"), py::arg("dy"), py::arg("dg"), py::arg("du"), py::arg("act"),
+        py::arg("max_blocks") = 0);
   m.def("segment_mask_f32", &segment_mask_f32);
   m.def("attn_dropout_f32", &attn_dropout_f32);
   m.def("attn_dropout_mask", &attn_dropout_mask);

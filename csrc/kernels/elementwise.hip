@@ -3,6 +3,7 @@
 // Replaces reference src/ops/element_unary.cu, src/ops/kernels/element_binary_kernels.cu,
 // src/ops/kernels/dropout_kernels.cu, src/ops/kernels/cast_kernels.cu.
 #include "common.h"
+#include "glu_act.h"
 #include "ops.h"
 
 #include <vector>
@@ -33,6 +34,7 @@ __device__ __forceinline__ float unary_f(int op, float x, float s) {
     case U_SQRT: return sqrtf(x);
     case U_NEG: return -x;
     case U_LEAKY_RELU: return x > 0.f ? x : x * s;
+    case U_SILU: return silu_f(x);  // finite for every finite x (glu_act.h)
     default: return x;
   }
 }
@@ -62,6 +64,7 @@ __device__ __forceinline__ float unary_df(int op, float x, float y, float s) {
     case U_SQRT: return 0.5f / y;
     case U_NEG: return -1.f;
     case U_LEAKY_RELU: return x > 0.f ? 1.f : s;
+    case U_SILU: return silu_df(x);
     default: return 1.f;
   }
 }

@@ -12,7 +12,7 @@ enum DType : int { DT_F32 = 0, DT_BF16 = 1 };
 enum UnaryOp : int {
   U_RELU = 0, U_SIGMOID, U_TANH, U_ELU, U_GELU, U_EXP, U_SIN, U_COS, U_RSQRT, U_POW, U_IDENTITY,
   U_SCALAR_MUL, U_SCALAR_ADD, U_SCALAR_SUB, U_SCALAR_TRUEDIV, U_SCALAR_FLOORDIV, U_LOG, U_SQRT, U_NEG,
-  U_LEAKY_RELU
+  U_LEAKY_RELU, U_SILU
 };
 enum BinaryOp : int { B_ADD = 0, B_SUB, B_MUL, B_DIV, B_MAX, B_MIN };
 
@@ -79,6 +79,30 @@ struct RopeArgs {
   int interleaved = 0, inverse = 0;
 };
 void rope(const RopeArgs& a, hipStream_t st);
+
+// glu.hip: gated linear units. y[r][c] = act(g[r][c]) * u[r][c] for r < rows, c < F, and the backward
+// dg = dy * u * act'(g), du = dy * act(g), one launch each. Every operand is addressed as base + r *
+// its own row stride (elements) + c, so g / u (and dg / du) may be two tensors, the halves of one
+// packed [rows][2F] buffer, or views into wider buffers; outputs must not overlap themselves (row
+// stride >= F) and nothing outside their rows < rows, columns < F is written. act: GluAct (glu_act.h):
+// 0 silu, 1 gelu (erf), 2 gelu_tanh, 3 relu, 4 sigmoid. fp32 arithmetic, one rounding per output;
+// act(g) and act'(g) are recomputed from g in the backward. 16-byte accesses where F, the row strides
+// and the base pointers allow, element accesses otherwise (chosen per launch). max_blocks > 0 caps
+// the grid below the usual cap.
+struct GluArgs {
+  int dt = DT_BF16;
+  int act = 0;
+  int64_t rows = 0, F = 0;
+  const void* g = nullptr;
+  const void* u = nullptr;
+  void* y = nullptr;         // forward only
+  const void* dy = nullptr;  // backward only, as dg and du
+  void* dg = nullptr;
+  void* du = nullptr;
+  int64_t sg = 0, su = 0, sy = 0, sdy = 0, sdg = 0, sdu = 0;
+};
+void glu_fwd(const GluArgs& a, hipStream_t st, int max_blocks = 0);
+void glu_bwd(const GluArgs& a, hipStream_t st, int max_blocks = 0);
 
 // transfer.hip: one launch over a list of boxes (pack / unpack / local re-layout of activation
 // shards); desc: device int64 [nbox][box_words()] (see transfer.hip), units of vec_bytes (copy)

@@ -3,6 +3,9 @@ position table), and per block RMSNorm, rotary grouped-query attention (`multihe
 causal=True, num_kv_heads=.., rotary=..)`), then a GELU MLP (flexflow_amd/models/decoder.py). The task is
 learnable (the label of a token is its next id), so the loss falls over a few steps.
 
+`--mlp swiglu` / `--mlp geglu` replace the GELU MLP by the gated FFN of the LLaMA family (`gated_ffn`:
+down(act(gate(x)) * up(x)), the gate one launch of the glu op); `--fused-gate-up` makes gate and up one GEMM.
+
 `--packed` trains on packed rows (flexflow_amd/utils/packing.py): sentences of random lengths are put back to
 back into rows of `--seq-length` tokens; the loader feeds per-token `segment_ids` (attention stays inside a
 sentence) and `position_ids` that restart at every sentence, which the rotation reads on the device
@@ -11,6 +14,7 @@ sentence) and `position_ids` that restart at every sentence, which the rotation 
     python examples/python/native/rope_decoder.py -b 8 --iterations 20
     python examples/python/native/rope_decoder.py --small --iterations 8            # CPU-sized
     python examples/python/native/rope_decoder.py --small --packed --iterations 8
+    python examples/python/native/rope_decoder.py --small --mlp swiglu --iterations 8
 """
 import argparse
 import sys
@@ -30,11 +34,14 @@ def top_level_task(argv=None):
     ap = argparse.ArgumentParser(add_help=False)
     ap.add_argument("--seq-length", type=int, default=0)
     ap.add_argument("--packed", action="store_true")
+    ap.add_argument("--mlp", choices=("gelu", "swiglu", "geglu"), default="gelu")
+    ap.add_argument("--fused-gate-up", action="store_true")
     args, rest = ap.parse_known_args(sys.argv[1:] if argv is None else argv)
     ffconfig, ffmodel, small, iterations = zoo.setup(rest)
     b = ffconfig.batch_size
     dc = DecoderConfig.tiny(args.seq_length or 32) if small else \
         DecoderConfig(hidden=512, heads=8, kv_heads=2, layers=4, ffn=2048, vocab=4096, seq=args.seq_length or 256)
+    dc.mlp, dc.fused_gate_up = args.mlp, args.fused_gate_up
     s = dc.seq
     seg = pos = None
     if args.packed:
@@ -75,6 +82,8 @@ def top_level_task(argv=None):
           (" packed" if args.packed else "", steps, b, s, run_time, b * steps / run_time))
     if args.packed:
         print("packed: %d sentences, fill ratio %.3f" % (len(lens), fill))
+    glu = [L for L in ffmodel.layers if L.op_type == OperatorType.OP_GLU]
+    print("mlp %s: %d glu ops, %d packed" % (dc.mlp, len(glu), sum(bool(L.attrs.get("packed")) for L in glu)))
     print("loss first %.4f last %.4f" % (losses[0], losses[-1]))
     return losses
 

@@ -179,6 +179,10 @@ class FFModel:
     def gelu(self, input, inplace=True, name=None):
         return self._unary(OperatorType.OP_GELU, input, name)
 
+    def silu(self, input, name=None):
+        """x * sigmoid(x) (extension: SiLU / swish; torch's aten.silu, Keras' "silu" / "swish")."""
+        return self._unary(OperatorType.OP_SILU, input, name)
+
     def elu(self, input, inplace=True, name=None):
         return self._unary(OperatorType.OP_ELU, input, name)
 
@@ -397,6 +401,43 @@ class FFModel:
             ins.append(position_ids)
             kw["rope_positions"] = True
         return self._add(OperatorType.OP_ROPE, ins, name, seq_dim=int(seq_dim), **kw).outputs[0]
+
+    def glu(self, gate, up=None, activation="silu", name=None):
+        """Gated linear unit (extension; ops/glu.py): activation(gate) * up in one launch, activation one of
+        silu (SwiGLU), gelu, gelu_tanh (GeGLU), relu, sigmoid (the original GLU). gate / up: same shape and
+        dtype. up=None: `gate` is packed, its last dim 2F holding the gate in [..., :F] and the up in
+        [..., F:] (one GEMM's output); the result's last dim is F."""
+        from .. import kernels as K
+        K.glu_act_code("glu", activation)
+        if up is None:
+            if not gate.dims or gate.dims[-1] % 2:
+                raise ValueError(f"glu: the packed input's last dim must be even (gate | up), got {list(gate.dims)}")
+            return self._add(OperatorType.OP_GLU, [gate], name, activation=str(activation), packed=True).outputs[0]
+        if tuple(gate.dims) != tuple(up.dims):
+            raise ValueError(f"glu: gate and up must have one shape, got {list(gate.dims)} and {list(up.dims)}")
+        if gate.data_type != up.data_type:
+            raise ValueError(f"glu: gate and up must have one dtype, got {gate.data_type.name} and {up.data_type.name}")
+        return self._add(OperatorType.OP_GLU, [gate, up], name, activation=str(activation)).outputs[0]
+
+    def gated_ffn(self, x, ffn_dim, out_dim=None, activation="silu", use_bias=False, fused_gate_up=False, name=None):
+        """The gated FFN of the LLaMA family: down(activation(gate(x)) * up(x)), built from dense, glu and
+        dense (layers {name}_gate, {name}_up, {name}_glu, {name}_down). fused_gate_up: gate and up as one
+        dense of 2 * ffn_dim outputs ({name}_gate_up, gate columns first) and the packed glu: one GEMM
+        less, but the packed columns cannot be sharded. out_dim defaults to x's last dim."""
+        from .. import kernels as K
+        K.glu_act_code("gated_ffn", activation)
+        if int(ffn_dim) < 1:
+            raise ValueError(f"gated_ffn: ffn_dim must be positive, got {ffn_dim}")
+        out_dim = int(x.dims[-1] if out_dim is None else out_dim)
+        n = (lambda s: None) if name is None else (lambda s: f"{name}_{s}")
+        if fused_gate_up:
+            gu = self.dense(x, 2 * int(ffn_dim), use_bias=use_bias, name=n("gate_up"))
+            h = self.glu(gu, activation=activation, name=n("glu"))
+        else:
+            g = self.dense(x, int(ffn_dim), use_bias=use_bias, name=n("gate"))
+            u = self.dense(x, int(ffn_dim), use_bias=use_bias, name=n("up"))
+            h = self.glu(g, u, activation=activation, name=n("glu"))
+        return self.dense(h, out_dim, use_bias=use_bias, name=n("down"))
 
     # ---- shape ops
     def concat(self, tensors, axis, name=None):

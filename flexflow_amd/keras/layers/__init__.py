@@ -233,7 +233,7 @@ class Activation(Layer):
     def _lower(self, ff, xs):
         a = self.activation
         fn = {"softmax": ff.softmax, "relu": ff.relu, "sigmoid": ff.sigmoid, "tanh": ff.tanh, "elu": ff.elu,
-              "gelu": ff.gelu, "linear": ff.identity}[a]
+              "gelu": ff.gelu, "silu": ff.silu, "swish": ff.silu, "linear": ff.identity}[a]
         return [self._track(ff, fn(xs[0], name=self.name))]
 
 

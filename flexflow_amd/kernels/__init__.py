@@ -1494,6 +1494,17 @@ def mse_grad(pred, label, gscale):
 U = dict(relu=0, sigmoid=1, tanh=2, elu=3, gelu=4, exp=5, sin=6, cos=7, rsqrt=8, pow=9, identity=10,
          scalar_multiply=11, scalar_add=12, scalar_sub=13, scalar_true_divide=14, scalar_floor_divide=15, log=16,
          sqrt=17, neg=18, leaky_relu=19)
+# unary functions behind the reference's element-unary set (codes continue ops.h UnaryOp). Do not merge
+# this into U: tests/test_small_kernels_gpu.py asserts at import that set(U) equals its own list of cases
+# (one per reference op), so a new name in U stops that whole module from being collected
+U_MORE = dict(silu=20)
+
+
+def unary_code(name) -> int:
+    c = U.get(name, U_MORE.get(name))
+    if c is None:
+        raise ValueError(f"unknown unary function {name!r}")
+    return c
 
 
 def unary_ref(name, x, s):
@@ -1506,6 +1517,7 @@ def unary_ref(name, x, s):
         "scalar_add": lambda: xf + s, "scalar_sub": lambda: xf - s, "scalar_true_divide": lambda: xf / s,
         "scalar_floor_divide": lambda: torch.floor(xf / s), "log": lambda: torch.log(xf),
         "sqrt": lambda: torch.sqrt(xf), "neg": lambda: -xf, "leaky_relu": lambda: F.leaky_relu(xf, s),
+        "silu": lambda: F.silu(xf),
     }[name]()
     return r.to(x.dtype)
 
@@ -1567,7 +1579,7 @@ def unary_fwd(name, x, s=0.0, out=None):
     if native(x) and x.dtype in (torch.bfloat16, torch.float32):
         xc = _dense(x)
         y = out if out is not None else torch.empty_like(xc)
-        ext().unary_fwd(xc, y, U[name], float(s))
+        ext().unary_fwd(xc, y, unary_code(name), float(s))
         return y
     r = unary_ref(name, x, s)
     if out is not None:
@@ -1581,12 +1593,122 @@ def unary_bwd(name, x, y, dy, s=0.0):
         xc = _dense(x)
         dyc = _like(dy, xc)
         dx = torch.empty_like(dyc)
-        ext().unary_bwd(xc, _like(y, xc), dyc, dx, U[name], float(s), False)
+        ext().unary_bwd(xc, _like(y, xc), dyc, dx, unary_code(name), float(s), False)
         return dx
     xr = x.detach().float().requires_grad_()
     out = unary_ref(name, xr, s).float() if name != "identity" else xr * 1.0
     (g,) = torch.autograd.grad(out, xr, dy.float())
     return g.to(dy.dtype)
+
+
+# ------------------------------------------------------------------ gated linear units (glu.hip)
+GLU_ACTS = dict(silu=0, gelu=1, gelu_tanh=2, relu=3, sigmoid=4)
+
+
+def glu_act_code(what, act) -> int:
+    if act not in GLU_ACTS:
+        raise ValueError(f"{what}: unknown activation {act!r} (one of {sorted(GLU_ACTS)})")
+    return GLU_ACTS[act]
+
+
+def _glu_act_f32(gf, act):
+    if act == "silu":
+        return gf * torch.sigmoid(gf)
+    if act == "gelu":
+        return F.gelu(gf)
+    if act == "gelu_tanh":
+        return F.gelu(gf, approximate="tanh")
+    if act == "relu":
+        return torch.relu(gf)
+    if act == "sigmoid":
+        return torch.sigmoid(gf)
+    raise ValueError(f"glu: unknown activation {act!r} (one of {sorted(GLU_ACTS)})")
+
+
+def glu_ref(g, u, act):
+    """y = act(g) * u by the definition glu.hip implements: plain torch, fp32 arithmetic, one rounding to
+    g's dtype. act: silu (x sigmoid(x)), gelu (erf form), gelu_tanh, relu, sigmoid. The CPU path."""
+    return (_glu_act_f32(g.float(), act) * u.float()).to(g.dtype)
+
+
+def _glu_2d(what, t, like=None):
+    """t as a [rows, F] view (no copy) when its leading dims collapse and its last dim is contiguous;
+    otherwise a contiguous copy's view."""
+    if like is not None and (tuple(t.shape) != tuple(like.shape) or t.dtype != like.dtype):
+        raise ValueError(f"{what}: operands must share one shape and dtype, got {list(t.shape)} {t.dtype} and "
+                         f"{list(like.shape)} {like.dtype}")
+    if t.dim() == 0:
+        raise ValueError(f"{what}: operands need at least one dim")
+    F_ = t.shape[-1]
+    if t.dim() == 2 and (F_ <= 1 or t.stride(1) == 1):
+        return t
+    if t.dim() == 1:
+        return t.unsqueeze(0) if (F_ <= 1 or t.stride(0) == 1) else t.contiguous().unsqueeze(0)
+    if F_ <= 1 or t.stride(-1) == 1:
+        try:
+            return t.view(-1, F_)  # raises where the leading dims do not collapse into one stride
+        except RuntimeError:
+            pass
+    return t.contiguous().view(-1, F_)
+
+
+def _glu_out(what, out, like):
+    if tuple(out.shape) != tuple(like.shape) or out.dtype != like.dtype or out.device != like.device:
+        raise ValueError(f"{what}: an output must have the operands' shape, dtype and device, got "
+                         f"{list(out.shape)} {out.dtype}")
+    o2 = _glu_2d(what, out)
+    if o2.data_ptr() != out.data_ptr():  # _glu_2d had to copy
+        raise ValueError(f"{what}: an output must be a strided view with a contiguous last dim whose leading dims "
+                         f"collapse, got strides {list(out.stride())}")
+    return o2
+
+
+@torch.no_grad()
+def glu_fwd(g, u, act, out=None, max_blocks=0):
+    """y = act(g) * u in ONE launch (glu.hip). g / u: same shape and dtype, any strided views with a
+    contiguous last dim whose leading dims collapse to one row stride (two tensors, the halves x[..., :F]
+    / x[..., F:] of a packed buffer, views into wider buffers: none is copied); other layouts are made
+    contiguous first. out: a view of the same kind to write into. Without a native device, or for other
+    dtypes than bf16 / fp32, the same definition runs as glu_ref."""
+    code = glu_act_code("glu_fwd", act)
+    g2 = _glu_2d("glu_fwd", g)
+    u2 = _glu_2d("glu_fwd", u, g)
+    if out is None:
+        out = torch.empty(g.shape, dtype=g.dtype, device=g.device)
+    o2 = _glu_out("glu_fwd", out, g)
+    if native(g) and g.dtype in (torch.bfloat16, torch.float32):
+        ext().glu_fwd(g2, u2, o2, code, int(max_blocks))
+    else:
+        o2.copy_(glu_ref(g2, u2, act))
+    return out
+
+
+def glu_bwd(g, u, dy, act, dg=None, du=None, max_blocks=0):
+    """(dg, du) = (dy * u * act'(g), dy * act(g)) in ONE launch; act(g) and act'(g) are recomputed from
+    g. dg / du: views to write into (e.g. the halves of one [.., 2F] gradient buffer), as glu_fwd's
+    out. Without a native device: autograd through glu_ref's arithmetic."""
+    code = glu_act_code("glu_bwd", act)
+    g2 = _glu_2d("glu_bwd", g)
+    u2 = _glu_2d("glu_bwd", u, g)
+    dy2 = _glu_2d("glu_bwd", dy, g)
+    if dg is None:
+        dg = torch.empty(g.shape, dtype=g.dtype, device=g.device)
+    if du is None:
+        du = torch.empty(g.shape, dtype=g.dtype, device=g.device)
+    dg2, du2 = _glu_out("glu_bwd", dg, g), _glu_out("glu_bwd", du, g)
+    if native(g) and g.dtype in (torch.bfloat16, torch.float32):
+        with torch.no_grad():
+            ext().glu_bwd(g2, u2, dy2, dg2, du2, code, int(max_blocks))
+        return dg, du
+    gr = g2.detach().float().requires_grad_()
+    ur = u2.detach().float().requires_grad_()
+    with torch.enable_grad():
+        y = _glu_act_f32(gr, act) * ur
+    a, b = torch.autograd.grad(y, (gr, ur), dy2.detach().float())
+    with torch.no_grad():
+        dg2.copy_(a)
+        du2.copy_(b)
+    return dg, du
 
 
 B = dict(add=0, sub=1, mul=2, div=3, max=4, min=5)

@@ -22,6 +22,7 @@ UNARY = {
     OperatorType.OP_SCALAR_SUB: "scalar_sub", OperatorType.OP_SCALAR_TRUE_DIV: "scalar_true_divide",
     OperatorType.OP_SCALAR_FLOOR_DIV: "scalar_floor_divide", OperatorType.OP_LOG: "log",
     OperatorType.OP_SQRT: "sqrt", OperatorType.OP_LEAKYRELU: "leaky_relu",
+    OperatorType.OP_SILU: "silu",  # extension; not in INPLACE_OK: its gradient needs x
 }
 
 

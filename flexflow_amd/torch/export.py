@@ -19,6 +19,10 @@ shapes of the given batch / sequence lengths) and the graph is mapped directly:
   batch_matmul -> (+ bias) -> softmax -> batch_matmul, or with fuse_sdpa=True one
   scaled_dot_product_attention op (ops/sdpa.py: the flash kernels with the constant mask as their
   additive score bias, no [B, H, Sq, Sk] scores or probabilities).
+* silu maps to the unary silu op. With fuse_glu=True a mul(act(a), b) (either operand order) whose
+  activation node is silu, gelu (approximate none / tanh), relu or sigmoid, feeds nothing else, and
+  whose a and b are model-dependent tensors of one shape becomes one glu op (ops/glu.py: the LLaMA /
+  Mistral / Qwen gate in one launch, no saved activation); anything else imports as before.
 
 The builders are resolved lazily from the graph outputs, so folded or replaced sub-graphs emit
 no dead FF layers.
@@ -59,9 +63,10 @@ def _example_inputs(model, input_names, batch_size, seq_length):
 
 
 class ExportImporter:
-    def __init__(self, model, input_names, batch_size=1, seq_length=None, fuse_sdpa=False):
+    def __init__(self, model, input_names, batch_size=1, seq_length=None, fuse_sdpa=False, fuse_glu=False):
         self.model = model
         self.fuse_sdpa = bool(fuse_sdpa)
+        self.fuse_glu = bool(fuse_glu)
         self.input_names = list(input_names or ["input_ids"])
         self.batch_size = batch_size
         self.seq_length = seq_length
@@ -191,6 +196,25 @@ class ExportImporter:
             return strip(h), float(eps)
         return None
 
+    def _glu_gate(self, g, u):
+        """mul(g, u) is a gated linear unit when g = act(a) with act one the glu op has, g feeds nothing
+        else, and a and u are model-dependent tensors of one shape: the activation's name, else None."""
+        if not (isinstance(g, torch.fx.Node) and isinstance(u, torch.fx.Node)) or self._is_const(g) or self._is_const(u):
+            return None
+        if g.op != "call_function" or len(g.users) != 1 or g.name in self._env:
+            return None
+        if g.target == aten.gelu.default:
+            approx = g.kwargs.get("approximate", g.args[1] if len(g.args) > 1 else "none")
+            act = {"none": "gelu", "tanh": "gelu_tanh"}.get(approx)
+        else:
+            act = {aten.silu.default: "silu", aten.relu.default: "relu", aten.sigmoid.default: "sigmoid"}.get(g.target)
+        a = g.args[0]
+        if act is None or not isinstance(a, torch.fx.Node) or self._is_const(a):
+            return None
+        if self._shape(a) != self._shape(u):
+            return None
+        return act
+
     def _build(self, n):
         ff, tgt, a = self._ff, n.target, n.args
         name = n.name
@@ -221,6 +245,11 @@ class ExportImporter:
                         out = ff.rms_norm(self._val(h), eps, name=name)
                         self._copies.append((ff.layers[-1].weights[0], self._const[w_.name].float().numpy()))
                         return out
+            if self.fuse_glu and tgt == aten.mul.Tensor:
+                for g_, u_ in ((x, y), (y, x)):
+                    act = self._glu_gate(g_, u_)
+                    if act is not None:
+                        return ff.glu(self._val(g_.args[0]), self._val(u_), activation=act, name=name)
             return self._binary("mul", x, y, name)
         if tgt in (aten.add.Tensor, aten.add.Scalar):
             if len(a) > 2 and a[2] != 1:
@@ -247,6 +276,8 @@ class ExportImporter:
             return ff.relu(self._val(a[0]), inplace=False, name=name)
         if tgt == aten.gelu.default:
             return ff.gelu(self._val(a[0]), inplace=False, name=name)
+        if tgt == aten.silu.default:
+            return ff.silu(self._val(a[0]), name=name)
         if tgt == aten.exp.default:
             return ff.exp(self._val(a[0]), name=name)
         if tgt == aten.sigmoid.default:

@@ -108,7 +108,7 @@ def _enc_module(m, node) -> (OpType, List[str]):
             raise NotImplementedError("MultiheadAttention(batch_first=False)")
         return OpType.MULTIHEAD_ATTENTION, [m.embed_dim, m.num_heads, int(m.in_proj_bias is not None), float(m.dropout)]
     simple = {nn.ReLU: OpType.RELU, nn.GELU: OpType.GELU, nn.Sigmoid: OpType.SIGMOID, nn.Tanh: OpType.TANH,
-              nn.ELU: OpType.ELU, nn.Identity: OpType.IDENTITY}
+              nn.ELU: OpType.ELU, nn.Identity: OpType.IDENTITY, nn.SiLU: OpType.SILU}
     for cls, op in simple.items():
         if isinstance(m, cls):
             return op, []
@@ -128,7 +128,7 @@ _SCALAR = {"add": OpType.SCALAR_ADD, "sub": OpType.SCALAR_SUB, "mul": OpType.SCA
            "iadd": OpType.SCALAR_ADD, "isub": OpType.SCALAR_SUB, "imul": OpType.SCALAR_MULTIPLY}
 _UNARY = {"relu": OpType.RELU, "gelu": OpType.GELU, "tanh": OpType.TANH, "sigmoid": OpType.SIGMOID,
           "exp": OpType.EXP, "rsqrt": OpType.RSQRT, "sin": OpType.SIN, "cos": OpType.COS, "elu": OpType.ELU,
-          "contiguous": OpType.CONTIGUOUS, "float": OpType.FLOAT}
+          "silu": OpType.SILU, "contiguous": OpType.CONTIGUOUS, "float": OpType.FLOAT}
 
 
 def _is_node(a):
@@ -256,7 +256,8 @@ def _build(ff, node: IRNode, ins: list, name: str):
         drop = float(a[3]) if len(a) > 3 else 0.0  # .ff files written before the field: no dropout
         return (ff.multihead_attention(q, k, v, E, H, E // H, E // H, drop, bias, name=name), None)
     unary = {OpType.RELU: ff.relu, OpType.GELU: ff.gelu, OpType.SIGMOID: ff.sigmoid, OpType.TANH: ff.tanh,
-             OpType.ELU: ff.elu, OpType.EXP: ff.exp, OpType.RSQRT: ff.rsqrt, OpType.SIN: ff.sin, OpType.COS: ff.cos}
+             OpType.ELU: ff.elu, OpType.EXP: ff.exp, OpType.RSQRT: ff.rsqrt, OpType.SIN: ff.sin, OpType.COS: ff.cos,
+             OpType.SILU: ff.silu}
     if op in unary:
         return unary[op](x, name=name)
     if op in (OpType.IDENTITY, OpType.CONTIGUOUS, OpType.FLOAT, OpType.TO, OpType.TYPE_AS):
@@ -324,9 +325,11 @@ def _build(ff, node: IRNode, ins: list, name: str):
 class PyTorchModel:
     """reference PyTorchModel (python/flexflow/torch/model.py:2408-2607)."""
 
-    def __init__(self, model, is_hf_model=False, input_names=None, batch_size=1, seq_length=None, fuse_sdpa=False):
+    def __init__(self, model, is_hf_model=False, input_names=None, batch_size=1, seq_length=None, fuse_sdpa=False,
+                 fuse_glu=False):
         """fuse_sdpa (HuggingFace import): map every scaled_dot_product_attention to one fused attention
-        op instead of batch_matmul / softmax / batch_matmul (torch/export.py)."""
+        op instead of batch_matmul / softmax / batch_matmul (torch/export.py). fuse_glu (same path): map
+        every mul(act(a), b) with act one of silu / gelu / relu / sigmoid to one gated linear unit op."""
         import torch
         assert isinstance(model, torch.nn.Module)
         self.model = model
@@ -335,6 +338,7 @@ class PyTorchModel:
         self.batch_size = batch_size
         self.seq_length = seq_length
         self.fuse_sdpa = bool(fuse_sdpa)
+        self.fuse_glu = bool(fuse_glu)
         self._ff_of_module: Dict[str, object] = {}
 
     # ------------------------------------------------------------------ tracing
@@ -394,7 +398,8 @@ class PyTorchModel:
     def torch_to_ff(self, ffmodel, input_tensors, verbose=False):
         if self.is_hf_model and not self._hf_fx_available():
             from .export import ExportImporter
-            imp = ExportImporter(self.model, self.input_names, self.batch_size, self.seq_length, fuse_sdpa=self.fuse_sdpa)
+            imp = ExportImporter(self.model, self.input_names, self.batch_size, self.seq_length, fuse_sdpa=self.fuse_sdpa,
+                                 fuse_glu=self.fuse_glu)
             return imp.to_ff(ffmodel, input_tensors)
         nodes = self._trace()
         outs, built = PyTorchModel._build_nodes(nodes, ffmodel, input_tensors, verbose)

@@ -169,6 +169,8 @@ class OperatorType(IntEnum):
     OP_RMS_NORM = 101  # extension: RMS norm (T5 / LLaMA), met by the HuggingFace import path
     OP_SDPA = 102  # extension: scaled dot-product attention on projected heads, with an additive score bias
     OP_ROPE = 103  # extension: rotary position embedding of projected heads (ops/rope.py)
+    OP_SILU = 104  # extension: x * sigmoid(x), element-unary (ops/elementwise.py)
+    OP_GLU = 105  # extension: gated linear unit act(gate) * up: SwiGLU / GeGLU / ReGLU / GLU (ops/glu.py)
 
 
 class OpType(Enum):
@@ -229,6 +231,7 @@ class OpType(Enum):
     TYPE_AS = 2104
     VIEW = 2105
     GATHER = 2106
+    SILU = 2107  # extension: nn.SiLU / F.silu in the fx front end
     ATTRIBUTE = 2200
 
 
