@@ -64,8 +64,22 @@ struct AttnArgs {
   // attn_bwd1b_kernel have none, so attn_bwd then leaves the fused bias gradient to the caller).
   // They bound their mask tests and tile loops by the runs; memory bounds stay on Sq / Sk. A padding
   // position gives o = 0, lse = +inf and zero dq / dk / dv rows.
+  //
+  // The kernels know no segments, only row intervals: query i sees the keys [seg_lo[b][i],
+  // seg_hi[b][i]) and key j is seen by the queries [seg_klo[b][j], seg_khi[b][j]). The contract:
+  //  * all four arrays are int32 [B][S] and non-decreasing along a row;
+  //  * the key side is the transpose of the query side: j in [lo[i], hi[i]) <=> i in [klo[j], khi[j]);
+  //  * an empty interval is anchored at its own index (lo[i] = hi[i] = i, klo[j] = khi[j] = j).
+  // seg_klo / seg_khi null (both) means the query-side arrays: a symmetric relation, which runs are.
+  // Half a pair, or a key side without the query side, is an error: attn_bwd launches nothing.
+  // A sliding window (attn_band_bounds: the band [i - left, i + right], alone or cut to the runs) is
+  // such a family with a key side of its own, [j - right, j + left]. The forward reads the query side
+  // only; the backward takes a lane's mask test from the key side and its query-tile ranges and dQ
+  // chains from the query side. The causal bound is applied on top by both.
   const int* seg_lo = nullptr;
   const int* seg_hi = nullptr;
+  const int* seg_klo = nullptr;
+  const int* seg_khi = nullptr;
   // grouped-query / multi-query attention: Hkv key / value heads under H query heads, query head h
   // reading KV head h / G with G = H / Hkv (torch's enable_gqa, repeat_interleave(G) over heads). 0 or
   // H: every head has its own K / V, what the kernels did before. With 0 < Hkv < H the strides k_s*,
@@ -84,6 +98,15 @@ struct AttnArgs {
 // [lo[i], hi[i]) is the run of position i; a padding position (id < 0) gets lo = hi = i. One
 // workgroup per row, nothing read on the host.
 void attn_seg_bounds(const int* ids, int* lo, int* hi, int B, int S, hipStream_t st);
+// Sliding window: lo / hi (query side) and klo / khi (key side), int32 [B][S] each, of the band
+// i - left <= j <= i + right (left / right < 0: unbounded on that side), cut to the runs seg_lo /
+// seg_hi of attn_seg_bounds when those are given (both or neither; [B][S]):
+//   lo[i] = max(seg_lo[i], i - left)    hi[i] = min(seg_hi[i], i + right + 1)
+//   klo[j] = max(seg_lo[j], j - right)  khi[j] = min(seg_hi[j], j + left + 1)
+// with 0 / S for the run without segments; a padding position (seg_lo == seg_hi) keeps its empty
+// interval on both sides. Element-wise, nothing read on the host. The outputs may not alias the inputs.
+void attn_band_bounds(int left, int right, const int* seg_lo, const int* seg_hi, int* lo, int* hi, int* klo, int* khi,
+                      int B, int S, hipStream_t st);
 // scores [H][Sq][Sk] (fp32) of one sample: -inf outside the query's run (rows lo / hi of that sample)
 void segment_mask_f32(float* s, int H, int Sq, int Sk, const int* lo, const int* hi, hipStream_t st);
 

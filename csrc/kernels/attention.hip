@@ -21,6 +21,7 @@
 #include "ops.h"
 #include "attention.h"
 #include "attn_dropout.h"
+#include <cstdio>
 #include <type_traits>
 #include <utility>
 
@@ -227,6 +228,12 @@ __global__ void __launch_bounds__(256, DMA ? (DROP || BIAS || SEG ? 3 : 4) : (D 
   // The deferred-max decision below is taken per wave; in a wave whose rows are not all of one run
   // (wmixed) a row moves its max only on its own account, so that no output of a segment depends on
   // the values of another one (a wave of one run decides as the other forms do: bitwise equal to them).
+  // The intervals need not be runs (attention.h): with a sliding window narrower than the wave's rows
+  // (left + right < 31) the common range is empty, wlo >= whi. Then kbase < wlo or kbase + KV > whi
+  // holds for every kbase, so every tile is masked per lane; and wmixed is true, since equal lo and
+  // equal hi at the wave's first and last row would make all 32 intervals the one common range, which
+  // is empty only for a padding row, and padding rows are anchored at distinct indices (the one
+  // exception, a wave whose only row is the sequence's last and padding, has nothing to decide).
   int slo = 0, shi = 0, wlo = 0, whi = 0, t0 = 0;
   bool wmixed = false;
   if constexpr (SEG) {
@@ -810,8 +817,9 @@ __device__ __forceinline__ unsigned pack_bf2(float x, float y) {
 //    lane owns one key, so the 16 bias elements of a 32-query block are 4-B loads that the lanes of
 //    a half-wave coalesce along a bias row; they are requested ahead of the block's S / dP MFMAs
 //    and predicated on key < Sk and q < Sq. The bias takes no gradient (dS is not written out).
-//  * SEG (packed sequences, AttnArgs.seg_lo / seg_hi; always MASK = true, never BIAS): the lane tests
-//    the query index against its own key's run, a key block runs only the query tiles whose dQ chain
+//  * SEG (packed sequences and sliding windows, AttnArgs.seg_lo / seg_hi and the key side seg_klo /
+//    seg_khi; always MASK = true, never BIAS): the lane tests the query index against its own key's
+//    interval, a key block runs only the query tiles whose dQ chain
 //    it is part of, and each tile's chain starts and ends at key blocks of its own (at qt_begin below).
 template <int D, int NW, bool MASK, bool CHAIN, bool DMA = false, bool DROP = false, bool BIAS = false, bool SEG = false>
 __global__ void __launch_bounds__(64 * NW, 8 / NW) attn_bwd_kernel(AttnArgs a, int nkb, int pass) {
@@ -911,15 +919,23 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) attn_bwd_kernel(AttnArgs a, i
 #pragma unroll
   for (int i = 0; i < D / 32; ++i) { dk[i] = f32x16{}; dv[i] = f32x16{}; }
   const int nqt = (a.Sq + QT - 1) / QT;
-  // SEG (AttnArgs.seg_lo / seg_hi; Sq == Sk): query q sees this lane's key iff q lies in the key's
-  // own run [klo, klo + klen), since both sides share one segmentation; [wlo, whi) are the queries every key
-  // of the wave sees (lo / hi do not decrease along a row). Query tile t has a chain of key blocks of
-  // its own, seg_first(t) .. seg_last(t), from the lo of its first row and the hi of its last (and
-  // the causal diagonal): exactly those blocks run it, the first starts the fp32 dQ sum without
-  // reading it and the last writes the bf16 dQ, so every tile's dQ is written once, an all-padding
-  // tile's as zeros (first <= last always: no chain is empty). Both ends do not decrease with t, so
-  // a block's tiles are one interval [qt_begin, qt_end), and every query that sees one of its keys
-  // lies in it.
+  // SEG (row intervals, attention.h; Sq == Sk): two sides of one relation are read here.
+  // Key side (seg_klo / seg_khi; the query-side arrays where the relation is symmetric, as runs are):
+  // query q sees this lane's key iff q lies in the key's interval [klo, klo + klen), and [wlo, whi)
+  // are the queries every key of the wave sees (klo / khi do not decrease along a row; with a band
+  // narrower than the wave's 32 keys that range is empty, wlo >= whi, and then the wave-uniform test
+  // below asks for the mask on every block: x < wlo or x + 32 > whi holds for every x).
+  // Query side (seg_lo / seg_hi): query tile t has a chain of key blocks of its own, seg_first(t) ..
+  // seg_last(t), from the lo of its first row and the hi of its last (and the causal diagonal):
+  // exactly those blocks run it, the first starts the fp32 dQ sum without reading it and the last
+  // writes the bf16 dQ, so every tile's dQ is written once, an all-padding tile's as zeros (first <=
+  // last always: no chain is empty). lo / hi do not decrease along a row, so neither end decreases
+  // with t and a block's tiles are one interval [qt_begin, qt_end). Every query q that sees a key j
+  // of the block lies in it, and that needs the query side alone: lo[first row of q's tile] <= lo[q]
+  // <= j gives seg_first <= kblk, hi[last row] >= hi[q] > j (and last row >= q >= j with causal) gives
+  // seg_last >= kblk. A block of the chain in which the tile sees no key (a band's corner) runs the
+  // tile with every P masked to 0: it adds nothing and carries the sum on. The transpose property is
+  // what makes the key-side test mask exactly the pairs the forward masked.
   const int* seglo = nullptr;
   const int* seghi = nullptr;
   int klo = 0, wlo = 0, whi = 0;
@@ -937,11 +953,13 @@ __global__ void __launch_bounds__(64 * NW, 8 / NW) attn_bwd_kernel(AttnArgs a, i
   auto seg_tiles = [&](int& end) {
     seglo = a.seg_lo + (int64_t)b * a.Sq;
     seghi = a.seg_hi + (int64_t)b * a.Sq;
+    const int* kseglo = a.seg_klo + (int64_t)b * a.Sq;  // attn_bwd points these at seg_lo / seg_hi when the caller gave none
+    const int* kseghi = a.seg_khi + (int64_t)b * a.Sq;
     const int kc = min(key, a.Sk - 1);
-    klo = a.causal ? max(seglo[kc], key) : seglo[kc];
-    klen = key < a.Sk ? (unsigned)max(seghi[kc] - klo, 0) : 0u;
-    wlo = __builtin_amdgcn_readfirstlane(seglo[min(kb0 + wave * 32 + 31, a.Sk - 1)]);
-    whi = __builtin_amdgcn_readfirstlane(seghi[min(kb0 + wave * 32, a.Sk - 1)]);
+    klo = a.causal ? max(kseglo[kc], key) : kseglo[kc];
+    klen = key < a.Sk ? (unsigned)max(kseghi[kc] - klo, 0) : 0u;
+    wlo = __builtin_amdgcn_readfirstlane(kseglo[min(kb0 + wave * 32 + 31, a.Sk - 1)]);
+    whi = __builtin_amdgcn_readfirstlane(kseghi[min(kb0 + wave * 32, a.Sk - 1)]);
     int begin = 0;
     while (begin < nqt && seg_last(begin, seg_first(begin)) < kblk) ++begin;
     end = begin;
@@ -1983,6 +2001,69 @@ void attn_seg_bounds(const int* ids, int* lo, int* hi, int B, int S, hipStream_t
   hipLaunchKernelGGL(attn_seg_bounds_kernel, dim3((unsigned)B), dim3(256), 0, st, ids, lo, hi, S);
 }
 
+// ------------------------------------------------------------------ sliding window (band bounds)
+// Element-wise, four positions per thread: the band around position p cut to its run [slo, shi) (0 / S
+// without segments), on the query side (left keys before, right behind) and, transposed, on the key
+// side. left / right < 0: that side is unbounded. A padding position (slo >= shi) keeps slo / shi.
+// VEC: S % 4 == 0 and 16-B aligned pointers, so a quad lies in one row and moves as int4.
+template <bool VEC>
+__global__ void __launch_bounds__(256) attn_band_bounds_kernel(int left, int right, const int* __restrict__ seg_lo,
+                                                               const int* __restrict__ seg_hi, int* __restrict__ lo,
+                                                               int* __restrict__ hi, int* __restrict__ klo,
+                                                               int* __restrict__ khi, int64_t n, int S) {
+  const int64_t e0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (e0 >= n) return;
+  int sl[4], sh[4], o[4][4];
+  if (VEC && seg_lo) {
+    const int4 a = *reinterpret_cast<const int4*>(seg_lo + e0), c = *reinterpret_cast<const int4*>(seg_hi + e0);
+    sl[0] = a.x; sl[1] = a.y; sl[2] = a.z; sl[3] = a.w;
+    sh[0] = c.x; sh[1] = c.y; sh[2] = c.z; sh[3] = c.w;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const bool in = e0 + j < n;
+      sl[j] = seg_lo ? (in ? seg_lo[e0 + j] : 0) : 0;
+      sh[j] = seg_lo ? (in ? seg_hi[e0 + j] : 0) : S;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int p = (int)((e0 + j) % S);
+    const bool pad = sl[j] >= sh[j];
+    // p + x + 1 cannot overflow: x < S - 1 after the caller's clamp, and p < S
+    o[0][j] = pad || left < 0 ? sl[j] : max(sl[j], p - left);
+    o[1][j] = pad || right < 0 ? sh[j] : min(sh[j], p + right + 1);
+    o[2][j] = pad || right < 0 ? sl[j] : max(sl[j], p - right);
+    o[3][j] = pad || left < 0 ? sh[j] : min(sh[j], p + left + 1);
+  }
+  int* const outs[4] = {lo, hi, klo, khi};
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+    if (VEC) {
+      *reinterpret_cast<int4*>(outs[a] + e0) = make_int4(o[a][0], o[a][1], o[a][2], o[a][3]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (e0 + j < n) outs[a][e0 + j] = o[a][j];
+    }
+  }
+}
+
+void attn_band_bounds(int left, int right, const int* seg_lo, const int* seg_hi, int* lo, int* hi, int* klo, int* khi,
+                      int B, int S, hipStream_t st) {
+  if (B <= 0 || S <= 0) return;
+  // sizes at or past S - 1 bound nothing; clamping keeps p + size + 1 inside int32
+  left = left < 0 || left >= S - 1 ? -1 : left;
+  right = right < 0 || right >= S - 1 ? -1 : right;
+  const int64_t n = (int64_t)B * S;
+  const dim3 grid((unsigned)(((n + 3) / 4 + 255) / 256));
+  uintptr_t al = (uintptr_t)lo | (uintptr_t)hi | (uintptr_t)klo | (uintptr_t)khi | (uintptr_t)seg_lo | (uintptr_t)seg_hi;
+  if (S % 4 == 0 && (al & 15) == 0)
+    hipLaunchKernelGGL(attn_band_bounds_kernel<true>, grid, dim3(256), 0, st, left, right, seg_lo, seg_hi, lo, hi, klo, khi, n, S);
+  else
+    hipLaunchKernelGGL(attn_band_bounds_kernel<false>, grid, dim3(256), 0, st, left, right, seg_lo, seg_hi, lo, hi, klo, khi, n, S);
+}
+
 // the fp32 device path: scores [H][Sq][Sk] of one sample, -inf outside the query's run
 __global__ void segment_mask_kernel(float* __restrict__ s, int64_t n, int Sq, int Sk, const int* __restrict__ lo,
                                     const int* __restrict__ hi) {
@@ -2091,6 +2172,18 @@ bool attn_bwd(AttnArgs a, hipStream_t st) {
   const bool drop = a.drop_thr > 0;
   if (drop && a.H_total <= 0) a.H_total = a.H;
   kv_groups(a);
+  // the interval arrays come in pairs, the key side only beside the query side: anything else would
+  // compute gradients under another mask than the forward's, so nothing is launched (the bindings
+  // reject it with a message before they get here)
+  if (!a.seg_lo != !a.seg_hi || !a.seg_klo != !a.seg_khi || (a.seg_klo && !a.seg_lo)) {
+    fprintf(stderr, "attn_bwd: seg_lo / seg_hi and seg_klo / seg_khi come in pairs, the key side beside the query side; nothing launched\n");
+    return false;
+  }
+  // no key-side intervals given: the relation is symmetric (runs), the key side is the query side
+  if (a.seg_lo && !a.seg_klo) {
+    a.seg_klo = a.seg_lo;
+    a.seg_khi = a.seg_hi;
+  }
   // grouped-query attention: the kernels store each query head's dK / dV into the expanded buffers
   // (contiguous rows: the 16-B row stores as they are) and attn_kv_group_sum_kernel folds the groups
   // into the caller's dk / dv behind them; no fused bias gradient (dbp is laid out for [3][H][D])

@@ -805,8 +805,11 @@ void attn_sbias_args(ffk::AttnArgs& a, const Tensor& q, const optional<Tensor>& 
 // on q's device; the query and the key side share them, and there is no form with a score bias or
 // key lengths (a padding id says what a length would)
 void attn_seg_args(ffk::AttnArgs& a, const Tensor& q, const optional<Tensor>& lo, const optional<Tensor>& hi,
-                   int64_t B, int64_t Sq, int64_t Sk) {
+                   int64_t B, int64_t Sq, int64_t Sk, const optional<Tensor>& klo = {}, const optional<Tensor>& khi = {}) {
   const bool has_lo = lo.has_value() && lo->defined(), has_hi = hi.has_value() && hi->defined();
+  const bool has_klo = klo.has_value() && klo->defined(), has_khi = khi.has_value() && khi->defined();
+  TORCH_CHECK(has_klo == has_khi, "attn: seg_klo and seg_khi come together");
+  TORCH_CHECK(!has_klo || (has_lo && has_hi), "attn: seg_klo / seg_khi (the key side) need seg_lo / seg_hi");
   if (!has_lo && !has_hi) return;
   TORCH_CHECK(has_lo && has_hi, "attn: seg_lo and seg_hi come together");
   for (const Tensor* t : {&*lo, &*hi}) {
@@ -819,6 +822,35 @@ void attn_seg_args(ffk::AttnArgs& a, const Tensor& q, const optional<Tensor>& lo
   TORCH_CHECK(a.key_lens == nullptr, "attn: segments with key lengths are not supported (use a padding id)");
   a.seg_lo = lo->data_ptr<int>();
   a.seg_hi = hi->data_ptr<int>();
+  if (has_klo) {  // a relation that is not symmetric (sliding window): the key-side intervals, laid out as seg_lo
+    for (const Tensor* t : {&*klo, &*khi}) {
+      TORCH_CHECK(t->scalar_type() == at::kInt && t->is_contiguous() && t->numel() == B * Sq,
+                  "attn: seg_klo / seg_khi must be contiguous int32 tensors of B * Sq elements, as seg_lo is");
+      TORCH_CHECK(t->device() == q.device(), "attn: seg_klo / seg_khi must be on the device of q");
+    }
+    a.seg_klo = klo->data_ptr<int>();
+    a.seg_khi = khi->data_ptr<int>();
+  }
+}
+
+// lo / hi / klo / khi of a sliding window (ffk::attn_band_bounds), optionally inside the runs seg_lo /
+// seg_hi; every tensor a contiguous int32 [B, S] on one device
+void attn_band_bounds(int64_t left, int64_t right, optional<Tensor> seg_lo, optional<Tensor> seg_hi, Tensor lo, Tensor hi,
+                      Tensor klo, Tensor khi) {
+  check_dev(lo, "lo");
+  TORCH_CHECK(lo.dim() == 2, "attn_band_bounds: lo must be [B, S]");
+  const bool has_lo = seg_lo.has_value() && seg_lo->defined(), has_hi = seg_hi.has_value() && seg_hi->defined();
+  TORCH_CHECK(has_lo == has_hi, "attn_band_bounds: seg_lo and seg_hi come together");
+  std::vector<const Tensor*> ts = {&lo, &hi, &klo, &khi};
+  if (has_lo) { ts.push_back(&*seg_lo); ts.push_back(&*seg_hi); }
+  for (const Tensor* t : ts)
+    TORCH_CHECK(t->scalar_type() == at::kInt && t->is_contiguous() && t->numel() == lo.numel() && t->device() == lo.device(),
+                "attn_band_bounds: all tensors must be contiguous int32 [B, S] on one device");
+  TORCH_CHECK(left >= -1 && right >= -1 && left <= INT32_MAX && right <= INT32_MAX,
+              "attn_band_bounds: window sizes are >= 0, or -1 for unbounded");
+  ffk::attn_band_bounds((int)left, (int)right, has_lo ? seg_lo->data_ptr<int>() : nullptr,
+                        has_lo ? seg_hi->data_ptr<int>() : nullptr, lo.data_ptr<int>(), hi.data_ptr<int>(),
+                        klo.data_ptr<int>(), khi.data_ptr<int>(), (int)lo.size(0), (int)lo.size(1), cur_stream());
 }
 
 void attn_seg_bounds(Tensor ids, Tensor lo, Tensor hi) {
@@ -994,7 +1026,7 @@ void attn_fwd(Tensor q, std::vector<int64_t> qs, Tensor k, std::vector<int64_t> 
               int64_t Sq, int64_t Sk, int64_t D, double scale, bool causal, optional<Tensor> key_lens,
               int64_t drop_thr, optional<Tensor> rng_step, int64_t rng_seed, int64_t b0, int64_t h0, int64_t H_total,
               optional<Tensor> sbias, int64_t sbias_sb, int64_t sbias_sh, optional<Tensor> seg_lo,
-              optional<Tensor> seg_hi, int64_t Hkv) {
+              optional<Tensor> seg_hi, int64_t Hkv, optional<Tensor> seg_klo, optional<Tensor> seg_khi) {
   TORCH_CHECK(D == 64 || D == 128, "flash attention supports head_dim 64/128");
   TORCH_CHECK(q.scalar_type() == at::kBFloat16 && o.scalar_type() == at::kBFloat16);
   TORCH_CHECK(lse.numel() >= B * H * Sq && lse.scalar_type() == at::kFloat);
@@ -1010,7 +1042,7 @@ void attn_fwd(Tensor q, std::vector<int64_t> qs, Tensor k, std::vector<int64_t> 
   a.key_lens = attn_key_lens(key_lens, q, B);
   attn_drop_args(a, q, drop_thr, rng_step, rng_seed, b0, h0, H_total, H);
   attn_sbias_args(a, q, sbias, sbias_sb, sbias_sh, B, H, Sq, Sk);
-  attn_seg_args(a, q, seg_lo, seg_hi, B, Sq, Sk);
+  attn_seg_args(a, q, seg_lo, seg_hi, B, Sq, Sk, seg_klo, seg_khi);
   ffk::attn_fwd(a, cur_stream());
 }
 int64_t attn_bwd_ws(int64_t B, int64_t H, int64_t Sq, int64_t Sk, int64_t D, int64_t Hkv) {
@@ -1023,7 +1055,7 @@ bool attn_bwd(Tensor q, std::vector<int64_t> qs, Tensor k, std::vector<int64_t> 
               double scale, bool causal, optional<Tensor> dbias, optional<Tensor> key_lens, int64_t drop_thr,
               optional<Tensor> rng_step, int64_t rng_seed, int64_t b0, int64_t h0, int64_t H_total,
               optional<Tensor> sbias, int64_t sbias_sb, int64_t sbias_sh, optional<Tensor> seg_lo,
-              optional<Tensor> seg_hi, int64_t Hkv) {
+              optional<Tensor> seg_hi, int64_t Hkv, optional<Tensor> seg_klo, optional<Tensor> seg_khi) {
   TORCH_CHECK(D == 64 || D == 128, "flash attention supports head_dim 64/128");
   TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.numel() >= ffk::attn_bwd_workspace_floats(B, H, Sq, Sk, D, Hkv),
               "attn_bwd: workspace too small");
@@ -1057,7 +1089,7 @@ bool attn_bwd(Tensor q, std::vector<int64_t> qs, Tensor k, std::vector<int64_t> 
   a.key_lens = attn_key_lens(key_lens, q, B);
   attn_drop_args(a, q, drop_thr, rng_step, rng_seed, b0, h0, H_total, H);
   attn_sbias_args(a, q, sbias, sbias_sb, sbias_sh, B, H, Sq, Sk);
-  attn_seg_args(a, q, seg_lo, seg_hi, B, Sq, Sk);
+  attn_seg_args(a, q, seg_lo, seg_hi, B, Sq, Sk, seg_klo, seg_khi);
   return ffk::attn_bwd(a, cur_stream());
 }
 
@@ -1428,7 +1460,8 @@ PYBIND11_MODULE(_C, m) {
         py::arg("D"), py::arg("scale"), py::arg("causal"), py::arg("key_lens") = py::none(),
         py::arg("drop_thr") = 0, py::arg("rng_step") = py::none(), py::arg("rng_seed") = 0, py::arg("b0") = 0,
         py::arg("h0") = 0, py::arg("H_total") = 0, py::arg("sbias") = py::none(), py::arg("sbias_sb") = 0,
-        py::arg("sbias_sh") = 0, py::arg("seg_lo") = py::none(), py::arg("seg_hi") = py::none(), py::arg("Hkv") = 0);
+        py::arg("sbias_sh") = 0, py::arg("seg_lo") = py::none(), py::arg("seg_hi") = py::none(), py::arg("Hkv") = 0,
+        py::arg("seg_klo") = py::none(), py::arg("seg_khi") = py::none());
   m.def("attn_bwd", &attn_bwd, py::arg("q"), py::arg("qs"), py::arg("k"), py::arg("ks"), py::arg("v"), py::arg("vs"),
         py::arg("o"), py::arg("os"), py::arg("dout"), py::arg("dos"), py::arg("lse"), py::arg("dq"), py::arg("dqs"),
         py::arg("dk"), py::arg("dks"), py::arg("dv"), py::arg("dvs"), py::arg("ws"), py::arg("B"), py::arg("H"),
@@ -1436,8 +1469,10 @@ PYBIND11_MODULE(_C, m) {
         py::arg("dbias") = py::none(), py::arg("key_lens") = py::none(), py::arg("drop_thr") = 0,
         py::arg("rng_step") = py::none(), py::arg("rng_seed") = 0, py::arg("b0") = 0, py::arg("h0") = 0,
         py::arg("H_total") = 0, py::arg("sbias") = py::none(), py::arg("sbias_sb") = 0, py::arg("sbias_sh") = 0,
-        py::arg("seg_lo") = py::none(), py::arg("seg_hi") = py::none(), py::arg("Hkv") = 0);
+        py::arg("seg_lo") = py::none(), py::arg("seg_hi") = py::none(), py::arg("Hkv") = 0,
+        py::arg("seg_klo") = py::none(), py::arg("seg_khi") = py::none());
   m.def("attn_seg_bounds", &attn_seg_bounds);
+  m.def("attn_band_bounds", &attn_band_bounds);
   m.def("rope", &rope, py::arg("q"), py::arg("q_out"), py::arg("qs"), py::arg("Hq"), py::arg("Sq"), py::arg("k"),
         py::arg("k_out"), py::arg("ks"), py::arg("Hk"), py::arg("Sk"), py::arg("B"), py::arg("D"), py::arg("rd"),
         py::arg("table"), py::arg("pos") = py::none(), py::arg("interleaved") = false, py::arg("inverse") = false);

@@ -11,7 +11,11 @@ back into rows of `--seq-length` tokens; the loader feeds per-token `segment_ids
 sentence) and `position_ids` that restart at every sentence, which the rotation reads on the device
 (`rope_position_ids`). The tail of a row is padding (label -100, left out of the loss).
 
+`--window W` is sliding-window attention (`DecoderConfig.sliding_window`): every query sees the last W keys,
+itself included (`window=(W - 1, 0)`), with `--packed` and without.
+
     python examples/python/native/rope_decoder.py -b 8 --iterations 20
+    python examples/python/native/rope_decoder.py --small --packed --window 8 --iterations 8
     python examples/python/native/rope_decoder.py --small --iterations 8            # CPU-sized
     python examples/python/native/rope_decoder.py --small --packed --iterations 8
     python examples/python/native/rope_decoder.py --small --mlp swiglu --iterations 8
@@ -36,12 +40,14 @@ def top_level_task(argv=None):
     ap.add_argument("--packed", action="store_true")
     ap.add_argument("--mlp", choices=("gelu", "swiglu", "geglu"), default="gelu")
     ap.add_argument("--fused-gate-up", action="store_true")
+    ap.add_argument("--window", type=int, default=0)
     args, rest = ap.parse_known_args(sys.argv[1:] if argv is None else argv)
     ffconfig, ffmodel, small, iterations = zoo.setup(rest)
     b = ffconfig.batch_size
     dc = DecoderConfig.tiny(args.seq_length or 32) if small else \
         DecoderConfig(hidden=512, heads=8, kv_heads=2, layers=4, ffn=2048, vocab=4096, seq=args.seq_length or 256)
     dc.mlp, dc.fused_gate_up = args.mlp, args.fused_gate_up
+    dc.sliding_window = args.window
     s = dc.seq
     seg = pos = None
     if args.packed:
@@ -84,6 +90,10 @@ def top_level_task(argv=None):
         print("packed: %d sentences, fill ratio %.3f" % (len(lens), fill))
     glu = [L for L in ffmodel.layers if L.op_type == OperatorType.OP_GLU]
     print("mlp %s: %d glu ops, %d packed" % (dc.mlp, len(glu), sum(bool(L.attrs.get("packed")) for L in glu)))
+    print("%.1f tokens/s (rows x tokens per row, padding included)" % (b * s * steps / run_time))
+    if args.window:
+        win = [L for L in ffmodel.layers if "window_left" in L.attrs]
+        print("sliding window %d: %d windowed attention layers" % (args.window, len(win)))
     print("loss first %.4f last %.4f" % (losses[0], losses[-1]))
     return losses
 

@@ -300,8 +300,14 @@ class FFModel:
     def multihead_attention(self, query, key, value, embed_dim, num_heads, kdim=0, vdim=0, dropout=0.0, bias=True,
                             add_bias_kv=False, add_zero_attn=False, kernel_initializer=None, causal=False, name=None,
                             key_lengths=None, attn_bias=None, segment_ids=None, num_kv_heads=None, rotary=None,
-                            rope_position_ids=None):
-        """rotary: rotary position embeddings (RoPE) on the projected query and key heads: None / False
+                            rope_position_ids=None, window=None):
+        """window: sliding-window (local) attention, flash-attention's window_size convention: None, an
+        int w (w keys on either side) or (left, right); query i sees key j iff i - left <= j <= i + right
+        (and j <= i with causal, and both in one run with segment_ids). None or -1 is unbounded. A side
+        >= seq - 1 is unbounded and causal drops the right side; a window that bounds nothing builds the
+        graph of a call without it. Needs Sq == Sk and goes with neither key_lengths nor attn_bias
+        (padding: negative segment ids). The flash kernels skip the tiles outside the band (ops/attention.py).
+        rotary: rotary position embeddings (RoPE) on the projected query and key heads: None / False
         (default: the graph built as ever), True, or a dict with `dim` (rotated width, even, default the
         per-head kdim), `base` (10000.0), `interleaved` (False: HF / NeoX rotate_half pairs (i, i + dim/2);
         True: GPT-J pairs (2i, 2i + 1)), `scale` (1.0; positions are divided by it), `inv_freq` (None; a
@@ -334,6 +340,8 @@ class FFModel:
             _check_segment_args("multihead_attention", key_lengths, attn_bias)
             ins.append(segment_ids)
             kw["segment_ids"] = True
+        kw.update(self._window_attrs("multihead_attention", window, query.dims[1], key.dims[1], causal, key_lengths,
+                                     attn_bias))
         if rotary:
             kw.update(self._rope_attrs("multihead_attention", rotary, int(kdim) or int(embed_dim) // int(num_heads),
                                        max(query.dims[1], key.dims[1])))
@@ -354,10 +362,10 @@ class FFModel:
                          causal=causal, self_attn=(query is key and key is value), **kw).outputs[0]
 
     def scaled_dot_product_attention(self, q, k, v, attn_bias=None, key_lengths=None, scale=None, causal=False,
-                                     dropout=0.0, name=None, segment_ids=None, enable_gqa=False):
+                                     dropout=0.0, name=None, segment_ids=None, enable_gqa=False, window=None):
         """softmax(scale * q.k^T + attn_bias) . v on projected heads: q [B, H, Sq, D], k [B, H, Sk, D],
         v [B, H, Sk, Dv] -> [B, H, Sq, Dv] (extension; ops/sdpa.py). attn_bias, key_lengths, causal and
-        dropout and segment_ids are those of multihead_attention; scale=None means 1 / sqrt(D).
+        dropout, segment_ids and window are those of multihead_attention; scale=None means 1 / sqrt(D).
         enable_gqa (torch's): k and v may have Hkv heads, Hkv dividing H; query head h reads KV head
         h // (H // Hkv)."""
         if not 0.0 <= float(dropout) < 1.0:
@@ -375,8 +383,25 @@ class FFModel:
             kw["attn_bias"] = True
         if enable_gqa:
             kw["enable_gqa"] = True
+        kw.update(self._window_attrs("scaled_dot_product_attention", window, q.dims[2], k.dims[2], causal, key_lengths,
+                                     attn_bias))
         return self._add(OperatorType.OP_SDPA, ins, name, scale=None if scale is None else float(scale),
                          causal=bool(causal), dropout=float(dropout), **kw).outputs[0]
+
+    @staticmethod
+    def _window_attrs(what, window, Sq, Sk, causal, key_lengths, attn_bias):
+        """The builders' `window` argument as the hashable layer attributes window_left / window_right (-1:
+        unbounded), or nothing at all for a window that bounds nothing (kernels.attn_window_config)."""
+        from .. import kernels as K
+        win = K.attn_window_config(what, window, Sq, Sk, bool(causal))
+        if win is None:
+            return {}
+        if key_lengths is not None:
+            raise ValueError(f"{what}: window cannot be combined with key_lengths (mark padding with a negative "
+                             "segment id)")
+        if attn_bias is not None:
+            raise ValueError(f"{what}: window cannot be combined with attn_bias")
+        return dict(window_left=win[0], window_right=win[1])
 
     @staticmethod
     def _rope_attrs(what, rotary, D, S_max):

@@ -37,6 +37,11 @@ def native(t: torch.Tensor) -> bool:
     return t.is_cuda
 
 
+def native_device(device) -> bool:
+    """native() of a tensor on `device`."""
+    return torch.device(device).type == "cuda"
+
+
 ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH, ACT_GELU = 10, 11, 12, 13, 14
 # kernel-internal: the 'pre-activation' operand holds act'(z) already (stored by the producer's
 # forward, linear_fwd(store_grad=True)); the backward multiplies by it
@@ -1004,20 +1009,149 @@ def attn_seg_bounds(ids):
     return lo, hi
 
 
-def attn_segments(segment_ids, B, S, device):
-    """Per-token segment ids of packed rows as the attention paths take them: (ids, lo, hi), ids a
-    contiguous int32 [B, S] on `device`, lo / hi its run bounds (attn_seg_bounds) on a native device
-    and None elsewhere (the reference path builds its mask from ids), or None. Nothing here reads a
-    value on the host."""
-    if segment_ids is None:
+# ---- sliding-window (local) attention: flash-attention's window_size convention
+def attn_window_config(what, window, Sq, Sk, causal):
+    """The builders' `window` argument, checked and normalised: None | w | (left, right) -> None or the
+    hashable pair (left, right) with -1 for an unbounded side. Query i sees key j iff i - left <= j <=
+    i + right (and j <= i with causal). None or -1 is unbounded, an int w is (w, w). A side >= S - 1 is
+    unbounded, causal drops the right side, and when nothing bounded remains the result is None: the
+    layer is then built as if the keyword had not been given."""
+    if window is None:
         return None
-    ids = segment_ids.reshape(segment_ids.shape[0], -1) if segment_ids.dim() == 3 else segment_ids
-    if tuple(ids.shape) != (B, S):
-        raise ValueError(f"segment_ids: expected [{B}, {S}] (one id per token), got {list(segment_ids.shape)}")
-    if ids.dtype != torch.int32 or ids.device != device or not ids.is_contiguous():
-        ids = ids.to(device=device, dtype=torch.int32).contiguous()
-    lo, hi = attn_seg_bounds(ids) if native(ids) else (None, None)
-    return ids, lo, hi
+    import numbers
+    if isinstance(window, numbers.Real):
+        sides = (window, window)
+    elif isinstance(window, (tuple, list)):
+        sides = tuple(window)
+    else:
+        sides = ()
+    if len(sides) != 2:
+        raise ValueError(f"{what}: window must be None, an int or (left, right), got {window!r}")
+    out = []
+    for w in sides:
+        w = -1 if w is None else w
+        if isinstance(w, bool) or int(w) != w or int(w) < -1:
+            raise ValueError(f"{what}: window sizes must be ints >= 0 (None or -1: unbounded), got {window!r}")
+        out.append(int(w))
+    left, right = out
+    if causal:
+        right = -1
+    if left < 0 and right < 0:
+        return None
+    if Sq != Sk:
+        raise ValueError(f"{what}: window needs Sq == Sk (positions are row indices), got Sq {Sq}, Sk {Sk}")
+    left = -1 if left >= Sq - 1 else left
+    right = -1 if right >= Sq - 1 else right
+    return None if left < 0 and right < 0 else (left, right)
+
+
+def attn_band_bounds_ref(S, left, right, lo=None, hi=None, B=1, device="cpu"):
+    """lo, hi, klo, khi (int32 [B, S]) of the band `left` / `right` (-1: unbounded), optionally inside the
+    runs lo / hi of attn_seg_bounds, with tensor ops on any device: query i sees the keys [lo[i], hi[i])
+    = [max(seg_lo, i - left), min(seg_hi, i + right + 1)) and key j is seen by the queries [klo[j],
+    khi[j]) = [max(seg_lo, j - right), min(seg_hi, j + left + 1)). A padding position (lo == hi) keeps
+    its empty interval on both sides. What attn_band_bounds computes on the device."""
+    if lo is not None:
+        B, device = lo.shape[0], lo.device
+        slo, shi = lo.to(torch.int64), hi.to(torch.int64)
+    else:
+        slo = torch.zeros(B, S, dtype=torch.int64, device=device)
+        shi = torch.full((B, S), S, dtype=torch.int64, device=device)
+    pos = torch.arange(S, device=device, dtype=torch.int64).expand(B, S)
+    pad = slo >= shi
+
+    def side(before, behind):
+        a = slo if before < 0 else torch.maximum(slo, pos - before)
+        b = shi if behind < 0 else torch.minimum(shi, pos + behind + 1)
+        return torch.where(pad, slo, a).to(torch.int32), torch.where(pad, shi, b).to(torch.int32)
+
+    return (*side(left, right), *side(right, left))
+
+
+def attn_band_bounds(S, left, right, lo=None, hi=None, B=1, device="cpu"):
+    """attn_band_bounds_ref by one launch of attn_band_bounds_kernel on a native device (nothing read on
+    the host), attn_band_bounds_ref elsewhere."""
+    if (lo is None) != (hi is None):
+        raise ValueError("attn_band_bounds: the run bounds lo and hi come together")
+    dev = lo.device if lo is not None else torch.device(device)
+    if not native_device(dev):
+        return attn_band_bounds_ref(S, left, right, lo, hi, B, device)
+    if lo is not None:
+        B = lo.shape[0]
+        lo, hi = lo.contiguous(), hi.contiguous()
+    out = tuple(torch.empty(B, S, dtype=torch.int32, device=dev) for _ in range(4))
+    ext().attn_band_bounds(int(left), int(right), lo, hi, *out)
+    return out
+
+
+_BAND_BOUNDS: dict = {}
+
+
+def attn_band_bounds_const(B, S, left, right, device):
+    """The four bound arrays of a window without segment ids, a constant of the layer: built once per
+    (device, S, left, right) for at least B rows (every row is the same, so a shard takes the first B of
+    them) and cached. The executor builds it when it sets a layer up, outside any captured region. An
+    entry is never replaced or freed: a captured graph holds raw pointers into it, so a later caller
+    that needs more rows gets a further entry beside the earlier ones."""
+    entries = _BAND_BOUNDS.setdefault((str(torch.device(device)), int(S), int(left), int(right)), [])
+    t = next((e for e in entries if e[0].shape[0] >= B), None)
+    if t is None:
+        t = attn_band_bounds(S, left, right, B=B, device=device)
+        entries.append(t)
+    return tuple(x[:B] for x in t)
+
+
+def band_mask_ref(S, left, right, causal, ids=None):
+    """bool [B|1, S, S] from the definition: query i sees key j iff i - left <= j <= i + right (-1:
+    unbounded), j <= i with causal, and, with segment ids [B, S], both lie in one run of equal ids >= 0."""
+    dev = ids.device if ids is not None else "cpu"
+    i = torch.arange(S, device=dev)[:, None]
+    j = torch.arange(S, device=dev)[None, :]
+    m = torch.ones(S, S, dtype=torch.bool, device=dev)
+    if left >= 0:
+        m = m & (j >= i - left)
+    if right >= 0:
+        m = m & (j <= i + right)
+    if causal:
+        m = m & (j <= i)
+    if ids is None:
+        return m[None]
+    return m[None] & segment_mask_ref(ids)
+
+
+class AttnSegments(tuple):
+    """(ids, lo, hi, klo, khi, window) as the attention paths take segments and / or a window; the first
+    three are what attn_segments returned before a window existed."""
+    ids = property(lambda s: s[0])
+    window = property(lambda s: s[5])
+
+
+def attn_segments(segment_ids, B, S, device, window=None):
+    """Per-token segment ids of packed rows and / or a sliding window (attn_window_config's pair) as the
+    attention paths take them: (ids, lo, hi, klo, khi, window), or None when neither is given. ids is a
+    contiguous int32 [B, S] on `device` (None without segment ids); lo / hi are the key interval of
+    every query (the run of attn_seg_bounds, cut to the band by attn_band_bounds), klo / khi the query
+    interval of every key (None without a window: the relation is then symmetric), all on a native
+    device and None elsewhere (the reference path builds its mask from ids and window). Nothing here
+    reads a value on the host."""
+    if segment_ids is None and window is None:
+        return None
+    device = torch.device(device)
+    on_device = native_device(device)  # one predicate for the run bounds and the band bounds
+    ids = lo = hi = klo = khi = None
+    if segment_ids is not None:
+        ids = segment_ids.reshape(segment_ids.shape[0], -1) if segment_ids.dim() == 3 else segment_ids
+        if tuple(ids.shape) != (B, S):
+            raise ValueError(f"segment_ids: expected [{B}, {S}] (one id per token), got {list(segment_ids.shape)}")
+        if ids.dtype != torch.int32 or ids.device != device or not ids.is_contiguous():
+            ids = ids.to(device=device, dtype=torch.int32).contiguous()
+        lo, hi = attn_seg_bounds(ids) if on_device else (None, None)
+    if window is not None and on_device:
+        if ids is None:
+            lo, hi, klo, khi = attn_band_bounds_const(B, S, window[0], window[1], device)
+        else:
+            lo, hi, klo, khi = attn_band_bounds(S, window[0], window[1], lo, hi, B=B, device=device)
+    return AttnSegments((ids, lo, hi, klo, khi, window))
 
 
 def segment_mask_ref(ids, causal=False):
@@ -1035,10 +1169,13 @@ def _seg_kw(segments, key_lens, bias, Sq, Sk):
     if segments is None:
         return {}
     if key_lens is not None or bias is not None:
-        raise ValueError("attention: segment_ids cannot be combined with key_lengths or attn_bias")
+        raise ValueError("attention: segment_ids / window cannot be combined with key_lengths or attn_bias")
     if segments[1] is None:
         raise ValueError("attention: the segment bounds are missing (attn_segments on a native device)")
-    return dict(seg_lo=segments[1], seg_hi=segments[2])
+    kw = dict(seg_lo=segments[1], seg_hi=segments[2])
+    if len(segments) > 3 and segments[3] is not None:  # a window: the key side is the transpose
+        kw.update(seg_klo=segments[3], seg_khi=segments[4])
+    return kw
 
 
 # ---- attention dropout: csrc/kernels/attn_dropout.h is the device definition, this is its mirror
@@ -1156,8 +1293,8 @@ def attn_kv_heads(H, Hkv):
 def flash_attn_fwd(q, qs, k, ks, v, vs, o, os_, B, H, Sq, Sk, D, scale, causal, key_lens=None, drop=None, bias=None,
                    segments=None, Hkv=None):
     """Hkv: optional KV head count (attn_kv_heads): k / v and their strides ks / vs then hold Hkv heads.
-    segments: optional packed-sequence runs (attn_segments): attention stays inside a token's own
-    run, a padding position gives o = 0, lse = +inf. key_lens: optional int32 [B] device tensor; key j of sample b is attended iff j < key_lens[b]
+    segments: optional packed-sequence runs and / or a sliding window (attn_segments): attention stays
+    inside a token's own run and band, a padding position gives o = 0, lse = +inf. key_lens: optional int32 [B] device tensor; key j of sample b is attended iff j < key_lens[b]
     (a length of 0: o = 0, lse = +inf). drop: optional attention dropout (thr, rng_step, rng_seed, b0,
     h0, H_total), see _drop_kw / attn_dropout_keep_ref; lse is that of the undropped softmax.
     bias: optional score bias [1|B, 1|H, Sq, Sk] (attn_score_bias)."""

@@ -26,6 +26,7 @@ class DecoderConfig:
     max_positions: int = 0  # 0: seq
     mlp: str = "gelu"  # "gelu" | "swiglu" | "geglu"
     fused_gate_up: bool = False  # gated MLPs: gate and up as one dense of 2 * ffn outputs
+    sliding_window: int = 0  # HuggingFace's convention: every query sees that many keys, itself included; 0: all
 
     @staticmethod
     def tiny(seq=32):
@@ -38,18 +39,23 @@ GATED_MLPS = {"swiglu": "silu", "geglu": "gelu_tanh"}  # DecoderConfig.mlp -> th
 def build_rope_decoder(ff, batch: int, cfg: DecoderConfig, segment_ids=None, position_ids=None):
     """Returns (ids_tensor, output). Output: [batch, seq, vocab] next-token probabilities.
     segment_ids / position_ids: optional int32 [batch, seq] tensors of packed rows (utils/packing.py):
-    attention stays inside a token's own sequence and its position restarts there."""
+    attention stays inside a token's own sequence and its position restarts there.
+    cfg.sliding_window = W (Mistral, Gemma's local layers): every layer attends to the last W keys, the
+    query included, i.e. multihead_attention(window=(W - 1, 0), causal=True); with and without packing."""
     if cfg.mlp != "gelu" and cfg.mlp not in GATED_MLPS:
         raise ValueError(f"build_rope_decoder: unknown mlp {cfg.mlp!r} (one of gelu, {', '.join(GATED_MLPS)})")
     S, H = cfg.seq, cfg.hidden
     rotary = dict(base=cfg.rope_base, max_positions=cfg.max_positions or S)
+    if cfg.sliding_window < 0:
+        raise ValueError(f"build_rope_decoder: sliding_window must be >= 0, got {cfg.sliding_window}")
+    window = (cfg.sliding_window - 1, 0) if cfg.sliding_window else None
     ids = ff.create_tensor([batch, S], DataType.DT_INT32, name="input_ids")
     x = ff.embedding(ids, cfg.vocab, H, AggrMode.AGGR_MODE_NONE, name="tok_emb")
     for l in range(cfg.layers):
         n = ff.rms_norm(x, name=f"l{l}_norm1")
         a = ff.multihead_attention(n, n, n, H, cfg.heads, bias=False, causal=True, name=f"l{l}_attn",
                                    num_kv_heads=cfg.kv_heads, segment_ids=segment_ids, rotary=rotary,
-                                   rope_position_ids=position_ids)
+                                   rope_position_ids=position_ids, window=window)
         x = ff.add(a, x, name=f"l{l}_res1")
         n = ff.rms_norm(x, name=f"l{l}_norm2")
         if cfg.mlp == "gelu":

@@ -43,6 +43,17 @@ SEG forms bound their mask tests and their tile loops by it, so tiles outside a 
 never fetched. Not combined with `key_lengths` (a pad id of -1 says the same) or `attn_bias`. It takes
 no gradient, is sharded with the batch and replicated over the heads axis.
 
+Sliding window (attributes `window_left` / `window_right`, set by the builder's `window=`; -1 is an
+unbounded side; absent for a window that bounds nothing, and then the graph and every launch are what
+they were): query i sees key j iff i - left <= j <= i + right, and j <= i with `causal`, and both lie in
+one run with `segment_ids` (flash-attention's window_size convention). It needs Sq == Sk and goes with
+neither `key_lengths` nor `attn_bias`, the rule of `segment_ids`; padding is said with negative segment
+ids. A small kernel (kernels.attn_band_bounds) writes the key interval of every query and, for the
+backward, the query interval of every key; the flash kernels' SEG forms bound their mask tests and their
+tile loops by them, so the tiles outside the band are never fetched. Without segment ids the arrays are
+a constant of the layer, built when the executor sets it up; with ids they follow the run bounds once
+per layer forward. `flops()` counts the band.
+
 Attention dropout (`dropout` = p in [0, 1), torch's `dropout_p`): in a training forward every
 attention probability is dropped with the effective rate p_eff = round(256 p) / 256 and the kept ones
 are scaled by 1 / (1 - p_eff); evaluation forwards apply nothing, and p_eff = 0 runs exactly the
@@ -100,8 +111,10 @@ def _pad_heads(t, st, B, S, H, d, Dp):
     return out
 
 
-def _attn_ref(q, k, v, scale, causal, key_lens=None, keep=None, keep_scale=1.0, bias=None, segments=None):
-    """segments: optional segment ids [B, S] of packed rows (Sq == Sk == S): query i sees key j iff both
+def _attn_ref(q, k, v, scale, causal, key_lens=None, keep=None, keep_scale=1.0, bias=None, segments=None, window=None):
+    """window: optional sliding window (left, right) with -1 for an unbounded side (Sq == Sk): the mask is
+    kernels.band_mask_ref's, built from the definition, with the runs of `segments` when those are given.
+    segments: optional segment ids [B, S] of packed rows (Sq == Sk == S): query i sees key j iff both
     lie in one run of equal ids >= 0; the mask is built on the tensor's device from the run boundaries
     (kernels.segment_mask_ref), and a padding row gets P = 0. keep: optional bool [B, H, Sq, Sk] attention dropout mask (kernels.attn_dropout_keep_ref), the
     kept probabilities scaled by keep_scale = 1 / (1 - p_eff). bias: optional score bias [1|B, 1|H, Sq,
@@ -115,10 +128,16 @@ def _attn_ref(q, k, v, scale, causal, key_lens=None, keep=None, keep_scale=1.0, 
         s = s + bias.to(device=s.device, dtype=s.dtype)
     if causal:
         s = s.masked_fill(torch.ones(Sq, Sk, dtype=torch.bool, device=s.device).triu(1), float("-inf"))
-    if segments is not None:
+    if segments is not None or window is not None:
         if key_lens is not None or bias is not None:
-            raise ValueError("attention: segment_ids cannot be combined with key_lengths or attn_bias")
-        see = K.segment_mask_ref(segments.to(s.device))[:, None]  # [B, 1, S, S]
+            raise ValueError("attention: segment_ids / window cannot be combined with key_lengths or attn_bias")
+        if window is not None:  # [B|1, 1, S, S]; the causal bound is in s already
+            if Sq != Sk:
+                raise ValueError(f"attention: window needs Sq == Sk, got Sq {Sq}, Sk {Sk}")
+            ids = segments.to(s.device) if segments is not None else None
+            see = K.band_mask_ref(Sq, window[0], window[1], False, ids).to(s.device)[:, None]
+        else:
+            see = K.segment_mask_ref(segments.to(s.device))[:, None]  # [B, 1, S, S]
         dead = ~see.any(-1, keepdim=True)  # padding rows: finite scores first, then P = 0
         s = torch.where(dead, torch.zeros_like(s), s.masked_fill(~see, float("-inf")))
         p = torch.where(dead, torch.zeros_like(s), torch.softmax(s, -1))
@@ -203,7 +222,7 @@ def attn_core_fwd(s, name, qv, qs, kv, ks, vv, vs, o, os_, B, Hl, Sq, Sk, kd, vd
             s["keep"] = keep
         _view4(o, os_, B, Hl, Sq, vd).copy_(
             _attn_ref(q4, k4, v4, scale, causal, kl, keep, 256.0 / (256 - drop[0]) if drop else 1.0, bias,
-                      seg[0] if seg is not None else None))
+                      seg[0] if seg is not None else None, seg.window if seg is not None else None))
 
 
 def attn_core_bwd(s, qv, qs, kv, ks, vv, vs, o, os_, do, dos, dq, dk, dv, B, Hl, Sq, Sk, kd, vd, scale, causal, kl, drop,
@@ -241,7 +260,8 @@ def attn_core_bwd(s, qv, qs, kv, ks, vv, vs, o, os_, do, dos, dq, dk, dv, B, Hl,
         v4 = _view4(vv, vs, B, Hkv, Sk, vd).detach().float().requires_grad_()
         with torch.enable_grad():
             out = _attn_ref(q4, _repeat_kv(k4, Hl // Hkv), _repeat_kv(v4, Hl // Hkv), scale, causal, kl, s.get("keep"),
-                            256.0 / (256 - drop[0]) if drop else 1.0, bias, seg[0] if seg is not None else None)
+                            256.0 / (256 - drop[0]) if drop else 1.0, bias, seg[0] if seg is not None else None,
+                            seg.window if seg is not None else None)
         g4 = _view4(do, dos, B, Hl, Sq, vd).float()
         gq, gk, gv = torch.autograd.grad(out, (q4, k4, v4), g4)
         _view4(dq, qs, B, Hl, Sq, kd).copy_(gq)
@@ -290,6 +310,46 @@ def check_segment_ids_dims(what, in_dims, nb, B, Sq, Sk):
                          f"got Sq {Sq}, Sk {Sk}")
     if tuple(in_dims[3]) != (B, Sq):
         raise ValueError(f"{what}: segment_ids must have shape [{B}, {Sq}], got {list(in_dims[3])}")
+
+
+def window_attrs(attrs):
+    """(left, right) of a layer built with a sliding window (-1: that side unbounded), or None."""
+    if "window_left" not in attrs and "window_right" not in attrs:
+        return None
+    return int(attrs.get("window_left", -1)), int(attrs.get("window_right", -1))
+
+
+def check_window_dims(what, attrs, has_kl, nb, Sq, Sk):
+    """infer-time checks of an attention layer built with window_left / window_right: the rule of
+    segment_ids (Sq == Sk, neither key lengths nor a score bias), and sizes >= 0 or -1."""
+    left, right = window_attrs(attrs)
+    if min(left, right) < -1 or max(left, right) < 0:
+        raise ValueError(f"{what}: window sizes must be >= 0 (-1: unbounded) with one side bounded, got {(left, right)}")
+    if has_kl:
+        raise ValueError(f"{what}: window cannot be combined with key_lengths (mark padding with a negative segment id)")
+    if nb:
+        raise ValueError(f"{what}: window cannot be combined with attn_bias")
+    if Sq != Sk:
+        raise ValueError(f"{what}: window needs Sq == Sk (positions are row indices), got Sq {Sq}, Sk {Sk}")
+
+
+def window_pairs(S, window, causal):
+    """The (query, key) pairs a window leaves in an S x S score matrix: per row min(i, left) +
+    min(S - 1 - i, right) + 1 keys, nothing to the right with causal."""
+    def side(w):  # sum over i of min(i, w): 0 + 1 + .. + w, then w for each of the S - 1 - w rows behind
+        w = S - 1 if w < 0 else min(w, S - 1)
+        return w * (w + 1) // 2 + (S - 1 - w) * w
+
+    left, right = window
+    return S + side(left) + (0 if causal else side(right))
+
+
+def setup_window(attrs, B, S, device):
+    """The bound arrays of a window without segment ids are a constant of the layer: built here, when
+    the executor sets the layer up, outside any captured region (kernels.attn_band_bounds_const)."""
+    win = window_attrs(attrs)
+    if win is not None and not attrs.get("segment_ids") and K.native_device(device):
+        K.attn_band_bounds_const(B, S, win[0], win[1], device)
 
 
 def rope_attrs(attrs):
@@ -346,6 +406,9 @@ class MultiHeadAttention(OpImpl):
             kl = tuple(in_dims[3])
             if kl not in ((q[0],), (q[0], 1)):
                 raise ValueError(f"key_lengths must have shape [{q[0]}] or [{q[0]}, 1], got {list(kl)}")
+        if window_attrs(attrs) is not None:
+            check_window_dims("multihead_attention", attrs, not attrs.get("segment_ids") and len(in_dims) - nb == 4,
+                              nb, q[1], k[1])
         if nb:
             from ..type import DataType
             check_attn_bias_dims("multihead_attention", in_dims[-1], q[0], attrs["num_heads"], q[1], k[1])
@@ -420,10 +483,12 @@ class MultiHeadAttention(OpImpl):
             (1 if self.attrs.get("rope_positions") else 0) > 3
 
     def setup_device(self, device):
-        """Called once by the executor, outside any captured region: uploads the rotary table."""
+        """Called once by the executor, outside any captured region: uploads the rotary table and builds
+        a sliding window's bound arrays."""
         rope = rope_attrs(self.attrs)
         if rope is not None:
             rope_table_of(rope, device)
+        setup_window(self.attrs, *self.layer.inputs[0].dims[:2], device)
 
     def _rope(self, pos, inverse, qb, kb, B, Hl, Hkv, Sq, Sk, kd, qs, ks):
         """One launch that rotates the Q and K head rows in place (inverse: dq / dk back)."""
@@ -478,7 +543,8 @@ class MultiHeadAttention(OpImpl):
         pos = xs[len(xs) - has_bias - 1] if has_pos else None
         if pos is not None and (pos.dtype != torch.int32 or pos.device != q_in.device or not pos.is_contiguous()):
             pos = pos.to(device=q_in.device, dtype=torch.int32).contiguous()
-        seg = K.attn_segments(xs[3], B, Sq, q_in.device) if has_seg else None
+        win = window_attrs(self.attrs)
+        seg = K.attn_segments(xs[3] if has_seg else None, B, Sq, q_in.device, window=win) if has_seg or win else None
         Sk = k_in.shape[1]
         kd, vd = self.attrs["kdim"], self.attrs["vdim"]
         Hl = W["o_weight"].shape[1]
@@ -625,6 +691,9 @@ class MultiHeadAttention(OpImpl):
         Hkv = Hl * (self.attrs.get("num_kv_heads") or H) // H  # this part's KV heads: the smaller K / V projections
         proj = 2.0 * B * (Sq * Hl * kd * Eq + Sk * Hkv * kd * Eq + Sk * Hkv * vd * Eq + Sq * Hl * vd * E)
         att = 2.0 * B * Hl * Sq * Sk * (kd + vd)
+        win = window_attrs(self.attrs)
+        if win is not None:  # the band's pairs only (the flash kernels skip the tiles outside it)
+            att = 2.0 * B * Hl * window_pairs(Sq, win, bool(self.attrs.get("causal"))) * (kd + vd)
         return proj + att
 
     def uses_mfma(self):

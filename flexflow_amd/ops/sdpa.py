@@ -28,7 +28,8 @@ import torch
 from .. import kernels as K
 from ..type import DataType, OperatorType
 from .attention import (attn_bias_map, attn_core_bwd, attn_core_fwd, attn_drop_args, attn_keep_ref,
-                        check_attn_bias_dims, check_segment_ids_dims)
+                        check_attn_bias_dims, check_segment_ids_dims, check_window_dims, setup_window, window_attrs,
+                        window_pairs)
 from .base import OpImpl, register
 
 
@@ -59,6 +60,8 @@ class ScaledDotProductAttention(OpImpl):
         B, H, Sq, _ = q
         if ns:
             check_segment_ids_dims("scaled_dot_product_attention", in_dims, nb, B, Sq, k[2])
+        if window_attrs(attrs) is not None:
+            check_window_dims("scaled_dot_product_attention", attrs, nk, nb, Sq, k[2])
         if nk:
             kl = tuple(in_dims[3])
             if kl not in ((B,), (B, 1)):
@@ -92,6 +95,11 @@ class ScaledDotProductAttention(OpImpl):
     def needs_input_grad(self, i):
         return i < 3
 
+    def setup_device(self, device):
+        """Called once by the executor, outside any captured region: a sliding window's bound arrays."""
+        q = self.layer.inputs[0].dims
+        setup_window(self.attrs, q[0], q[2], device)
+
     def drops_attention(self) -> bool:
         return K.attn_dropout_thr(self.attrs.get("dropout", 0.0)) > 0
 
@@ -102,7 +110,8 @@ class ScaledDotProductAttention(OpImpl):
         has_kl, has_bias = bool(self.attrs.get("key_lengths")), bool(self.attrs.get("attn_bias"))
         kl = K.attn_key_lens(xs[3], B, q.device) if has_kl else None
         bias = K.attn_score_bias(xs[-1], B, Hl, Sq, Sk, q.device) if has_bias else None
-        seg = K.attn_segments(xs[3], B, Sq, q.device) if self.attrs.get("segment_ids") else None
+        has_seg, win = bool(self.attrs.get("segment_ids")), window_attrs(self.attrs)
+        seg = K.attn_segments(xs[3] if has_seg else None, B, Sq, q.device, window=win) if has_seg or win else None
         sc = self.attrs.get("scale")
         scale = 1.0 / math.sqrt(kd) if sc is None else float(sc)
         causal = bool(self.attrs.get("causal", False))
@@ -135,6 +144,9 @@ class ScaledDotProductAttention(OpImpl):
     def flops(self, in_shapes, out_shapes, w_shapes):
         B, H, Sq, D = in_shapes[0]
         Sk, Dv = in_shapes[2][2], in_shapes[2][3]
+        win = window_attrs(self.attrs)
+        if win is not None:  # the band's pairs only
+            return 2.0 * B * H * window_pairs(Sq, win, bool(self.attrs.get("causal"))) * (D + Dv)
         return 2.0 * B * H * Sq * Sk * (D + Dv)
 
     def uses_mfma(self):

@@ -236,6 +236,8 @@ def fabricate_int_input(layer, i: int, shp, cfg: OpConfig, device) -> torch.Tens
         return torch.arange(int(shp[-1]), device=device, dtype=torch.int32).expand(tuple(shp)).contiguous()
     if layer.op_type in (OperatorType.OP_MULTIHEAD_ATTENTION, OperatorType.OP_SDPA) and i == 3 and \
             layer.attrs.get("segment_ids"):  # packed rows: one full-length segment per row
+        # (a sliding window needs nothing here: its bounds do not depend on data, window_left / window_right
+        # are in cost_params_key, and the layer is timed with its real window, inside that one run)
         return torch.zeros(tuple(shp), device=device, dtype=torch.int32)
     if layer.op_type == OperatorType.OP_MULTIHEAD_ATTENTION and i == 3:
         return torch.full(tuple(shp), int(layer.inputs[1].dims[1]), device=device, dtype=torch.int32)
