@@ -441,6 +441,16 @@ class LAMBOptimizer : public Optimizer {
                   "LAMBOptimizer") {}
 };
 
+// AdamW: Adam with decoupled weight decay (torch.optim.AdamW); exclude_1d leaves biases and
+// LayerNorm vectors out of the decay
+class AdamWOptimizer : public Optimizer {
+ public:
+  explicit AdamWOptimizer(const FFModel& m, double lr = 0.001, double beta1 = 0.9, double beta2 = 0.999,
+                          double weight_decay = 0.01, double epsilon = 1e-8, bool exclude_1d = true)
+      : Optimizer(flexflow_adamw_optimizer_create(m.raw(), lr, beta1, beta2, weight_decay, epsilon, exclude_1d),
+                  "AdamWOptimizer") {}
+};
+
 // wall-clock microseconds (reference Realm::Clock::current_time_in_microseconds)
 inline double current_time_in_microseconds() {
   using namespace std::chrono;

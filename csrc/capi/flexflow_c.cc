@@ -521,6 +521,9 @@ void flexflow_model_set_adam_optimizer(flexflow_model_t h, flexflow_adam_optimiz
 void flexflow_model_set_lamb_optimizer(flexflow_model_t h, flexflow_lamb_optimizer_t o) {
   FF_VOID("model_set_opt", "(OO)", obj(h.impl), obj(o.impl));
 }
+void flexflow_model_set_adamw_optimizer(flexflow_model_t h, flexflow_adamw_optimizer_t o) {
+  FF_VOID("model_set_opt", "(OO)", obj(h.impl), obj(o.impl));
+}
 void flexflow_model_set_optimizer(flexflow_model_t h, flexflow_optimizer_t o) {
   FF_VOID("model_set_opt", "(OO)", obj(h.impl), obj(o.impl));
 }
@@ -694,6 +697,15 @@ flexflow_lamb_optimizer_t flexflow_lamb_optimizer_create(flexflow_model_t m, dou
 }
 void flexflow_lamb_optimizer_destroy(flexflow_lamb_optimizer_t h) { drop(h.impl); }
 void flexflow_lamb_optimizer_set_lr(flexflow_lamb_optimizer_t h, double lr) {
+  FF_VOID("optimizer_set_lr", "(Od)", obj(h.impl), lr);
+}
+flexflow_adamw_optimizer_t flexflow_adamw_optimizer_create(flexflow_model_t m, double lr, double b1, double b2,
+                                                           double wd, double eps, bool exclude_1d) {
+  FF_HANDLE(flexflow_adamw_optimizer_t, "adamw_create", "(Odddddi)", obj(m.impl), lr, b1, b2, wd, eps,
+            (int)exclude_1d);
+}
+void flexflow_adamw_optimizer_destroy(flexflow_adamw_optimizer_t h) { drop(h.impl); }
+void flexflow_adamw_optimizer_set_lr(flexflow_adamw_optimizer_t h, double lr) {
   FF_VOID("optimizer_set_lr", "(Od)", obj(h.impl), lr);
 }
 

@@ -38,6 +38,7 @@ FF_AMD_HANDLE(flexflow_parallel_tensor_t);
 FF_AMD_HANDLE(flexflow_sgd_optimizer_t);
 FF_AMD_HANDLE(flexflow_adam_optimizer_t);
 FF_AMD_HANDLE(flexflow_lamb_optimizer_t);
+FF_AMD_HANDLE(flexflow_adamw_optimizer_t);
 FF_AMD_HANDLE(flexflow_initializer_t);
 FF_AMD_HANDLE(flexflow_glorot_uniform_initializer_t);
 FF_AMD_HANDLE(flexflow_zero_initializer_t);
@@ -171,6 +172,7 @@ flexflow_tensor_t flexflow_model_add_multihead_attention(flexflow_model_t handle
 void flexflow_model_set_sgd_optimizer(flexflow_model_t handle, flexflow_sgd_optimizer_t optimizer);
 void flexflow_model_set_adam_optimizer(flexflow_model_t handle, flexflow_adam_optimizer_t optimizer);
 void flexflow_model_set_lamb_optimizer(flexflow_model_t handle, flexflow_lamb_optimizer_t optimizer);
+void flexflow_model_set_adamw_optimizer(flexflow_model_t handle, flexflow_adamw_optimizer_t optimizer);
 void flexflow_model_print_layers(flexflow_model_t handle, int id);
 flexflow_op_t flexflow_model_get_layer_by_id(flexflow_model_t handle, int layer_id);
 flexflow_op_t flexflow_model_get_last_layer(flexflow_model_t handle);
@@ -232,6 +234,13 @@ flexflow_lamb_optimizer_t flexflow_lamb_optimizer_create(flexflow_model_t model,
                                                          bool exclude_1d);
 void flexflow_lamb_optimizer_destroy(flexflow_lamb_optimizer_t handle);
 void flexflow_lamb_optimizer_set_lr(flexflow_lamb_optimizer_t handle, double lr);
+/* AdamW: Adam with decoupled weight decay (torch.optim.AdamW); exclude_1d leaves biases and
+   LayerNorm vectors out of the decay */
+flexflow_adamw_optimizer_t flexflow_adamw_optimizer_create(flexflow_model_t model, double lr, double beta1,
+                                                           double beta2, double weight_decay, double epsilon,
+                                                           bool exclude_1d);
+void flexflow_adamw_optimizer_destroy(flexflow_adamw_optimizer_t handle);
+void flexflow_adamw_optimizer_set_lr(flexflow_adamw_optimizer_t handle, double lr);
 
 /* ------------------------------------------------------------------ initializers */
 flexflow_initializer_t flexflow_initializer_create_null(void);

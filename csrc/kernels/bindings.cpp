@@ -559,6 +559,28 @@ void lamb_apply(Tensor master, Tensor m, Tensor v, optional<Tensor> lowp, Tensor
                   a.n_chunks, wtab.data_ptr(), a.n_weights, hyper.data_ptr<float>(), (float)eps,
                   norms.data_ptr<float>(), cur_stream());
 }
+void adamw_update(Tensor master, Tensor grad, Tensor m, Tensor v, optional<Tensor> lowp, Tensor chunks, Tensor wtab,
+                  int64_t c0, int64_t c1, Tensor hyper, optional<Tensor> gscale_dev, double b1, double b2, double eps,
+                  int64_t max_blocks) {
+  const char* fn = "adamw_update";
+  const LambArgs a = lamb_check(fn, master, chunks, wtab, hyper);
+  TORCH_CHECK(hyper.numel() == 3, fn, ": hyper must hold 3 fp32");
+  TORCH_CHECK(0 <= c0 && c0 <= c1 && c1 <= a.n_chunks, fn, ": chunks [", c0, ", ", c1, ") outside the table's ",
+              a.n_chunks);
+  const int64_t n = master.numel();
+  lamb_f32(fn, master, master, n, true); lamb_f32(fn, grad, master, n, true);
+  lamb_f32(fn, m, master, n, true); lamb_f32(fn, v, master, n, true);
+  if (lowp.has_value() && lowp->defined()) {
+    TORCH_CHECK(lowp->scalar_type() == at::kBFloat16 && lowp->numel() >= n && lowp->is_cuda() &&
+                lowp->device() == master.device(), fn, ": lowp must be bf16, at least as long as master");
+    check_contig(*lowp, "adamw_update: lowp");
+    check_aligned(*lowp, 8, "adamw_update: lowp");
+  }
+  const float* gsd = dev_scalar(gscale_dev, master, "adamw_update: gscale_dev");
+  ffk::adamw_update(master.data_ptr<float>(), grad.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
+                    ptr(lowp), n, chunks.data_ptr(), (int)c0, (int)c1, wtab.data_ptr(), a.n_weights,
+                    hyper.data_ptr<float>(), gsd, b1, b2, (float)eps, cur_stream(), (int)max_blocks);
+}
 void embedding_fwd(Tensor idx, Tensor table, Tensor out, int64_t n_rows, int64_t bag, int64_t dim, bool avg) {
   TORCH_CHECK(idx.numel() == n_rows * bag && out.numel() == n_rows * dim && table.size(-1) == dim);
   check_contig(idx, "embedding_fwd: idx"); check_contig(table, "embedding_fwd: table");
@@ -1433,6 +1455,9 @@ PYBIND11_MODULE(_C, m) {
         py::arg("norms"));
   m.def("lamb_apply", &lamb_apply, py::arg("master"), py::arg("m"), py::arg("v"), py::arg("lowp"), py::arg("chunks"),
         py::arg("wtab"), py::arg("hyper"), py::arg("eps"), py::arg("norms"));
+  m.def("adamw_update", &adamw_update, py::arg("master"), py::arg("grad"), py::arg("m"), py::arg("v"), py::arg("lowp"),
+        py::arg("chunks"), py::arg("wtab"), py::arg("c0"), py::arg("c1"), py::arg("hyper"), py::arg("gscale_dev"),
+        py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("max_blocks") = 0);
   m.def("embedding_fwd", &embedding_fwd);
   m.def("embedding_bwd", &embedding_bwd);
   m.def("init_uniform", &init_uniform);

@@ -204,6 +204,11 @@ void lamb_norms(const float* partial, int n_chunks, const void* wtab, int n_weig
 void lamb_apply(float* master, const float* m, const float* v, void* param_lowp, int64_t n, const void* chunks,
                 int n_chunks, const void* wtab, int n_weights, const float* hyper, float eps, const float* norms,
                 hipStream_t st);
+// AdamW (decoupled, per-weight decay) in one pass over the chunks [c0, c1) of a LAMB chunk table:
+// m, v, w and the bf16 copy written, grad only read; max_blocks > 0 caps the grid
+void adamw_update(float* master, const float* grad, float* m, float* v, void* param_lowp, int64_t n,
+                  const void* chunks, int c0, int c1, const void* wtab, int n_weights, const float* hyper,
+                  const float* gscale_dev, double beta1, double beta2, float eps, hipStream_t st, int max_blocks = 0);
 
 // embedding.hip
 void embedding_fwd(int dt, int idx64, const void* idx, const void* table, void* out, int64_t n_out_rows, int bag,

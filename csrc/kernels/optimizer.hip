@@ -426,6 +426,78 @@ lamb_apply_kernel(float* __restrict__ w, const float* __restrict__ m, const floa
   }
 }
 
+// ------------------------------------------------------------------------------------------- AdamW
+// (Loshchilov & Hutter, "Decoupled Weight Decay Regularization", ICLR 2019.) LAMB with a trust ratio
+// of 1, in one pass: the moments as lamb_moments forms them, u by the same lamb_u, w -= lr u and
+// the bf16 copy, over the chunks [c0, c1) of a LAMB chunk table. lambda is per weight (the table's
+// row), so biases and norm gains can go undecayed; the padding between entries is in no chunk.
+// No reduction, no LDS, no atomics: the same input gives the same bits. One workgroup per chunk
+// (at most kLambChunk elements, 8 float4 groups per thread): the short-lived workgroups the
+// overlapped update wants (opt_grid, max_blocks < 0); a capped grid strides over the chunks.
+__global__ void __launch_bounds__(256)
+adamw_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+             bf16_t* __restrict__ wl, int64_t n, const LambChunk* __restrict__ chunks, int c0, int c1,
+             const LambWeight* __restrict__ wtab, int n_weights, const float* __restrict__ hyper,
+             const float* __restrict__ gscale_dev, float b1, float c1m, float b2, float c2m, float eps) {
+  const float gs = gscale_dev ? *gscale_dev : 1.f;
+  const float lr = hyper[0], rc1 = hyper[1], rc2 = hyper[2];
+  for (int ci = c0 + (int)blockIdx.x; ci < c1; ci += (int)gridDim.x) {
+    const LambChunk c = chunks[ci];
+    if (!lamb_chunk_ok(c, n, n_weights)) continue;  // uniform over the workgroup
+    const float lambda = wtab[c.weight].lambda;
+    const int nv = c.len >> 2;
+    float4* wv4 = reinterpret_cast<float4*>(w + c.start);
+    const float4* gv4 = reinterpret_cast<const float4*>(g + c.start);
+    float4* mv4 = reinterpret_cast<float4*>(m + c.start);
+    float4* vv4 = reinterpret_cast<float4*>(v + c.start);
+#pragma unroll 2
+    for (int i = threadIdx.x; i < nv; i += 256) {
+      float4 wv = wv4[i];
+      const float4 gv = gv4[i];
+      float4 mv = mv4[i];
+      float4 vv = vv4[i];
+      float* wp = &wv.x; const float* gp = &gv.x; float* mp = &mv.x; float* vp = &vv.x;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float gt = gp[j] * gs;
+        mp[j] = fmaf(b1, mp[j], c1m * gt);
+        vp[j] = fmaf(b2, vp[j], c2m * gt * gt);
+        wp[j] -= lr * lamb_u(mp[j], vp[j], wp[j], rc1, rc2, eps, lambda);
+      }
+      wv4[i] = wv;
+      mv4[i] = mv;
+      vv4[i] = vv;
+      if (wl) {
+        ushort4 o;
+        o.x = f2bf(wp[0]); o.y = f2bf(wp[1]); o.z = f2bf(wp[2]); o.w = f2bf(wp[3]);
+        reinterpret_cast<ushort4*>(wl + c.start)[i] = o;
+      }
+    }
+    const int64_t t = c.start + (nv << 2) + threadIdx.x;  // the chunk's len % 4 tail elements
+    if ((int)threadIdx.x < (c.len & 3)) {
+      const float gt = g[t] * gs;
+      const float mt = fmaf(b1, m[t], c1m * gt);
+      const float vt = fmaf(b2, v[t], c2m * gt * gt);
+      const float wt = w[t] - lr * lamb_u(mt, vt, w[t], rc1, rc2, eps, lambda);
+      m[t] = mt;
+      v[t] = vt;
+      w[t] = wt;
+      if (wl) wl[t] = f2bf(wt);
+    }
+  }
+}
+
+void adamw_update(float* master, const float* grad, float* m, float* v, void* param_lowp, int64_t n,
+                  const void* chunks, int c0, int c1, const void* wtab, int n_weights, const float* hyper,
+                  const float* gscale_dev, double beta1, double beta2, float eps, hipStream_t st, int max_blocks) {
+  if (c1 <= c0) return;
+  const int grid = max_blocks > 0 ? std::min(c1 - c0, max_blocks) : c1 - c0;
+  // 1 - beta rounded once from double, as lamb_moments
+  hipLaunchKernelGGL(adamw_kernel, dim3(grid), dim3(256), 0, st, master, grad, m, v, (bf16_t*)param_lowp, n,
+                     (const LambChunk*)chunks, c0, c1, (const LambWeight*)wtab, n_weights, hyper, gscale_dev,
+                     (float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), eps);
+}
+
 void lamb_moments(const float* master, const float* grad, float* m, float* v, int64_t n, const void* chunks,
                   int n_chunks, const void* wtab, int n_weights, const float* hyper, const float* gscale_dev,
                   double beta1, double beta2, float eps, float* partial, hipStream_t st) {

@@ -6,7 +6,8 @@ into a graph). Synthetic data. By default the labels of pad positions still coun
 loss_reduction="valid"`, so the pad rows leave loss, gradients and accuracy and the loss is the
 mean over the real tokens. `--clip-grad-norm C` is FFConfig's flag: it goes through to the
 optimizer, which then clips the global gradient norm to C on the device. `--optimizer lamb` trains
-with LAMB (decoupled weight decay, one trust ratio per weight) in place of Adam.
+with LAMB (decoupled weight decay, one trust ratio per weight) in place of Adam, `--optimizer adamw`
+with AdamW (the same decay, no trust ratio, one pass).
 
 `--pack` trains the same corpus packed (flexflow_amd/utils/packing.py): the sentences are put back to
 back into rows of `--seq-length` tokens, first-fit-decreasing; the loader feeds per-token
@@ -30,6 +31,7 @@ import numpy as np
 from flexflow_amd.core import *  # noqa: F401,F403
 from flexflow_amd.models.bert import BertConfig, build_bert
 
+OPTIMIZERS = {"adam": AdamOptimizer, "adamw": AdamWOptimizer, "lamb": LAMBOptimizer}  # noqa: F405
 
 def top_level_task(argv=None):
     ap = argparse.ArgumentParser(add_help=False)
@@ -37,7 +39,7 @@ def top_level_task(argv=None):
     ap.add_argument("--iterations", type=int, default=20)
     ap.add_argument("--min-length", type=int, default=8)
     ap.add_argument("--ignore-pad-labels", action="store_true")
-    ap.add_argument("--optimizer", choices=["adam", "lamb"], default="adam")
+    ap.add_argument("--optimizer", choices=sorted(OPTIMIZERS), default="adam")
     ap.add_argument("--pack", action="store_true")
     args, rest = ap.parse_known_args(sys.argv[1:] if argv is None else argv)
     ffconfig = FFConfig(rest)
@@ -48,7 +50,7 @@ def top_level_task(argv=None):
         return run_packed(args, ffconfig, ffmodel, bc)
     lengths = ffmodel.create_tensor([b], DataType.DT_INT32, name="key_lengths")
     ids, pos, _ = build_bert(ffmodel, b, bc, key_lengths=lengths)
-    ffmodel.optimizer = LAMBOptimizer(ffmodel, 1e-3) if args.optimizer == "lamb" else AdamOptimizer(ffmodel, 1e-3)
+    ffmodel.optimizer = OPTIMIZERS[args.optimizer](ffmodel, 1e-3)
     masking = dict(ignore_index=-100, loss_reduction="valid") if args.ignore_pad_labels else {}
     ffmodel.compile(loss_type=LossType.LOSS_SPARSE_CATEGORICAL_CROSSENTROPY, metrics=[MetricsType.METRICS_ACCURACY],
                     **masking)
@@ -93,7 +95,7 @@ def run_packed(args, ffconfig, ffmodel, bc):
     b, s = ffconfig.batch_size, args.seq_length
     seg = ffmodel.create_tensor([b, s], DataType.DT_INT32, name="segment_ids")
     ids, pos, _ = build_bert(ffmodel, b, bc, segment_ids=seg)
-    ffmodel.optimizer = LAMBOptimizer(ffmodel, 1e-3) if args.optimizer == "lamb" else AdamOptimizer(ffmodel, 1e-3)
+    ffmodel.optimizer = OPTIMIZERS[args.optimizer](ffmodel, 1e-3)
     ffmodel.compile(loss_type=LossType.LOSS_SPARSE_CATEGORICAL_CROSSENTROPY, metrics=[MetricsType.METRICS_ACCURACY],
                     ignore_index=-100, loss_reduction="valid")
     rng = np.random.default_rng(0)

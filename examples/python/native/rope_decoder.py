@@ -14,7 +14,11 @@ sentence) and `position_ids` that restart at every sentence, which the rotation 
 `--window W` is sliding-window attention (`DecoderConfig.sliding_window`): every query sees the last W keys,
 itself included (`window=(W - 1, 0)`), with `--packed` and without.
 
+`--optimizer adamw --weight-decay X` trains with AdamW (decoupled weight decay X on the matrices and the
+embedding table, none on the RMSNorm gains), as the recipes of these models do; the default stays Adam.
+
     python examples/python/native/rope_decoder.py -b 8 --iterations 20
+    python examples/python/native/rope_decoder.py --small --iterations 8 --optimizer adamw --weight-decay 0.1
     python examples/python/native/rope_decoder.py --small --packed --window 8 --iterations 8
     python examples/python/native/rope_decoder.py --small --iterations 8            # CPU-sized
     python examples/python/native/rope_decoder.py --small --packed --iterations 8
@@ -41,6 +45,8 @@ def top_level_task(argv=None):
     ap.add_argument("--mlp", choices=("gelu", "swiglu", "geglu"), default="gelu")
     ap.add_argument("--fused-gate-up", action="store_true")
     ap.add_argument("--window", type=int, default=0)
+    ap.add_argument("--optimizer", choices=("adam", "adamw"), default="adam")
+    ap.add_argument("--weight-decay", type=float, default=0.01)
     args, rest = ap.parse_known_args(sys.argv[1:] if argv is None else argv)
     ffconfig, ffmodel, small, iterations = zoo.setup(rest)
     b = ffconfig.batch_size
@@ -54,7 +60,9 @@ def top_level_task(argv=None):
         seg = ffmodel.create_tensor([b, s], DataType.DT_INT32, name="segment_ids")
         pos = ffmodel.create_tensor([b, s], DataType.DT_INT32, name="rope_position_ids")
     ids, out = build_rope_decoder(ffmodel, b, dc, segment_ids=seg, position_ids=pos)
-    ffmodel.optimizer = AdamOptimizer(ffmodel, 3e-3 if small else 1e-3)
+    lr = 3e-3 if small else 1e-3
+    ffmodel.optimizer = AdamWOptimizer(ffmodel, lr, weight_decay=args.weight_decay) if args.optimizer == "adamw" \
+        else AdamOptimizer(ffmodel, lr)
     ffmodel.compile(loss_type=zoo.SCCE, metrics=[MetricsType.METRICS_ACCURACY], ignore_index=-100, loss_reduction="valid")
     rng = np.random.default_rng(0)
     if args.packed:

@@ -12,7 +12,7 @@ import ctypes
 import numpy as np
 
 from .config import FFConfig
-from .core import AdamOptimizer, FFModel, LAMBOptimizer, SGDOptimizer
+from .core import AdamOptimizer, AdamWOptimizer, FFModel, LAMBOptimizer, SGDOptimizer
 from .type import ActiMode, AggrMode, CompMode, DataType, LossType, MetricsType, PoolType
 
 
@@ -60,6 +60,10 @@ def adam_create(m, alpha, b1, b2, wd, eps):
 
 def lamb_create(m, lr, b1, b2, wd, eps, bias_correction=True, exclude_1d=True):
     return LAMBOptimizer(m, lr, b1, b2, wd, eps, bool(bias_correction), bool(exclude_1d))
+
+
+def adamw_create(m, lr, b1, b2, wd, eps, exclude_1d=True):
+    return AdamWOptimizer(m, lr, b1, b2, wd, eps, bool(exclude_1d))
 
 
 def model_set_optimizer(m, opt):

@@ -13,7 +13,7 @@ for _c in OP_CLASSES.values():  # reference per-op layer classes: Linear, Conv2D
 Batch_Norm = _op_class(OperatorType.OP_BATCHNORM)
 from .model import FFModel, PerfMetrics  # noqa: F401
 from .netconfig import DLRMConfig, NetConfig  # noqa: F401
-from .optimizers import AdamOptimizer, LAMBOptimizer, Optimizer, SGDOptimizer  # noqa: F401
+from .optimizers import AdamOptimizer, AdamWOptimizer, LAMBOptimizer, Optimizer, SGDOptimizer  # noqa: F401
 from .tensor import Parameter, RegionNdarray, Tensor  # noqa: F401
 
 Op = Layer

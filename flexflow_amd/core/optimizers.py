@@ -3,7 +3,9 @@ optimizer_kernel.cu).
 
 The reference launches one update task per weight (with a NCCL all-reduce inside each). Here
 every weight shard of a replica group lives in one flat fp32 arena, so an update is ONE fused HIP
-kernel per arena (multi-tensor apply) that also refreshes the bf16 compute copy.
+kernel per arena (multi-tensor apply) that also refreshes the bf16 compute copy. AdamW and LAMB
+(not in the reference) decay each weight by its own lambda: their kernels walk a chunk table of the
+arena (kernels.lamb_table), AdamW in one pass per update range, LAMB in two with the norms between.
 """
 from __future__ import annotations
 
@@ -125,6 +127,135 @@ class AdamOptimizer(Optimizer):
                       gscale_dev=self._gscale_dev())
 
 
+def _check_hyper(cls, **kw):
+    """ValueError naming the first hyper-parameter that is not a finite number in its range."""
+    rules = {"lr": lambda x: x >= 0, "beta1": lambda x: 0 <= x < 1, "beta2": lambda x: 0 <= x < 1,
+             "weight_decay": lambda x: x >= 0, "epsilon": lambda x: x > 0}
+    for name, val in kw.items():
+        try:
+            good = not isinstance(val, (bool, str)) and math.isfinite(float(val)) and rules[name](float(val))
+        except (TypeError, ValueError):
+            good = False
+        if not good:
+            raise ValueError(f"{cls}: invalid {name}={val!r}")
+
+
+class AdamWOptimizer(Optimizer):
+    """AdamW (Loshchilov & Hutter, "Decoupled Weight Decay Regularization", ICLR 2019), which is
+    torch.optim.AdamW with amsgrad=False: Adam moments of the (clipped) gradient alone, bias
+    correction inside epsilon, and the decay lambda_p * w added to the update, not to the gradient.
+    With exclude_1d, weights of one dimension or fewer (biases, LayerNorm / RMSNorm vectors) get
+    lambda_p = 0, the rule LAMBOptimizer uses; exclude_1d=False decays everything, as torch does
+    over one parameter group.
+
+    One HIP pass per update range (kernels.adamw_update) over a chunk table of the arena
+    (kernels.lamb_table) that the executor hands over at init_optimizer (set_table): a range
+    [lo, hi) is a run of consecutive chunks, found on the host and cached. The hyper-parameters live
+    on the device ([lr, 1 / (1 - beta1^t), 1 / (1 - beta2^t)], refreshed by next()), so a captured
+    whole-step hipGraph replays the same launches. State is (m, v) per arena, as Adam's."""
+
+    def __init__(self, ffmodel=None, lr=1e-3, beta1=0.9, beta2=0.999, weight_decay=0.01, epsilon=1e-8,
+                 exclude_1d=True, clip_norm=None):
+        _check_hyper("AdamWOptimizer", lr=lr, beta1=beta1, beta2=beta2, weight_decay=weight_decay, epsilon=epsilon)
+        super().__init__(ffmodel, float(lr), clip_norm)
+        self.beta1, self.beta2 = float(beta1), float(beta2)
+        self.weight_decay = float(weight_decay)
+        self.epsilon = float(epsilon)
+        self.exclude_1d = bool(exclude_1d)
+        self.beta1_t = 1.0
+        self.beta2_t = 1.0
+        self.hyper_dev = None  # fp32 [3] on the arenas' device: lr, 1 / (1 - beta1^t), 1 / (1 - beta2^t)
+        # per arena: [entries, sorted cut points, tables (never freed: captured graphs hold their
+        # pointers), {(lo, hi): (table, c0, c1)}]
+        self._plans = {}
+
+    def _hyper(self):
+        if self.beta1_t == 1.0:  # before the first next(): no correction yet
+            return self.lr, 1.0, 1.0
+        return self.lr, 1.0 / (1.0 - self.beta1_t), 1.0 / (1.0 - self.beta2_t)
+
+    def _refresh(self):
+        if self.hyper_dev is not None:
+            for i, x in enumerate(self._hyper()):
+                self.hyper_dev[i].fill_(x)
+
+    def use_device_alpha(self, device):
+        """AdamW always reads its hyper-parameters from the device (the hook a captured step calls)."""
+        if self.hyper_dev is None:
+            self.hyper_dev = torch.zeros(3, device=device, dtype=torch.float32)
+            self._refresh()
+
+    def set_learning_rate(self, learning_rate):
+        self.lr = float(learning_rate)
+        self._refresh()
+
+    def weight_rule(self, shape):
+        """lambda_p of a weight of this (shard) shape."""
+        return 0.0 if self.exclude_1d and len(shape) <= 1 else self.weight_decay
+
+    def init_state(self, arena):
+        self.state[id(arena)] = (torch.zeros_like(arena.master), torch.zeros_like(arena.master))
+        self.use_device_alpha(arena.master.device)
+
+    def next(self):
+        self.beta1_t *= self.beta1
+        self.beta2_t *= self.beta2
+        self._refresh()
+
+    def set_table(self, arena, entries, cuts):
+        """entries: [(offset, numel, weight, lambda, False)] of the arena (kernels.lamb_table);
+        cuts: every bound (a multiple of 4) of a range step_range will be given. Builds the arena's
+        table; a table built earlier stays alive."""
+        old = self._plans.get(id(arena))
+        self._plans[id(arena)] = [list(entries), sorted(set(int(c) for c in cuts)), old[2] if old else [], {}]
+        self._build(arena)
+
+    def _build(self, arena):
+        entries, cuts, tabs, _ = self._plans[id(arena)]
+        size = arena.master.numel()
+        pts = sorted({0, size, *(c for c in cuts if 0 < c < size)})
+        tab = K.lamb_table(entries, list(zip(pts[:-1], pts[1:])), len(entries), size, arena.master.device)
+        starts = [int(s) for s in tab.chunks_host[:, 0]]
+        ends = [s + ln for s, ln, _ in tab.rows()]
+        tabs.append((tab, starts, ends))
+
+    def _resolve(self, arena, lo, hi):
+        plan = self._plans.get(id(arena))
+        if plan is None:
+            raise RuntimeError("AdamWOptimizer updates through a chunk table of the arena that "
+                               "Executor.init_optimizer() builds (FFModel.compile())")
+        lo, hi = int(lo), int(hi)
+        if not 0 <= lo <= hi <= arena.master.numel():
+            raise RuntimeError(f"AdamWOptimizer.step_range: [{lo}, {hi}) is outside the arena")
+        hit = plan[3].get((lo, hi))
+        if hit is not None:
+            return hit
+        import bisect
+        for _ in range(2):
+            tab, starts, ends = plan[2][-1]
+            c0, c1 = bisect.bisect_left(starts, lo), bisect.bisect_left(starts, hi)
+            # a bound is a cut when no chunk lies across it (the end of an entry is one, whatever its size)
+            across = [b for b, c in ((lo, c0), (hi, c1)) if c > 0 and ends[c - 1] > b]
+            if not across:
+                plan[3][(lo, hi)] = (tab, c0, c1)
+                return plan[3][(lo, hi)]
+            if any(b % 4 for b in across):
+                raise RuntimeError(f"AdamWOptimizer.step_range: [{lo}, {hi}) cuts a weight at an element that is "
+                                   "not a multiple of 4")
+            plan[1] = sorted(set(plan[1]) | set(across))  # a new range: one more table, built once
+            self._build(arena)
+        raise RuntimeError(f"AdamWOptimizer.step_range: no chunk run for [{lo}, {hi})")
+
+    def step(self, arena):
+        self.step_range(arena, 0, arena.master.numel() if arena is not None else 0)
+
+    def step_range(self, arena, lo, hi, max_blocks=0):
+        tab, c0, c1 = self._resolve(arena, lo, hi)
+        m, v = self.state[id(arena)]
+        K.adamw_update(arena.master, arena.grad, m, v, arena.lowp, tab, c0, c1, self.hyper_dev, self._gscale_dev(),
+                       self.beta1, self.beta2, self.epsilon, max_blocks=max_blocks)
+
+
 class LAMBOptimizer(Optimizer):
     """LAMB (You et al., "Large Batch Optimization for Deep Learning", ICLR 2020): Adam moments,
     decoupled weight decay and a trust ratio |w| / |update| per logical weight, taken over the
@@ -140,15 +271,7 @@ class LAMBOptimizer(Optimizer):
 
     def __init__(self, ffmodel=None, lr=1e-3, beta1=0.9, beta2=0.999, weight_decay=0.01, epsilon=1e-6,
                  bias_correction=True, exclude_1d=True, clip_norm=None):
-        for name, val, ok in (("lr", lr, lambda x: x >= 0), ("beta1", beta1, lambda x: 0 <= x < 1),
-                              ("beta2", beta2, lambda x: 0 <= x < 1), ("weight_decay", weight_decay, lambda x: x >= 0),
-                              ("epsilon", epsilon, lambda x: x > 0)):
-            try:
-                good = not isinstance(val, (bool, str)) and math.isfinite(float(val)) and ok(float(val))
-            except (TypeError, ValueError):
-                good = False
-            if not good:
-                raise ValueError(f"LAMBOptimizer: invalid {name}={val!r}")
+        _check_hyper("LAMBOptimizer", lr=lr, beta1=beta1, beta2=beta2, weight_decay=weight_decay, epsilon=epsilon)
         super().__init__(ffmodel, float(lr), clip_norm)
         self.beta1, self.beta2 = float(beta1), float(beta2)
         self.weight_decay = float(weight_decay)

@@ -1,11 +1,11 @@
-"""Keras optimizers (reference keras/optimizers.py) -> fused HIP SGD / Adam / LAMB of flexflow_amd.core.
+"""Keras optimizers (reference keras/optimizers.py) -> fused HIP SGD / Adam / AdamW / LAMB of flexflow_amd.core.
 
 global_clipnorm=C clips the global gradient norm of all trainable weights to C (the core optimizers'
 clip_norm). Keras' clipnorm (per variable) and clipvalue (per element) are not implemented: they
 are accepted and ignored, like every other unknown keyword."""
 from __future__ import annotations
 
-from ..core.optimizers import AdamOptimizer, LAMBOptimizer, SGDOptimizer
+from ..core.optimizers import AdamOptimizer, AdamWOptimizer, LAMBOptimizer, SGDOptimizer
 
 
 class Optimizer:
@@ -63,7 +63,24 @@ class Lamb(Optimizer):
         return self.ffhandle
 
 
+class AdamW(Optimizer):
+    """AdamW (core AdamWOptimizer) with Keras' defaults: decoupled weight_decay=0.004 on every
+    variable; exclude_1d=True leaves biases and LayerNorm vectors out of the decay."""
+
+    def __init__(self, learning_rate=0.001, weight_decay=0.004, beta_1=0.9, beta_2=0.999, epsilon=1e-7,
+                 exclude_1d=False, global_clipnorm=None, **kw):
+        self.learning_rate = float(kw.pop("lr", learning_rate))
+        self.beta_1, self.beta_2, self.epsilon, self.weight_decay = beta_1, beta_2, epsilon, weight_decay
+        self.exclude_1d = exclude_1d
+        self.global_clipnorm = global_clipnorm
+
+    def create_ffhandle(self, ffmodel):
+        self.ffhandle = AdamWOptimizer(ffmodel, self.learning_rate, self.beta_1, self.beta_2, self.weight_decay,
+                                       self.epsilon, self.exclude_1d, clip_norm=self.global_clipnorm)
+        return self.ffhandle
+
+
 def get(spec):
     if isinstance(spec, Optimizer):
         return spec
-    return {"sgd": SGD, "adam": Adam, "lamb": Lamb}[str(spec).lower()]()
+    return {"sgd": SGD, "adam": Adam, "adamw": AdamW, "lamb": Lamb}[str(spec).lower()]()

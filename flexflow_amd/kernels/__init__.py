@@ -2242,6 +2242,48 @@ def lamb_ref(w, g, m, v, entries, t, lr, b1, b2, eps, bias_correction=True, coef
     return w, m, v, norms
 
 
+# AdamW (csrc/kernels/optimizer.hip): LAMB with a trust ratio of 1, in one pass over the chunks
+# [c0, c1) of a lamb_table (built with adapt=False): decoupled decay, lambda per weight
+def adamw_update(master, grad, m, v, lowp, table, c0, c1, hyper, gscale_dev, b1, b2, eps, max_blocks=0):
+    """m, v updated from gscale_dev * grad, then w -= lr * (m rc1 / (sqrt(v rc2) + eps) + lambda w)
+    and the bf16 copy, over the table's chunks [c0, c1) only. hyper: fp32 [3] = (lr, rc1, rc2) on
+    the tensors' device. grad is never written, nor is anything outside those chunks. max_blocks
+    > 0 caps the launch grid (the chunks are then strode over); <= 0: one workgroup per chunk."""
+    c0, c1 = int(c0), int(c1)
+    if native(master):
+        ext().adamw_update(master, grad, m, v, lowp, table.chunks, table.wtab, c0, c1, hyper, gscale_dev, b1, b2,
+                           eps, max(int(max_blocks), 0))
+        return
+    if not 0 <= c0 <= c1 <= table.n_chunks:
+        raise RuntimeError(f"adamw_update: chunks [{c0}, {c1}) outside the table's {table.n_chunks}")
+    gs = gscale_dev[0] if gscale_dev is not None else 1.0
+    lam = torch.from_numpy(table.wtab_host[:, 0].copy()).view(torch.float32)
+    for s, ln, wi in table.rows()[c0:c1]:
+        g = grad[s:s + ln] * gs
+        m[s:s + ln].mul_(b1).add_((1 - b1) * g)
+        v[s:s + ln].mul_(b2).add_((1 - b2) * g * g)
+        w = master[s:s + ln]
+        w.sub_(hyper[0] * _lamb_u(m[s:s + ln], v[s:s + ln], w, hyper[1], hyper[2], eps, lam[wi]))
+        if lowp is not None:
+            lowp[s:s + ln].copy_(w)
+
+
+def adamw_ref(w, g, m, v, entries, t, lr, b1, b2, eps, coef=1.0):
+    """The AdamW step in float64 (torch.optim.AdamW with amsgrad=False, one decay per entry), the
+    oracle of the kernel and of the optimizer. w, g, m, v: flat tensors; entries as in lamb_table
+    (offset, numel, weight, lambda, adapt), adapt ignored. Returns (w, m, v) as new float64
+    tensors; elements in no entry are copied."""
+    w, g, m, v = (x.detach().cpu().double().clone() for x in (w, g, m, v))
+    d1, d2 = 1 - b1 ** t, 1 - b2 ** t
+    for off, n, _, lam, *_ in entries:
+        s = slice(int(off), int(off) + int(n))
+        gp = coef * g[s]
+        m[s] = b1 * m[s] + (1 - b1) * gp
+        v[s] = b2 * v[s] + (1 - b2) * gp * gp
+        w[s] = w[s] - lr * ((m[s] / d1) / ((v[s] / d2).sqrt() + eps) + lam * w[s])
+    return w, m, v
+
+
 # ---------------------------------------------------------------------------- initializers
 def _mix64(z):
     M = (1 << 64) - 1

@@ -770,6 +770,8 @@ class Executor:
         self._opt_next_done = None
         self._bwd_since_update += 1
         if self._overlap_active:
+            if getattr(self.model.optimizer, "set_table", None) is not None:
+                self._adamw_setup(self.model.optimizer)
             self.model.optimizer.next()  # this step's bias-corrected scalars, before any bucket update
             self._opt_next_done = self.model.optimizer
         self._wdone = {}
@@ -1160,6 +1162,8 @@ class Executor:
         self._bwd_since_update = 0
         if getattr(optimizer, "two_phase", False):
             self._lamb_update(optimizer)
+        if getattr(optimizer, "set_table", None) is not None:
+            self._adamw_setup(optimizer)  # a no-op unless weight_decay or exclude_1d changed
         for grp, ar in self.arenas.items():
             if not ar.size:
                 continue
@@ -1249,6 +1253,35 @@ class Executor:
         norms = torch.zeros(max(2 * P, 2), dtype=torch.float32, device=self.device)
         self._lamb_key, self._lamb = key, (tabs, norms)
         return self._lamb
+
+    def _adamw_setup(self, optimizer):
+        """AdamW's chunk tables, built once per optimizer and set of hyper-parameters the tables
+        hold (outside any step or capture): one per non-empty arena, cut at every bound of a range
+        this executor hands to step_range — the gradient buckets, the FF_UPD_CHUNK pieces of the
+        overlapped update inside each bucket, and under ZeRO each bucket's own chunk — so that
+        each such range is a run of whole chunks."""
+        key = (id(optimizer), optimizer.weight_decay, optimizer.exclude_1d, os.environ.get("FF_UPD_CHUNK"))
+        if getattr(self, "_adamw_key", None) == key:
+            return
+        ch = int(os.environ.get("FF_UPD_CHUNK", "4194304")) // 8 * 8  # as _on_bucket_ready
+        for grp, ar in self.arenas.items():
+            if not ar.size:
+                continue
+            entries = [(off, n, i, optimizer.weight_rule(shape), False) for i, (_, off, n, shape) in enumerate(ar.entries)]
+            cuts = set()
+            for _, flat, buckets in self.bucketer.arenas:
+                if flat is not ar.grad:
+                    continue
+                for b in buckets:
+                    # an unsharded bucket ends with its last entry, whose size need not be a
+                    # multiple of 4: the cut goes into the padding behind it
+                    cuts.update((b["lo"], (b["hi"] + 7) // 8 * 8))
+                    if b.get("sharded"):
+                        cuts.update(b["own"])
+                    elif ch > 0:
+                        cuts.update(range(b["lo"], b["hi"], ch))
+            optimizer.set_table(ar, entries, cuts)
+        self._adamw_key = key
 
     def _lamb_update(self, optimizer):
         """The two-pass LAMB update: stage 1 over every arena's ranges, the per-weight norms, one
@@ -1341,6 +1374,8 @@ class Executor:
             self._clip_setup(optimizer)
         if getattr(optimizer, "two_phase", False):
             self._lamb_setup(optimizer)
+        if getattr(optimizer, "set_table", None) is not None:  # AdamW: ranges over a chunk table
+            self._adamw_setup(optimizer)
 
     def _clip_setup(self, optimizer):
         """Gradient clipping's device scalars [sum of squares, norm, coefficient] and grad_sumsq's

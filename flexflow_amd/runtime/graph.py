@@ -95,16 +95,16 @@ class StepGraph:
         included): one process, Adam (its launches read the per-step alpha_t from a device scalar
         that next() refreshes before each replay; with clip_norm the captured update also holds the
         gradient's sum of squares, the coefficient kernel and the Adam launches that read it, all
-        on the device), or LAMB (all of its hyper-parameters, norms and trust ratios stay on the
-        device). Other optimizers and multi-rank steps keep
-        update() eager after the replay. Opt-in (FF_GRAPH_UPDATE=1): same-box A/B AlexNet 1.665-1.671
+        on the device), or LAMB and AdamW (all of their hyper-parameters, norms and trust ratios stay
+        on the device; AdamW's chunk tables were built at init_optimizer). Other optimizers and
+        multi-rank steps keep update() eager after the replay. Opt-in (FF_GRAPH_UPDATE=1): same-box A/B AlexNet 1.665-1.671
         vs 1.670-1.682 ms, ResNet-50 7.58-7.60 vs 7.60 ms (profiles/graph_update_ab_r5.txt) — the
         eager update after the replay was not exposed enough for the overlap to pay."""
         import torch.distributed as dist
-        from ..core.optimizers import AdamOptimizer, LAMBOptimizer
+        from ..core.optimizers import AdamOptimizer, AdamWOptimizer, LAMBOptimizer
         if ex.comm.distributed or getattr(ex.comm, "force", False) or (dist.is_available() and dist.is_initialized()):
             return False  # any process group (a forced world-1 RCCL one included): update() stays eager
-        return type(m.optimizer) in (AdamOptimizer, LAMBOptimizer) and os.environ.get("FF_GRAPH_UPDATE", "0") == "1"
+        return type(m.optimizer) in (AdamOptimizer, AdamWOptimizer, LAMBOptimizer) and os.environ.get("FF_GRAPH_UPDATE", "0") == "1"
 
     def step(self):
         m = self.model
