@@ -9,6 +9,13 @@
 
 namespace ffk {
 
+// four updated floats -> the float4 group i of the bf16 copy, as one 8-byte store
+__device__ __forceinline__ void store_bf16x4(bf16_t* wl, int64_t i, const float* wp) {
+  ushort4 o;
+  o.x = f2bf(wp[0]); o.y = f2bf(wp[1]); o.z = f2bf(wp[2]); o.w = f2bf(wp[3]);
+  reinterpret_cast<ushort4*>(wl)[i] = o;
+}
+
 __global__ void sgd_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ v,
                            bf16_t* __restrict__ wl, int64_t n, float lr, float momentum, int nesterov, float wd,
                            float gscale, const float* __restrict__ gscale_dev) {
@@ -34,11 +41,7 @@ __global__ void sgd_kernel(float* __restrict__ w, const float* __restrict__ g, f
     }
     reinterpret_cast<float4*>(w)[i] = wv;
     if (momentum > 0.f) reinterpret_cast<float4*>(v)[i] = vv;
-    if (wl) {
-      ushort4 o;
-      o.x = f2bf(wp[0]); o.y = f2bf(wp[1]); o.z = f2bf(wp[2]); o.w = f2bf(wp[3]);
-      reinterpret_cast<ushort4*>(wl)[i] = o;
-    }
+    if (wl) store_bf16x4(wl, i, wp);
   }
   for (int64_t i = nv * 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     float gt = g[i] * gscale + wd * w[i];
@@ -79,11 +82,7 @@ __global__ void adam_kernel(float* __restrict__ w, const float* __restrict__ g, 
     reinterpret_cast<float4*>(w)[i] = wv;
     reinterpret_cast<float4*>(m)[i] = mv;
     reinterpret_cast<float4*>(v)[i] = vv;
-    if (wl) {
-      ushort4 o;
-      o.x = f2bf(wp[0]); o.y = f2bf(wp[1]); o.z = f2bf(wp[2]); o.w = f2bf(wp[3]);
-      reinterpret_cast<ushort4*>(wl)[i] = o;
-    }
+    if (wl) store_bf16x4(wl, i, wp);
   }
   for (int64_t i = nv * 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     const float gt = g[i] * gscale + wd * w[i];
@@ -303,6 +302,27 @@ __device__ __forceinline__ bool lamb_chunk_ok(const LambChunk& c, int64_t n, int
          c.weight >= 0 && c.weight < n_weights;
 }
 
+// the Adam moments of one element from its (scaled) gradient; c = 1 - b (one_minus)
+__device__ __forceinline__ void adam_moments(float& m, float& v, float gt, float b1, float c1, float b2, float c2) {
+  m = fmaf(b1, m, c1 * gt);
+  v = fmaf(b2, v, c2 * gt * gt);
+}
+
+// One workgroup of 256 threads over one chunk: body4(i) for each float4 group i of the chunk
+// (counted from c.start, which is 16-byte aligned), between() once in every thread, then tail(t)
+// for each of the chunk's len % 4 last elements (t an index into the arena). The callers' lambdas
+// capture by value where they can: by reference the compiler orders the address arithmetic and
+// the loads differently (same results, other instructions).
+template <class Body4, class Between, class Tail>
+__device__ __forceinline__ void walk_chunk(const LambChunk& c, Body4 body4, Between between, Tail tail) {
+  const int nv = c.len >> 2;
+#pragma unroll 2
+  for (int i = threadIdx.x; i < nv; i += 256) body4(i);
+  between();
+  const int64_t t = c.start + (nv << 2) + threadIdx.x;
+  if ((int)threadIdx.x < (c.len & 3)) tail(t);
+}
+
 __global__ void __launch_bounds__(256)
 lamb_moments_kernel(const float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m,
                     float* __restrict__ v, int64_t n, const LambChunk* __restrict__ chunks,
@@ -318,13 +338,11 @@ lamb_moments_kernel(const float* __restrict__ w, const float* __restrict__ g, fl
     const float gs = gscale_dev ? *gscale_dev : 1.f;
     const float rc1 = hyper[1], rc2 = hyper[2];
     const float lambda = wtab[c.weight].lambda;
-    const int nv = c.len >> 2;
     const float4* wv4 = reinterpret_cast<const float4*>(w + c.start);
     const float4* gv4 = reinterpret_cast<const float4*>(g + c.start);
     float4* mv4 = reinterpret_cast<float4*>(m + c.start);
     float4* vv4 = reinterpret_cast<float4*>(v + c.start);
-#pragma unroll 2
-    for (int i = threadIdx.x; i < nv; i += 256) {
+    walk_chunk(c, [&](int i) {
       const float4 wv = wv4[i];
       const float4 gv = gv4[i];
       float4 mv = mv4[i];
@@ -333,30 +351,26 @@ lamb_moments_kernel(const float* __restrict__ w, const float* __restrict__ g, fl
       float* mp = &mv.x; float* vp = &vv.x; float* awp = &aw.x; float* aup = &au.x;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const float gt = gp[j] * gs;
-        mp[j] = fmaf(b1, mp[j], c1 * gt);
-        vp[j] = fmaf(b2, vp[j], c2 * gt * gt);
+        adam_moments(mp[j], vp[j], gp[j] * gs, b1, c1, b2, c2);
         const float u = lamb_u(mp[j], vp[j], wp[j], rc1, rc2, eps, lambda);
         awp[j] = fmaf(wp[j], wp[j], awp[j]);
         aup[j] = fmaf(u, u, aup[j]);
       }
       mv4[i] = mv;
       vv4[i] = vv;
-    }
-    sw = (aw.x + aw.y) + (aw.z + aw.w);
-    su = (au.x + au.y) + (au.z + au.w);
-    const int64_t t = c.start + (nv << 2) + threadIdx.x;  // the chunk's len % 4 tail elements
-    if ((int)threadIdx.x < (c.len & 3)) {
-      const float gt = g[t] * gs;
-      const float mt = fmaf(b1, m[t], c1 * gt);
-      const float vt = fmaf(b2, v[t], c2 * gt * gt);
+    }, [&] {  // the tail element is added to the sum of the accumulators
+      sw = (aw.x + aw.y) + (aw.z + aw.w);
+      su = (au.x + au.y) + (au.z + au.w);
+    }, [=, &sw, &su](int64_t t) {
+      float mt = m[t], vt = v[t];
+      adam_moments(mt, vt, g[t] * gs, b1, c1, b2, c2);
       const float wt = w[t];
       const float u = lamb_u(mt, vt, wt, rc1, rc2, eps, lambda);
       m[t] = mt;
       v[t] = vt;
       sw = fmaf(wt, wt, sw);
       su = fmaf(u, u, su);
-    }
+    });
   }
   sw = block_sum<256>(sw, red_w);
   su = block_sum<256>(su, red_u);
@@ -399,12 +413,10 @@ lamb_apply_kernel(float* __restrict__ w, const float* __restrict__ m, const floa
   const float rc1 = hyper[1], rc2 = hyper[2];
   const float wn = sqrtf(norms[2 * c.weight]), un = sqrtf(norms[2 * c.weight + 1]);
   const float step = hyper[0] * (((e.flags & 1) && wn > 0.f && un > 0.f) ? wn / un : 1.f);
-  const int nv = c.len >> 2;
   float4* wv4 = reinterpret_cast<float4*>(w + c.start);
   const float4* mv4 = reinterpret_cast<const float4*>(m + c.start);
   const float4* vv4 = reinterpret_cast<const float4*>(v + c.start);
-#pragma unroll 2
-  for (int i = threadIdx.x; i < nv; i += 256) {
+  walk_chunk(c, [=](int i) {
     float4 wv = wv4[i];
     const float4 mv = mv4[i];
     const float4 vv = vv4[i];
@@ -412,18 +424,12 @@ lamb_apply_kernel(float* __restrict__ w, const float* __restrict__ m, const floa
 #pragma unroll
     for (int j = 0; j < 4; ++j) wp[j] -= step * lamb_u(mp[j], vp[j], wp[j], rc1, rc2, eps, e.lambda);
     wv4[i] = wv;
-    if (wl) {
-      ushort4 o;
-      o.x = f2bf(wp[0]); o.y = f2bf(wp[1]); o.z = f2bf(wp[2]); o.w = f2bf(wp[3]);
-      reinterpret_cast<ushort4*>(wl + c.start)[i] = o;
-    }
-  }
-  const int64_t t = c.start + (nv << 2) + threadIdx.x;
-  if ((int)threadIdx.x < (c.len & 3)) {
+    if (wl) store_bf16x4(wl + c.start, i, wp);
+  }, [] {}, [=](int64_t t) {
     const float wt = w[t] - step * lamb_u(m[t], v[t], w[t], rc1, rc2, eps, e.lambda);
     w[t] = wt;
     if (wl) wl[t] = f2bf(wt);
-  }
+  });
 }
 
 // ------------------------------------------------------------------------------------------- AdamW
@@ -445,13 +451,11 @@ adamw_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restri
     const LambChunk c = chunks[ci];
     if (!lamb_chunk_ok(c, n, n_weights)) continue;  // uniform over the workgroup
     const float lambda = wtab[c.weight].lambda;
-    const int nv = c.len >> 2;
     float4* wv4 = reinterpret_cast<float4*>(w + c.start);
     const float4* gv4 = reinterpret_cast<const float4*>(g + c.start);
     float4* mv4 = reinterpret_cast<float4*>(m + c.start);
     float4* vv4 = reinterpret_cast<float4*>(v + c.start);
-#pragma unroll 2
-    for (int i = threadIdx.x; i < nv; i += 256) {
+    walk_chunk(c, [=](int i) {
       float4 wv = wv4[i];
       const float4 gv = gv4[i];
       float4 mv = mv4[i];
@@ -459,53 +463,45 @@ adamw_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restri
       float* wp = &wv.x; const float* gp = &gv.x; float* mp = &mv.x; float* vp = &vv.x;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const float gt = gp[j] * gs;
-        mp[j] = fmaf(b1, mp[j], c1m * gt);
-        vp[j] = fmaf(b2, vp[j], c2m * gt * gt);
+        adam_moments(mp[j], vp[j], gp[j] * gs, b1, c1m, b2, c2m);
         wp[j] -= lr * lamb_u(mp[j], vp[j], wp[j], rc1, rc2, eps, lambda);
       }
       wv4[i] = wv;
       mv4[i] = mv;
       vv4[i] = vv;
-      if (wl) {
-        ushort4 o;
-        o.x = f2bf(wp[0]); o.y = f2bf(wp[1]); o.z = f2bf(wp[2]); o.w = f2bf(wp[3]);
-        reinterpret_cast<ushort4*>(wl + c.start)[i] = o;
-      }
-    }
-    const int64_t t = c.start + (nv << 2) + threadIdx.x;  // the chunk's len % 4 tail elements
-    if ((int)threadIdx.x < (c.len & 3)) {
-      const float gt = g[t] * gs;
-      const float mt = fmaf(b1, m[t], c1m * gt);
-      const float vt = fmaf(b2, v[t], c2m * gt * gt);
+      if (wl) store_bf16x4(wl + c.start, i, wp);
+    }, [] {}, [=](int64_t t) {
+      float mt = m[t], vt = v[t];
+      adam_moments(mt, vt, g[t] * gs, b1, c1m, b2, c2m);
       const float wt = w[t] - lr * lamb_u(mt, vt, w[t], rc1, rc2, eps, lambda);
       m[t] = mt;
       v[t] = vt;
       w[t] = wt;
       if (wl) wl[t] = f2bf(wt);
-    }
+    });
   }
 }
+
+// 1 - beta as the moment kernels take it: rounded once from double (1.f - 0.999f is 4.7e-5 off 0.001)
+static float one_minus(double beta) { return (float)(1.0 - beta); }
 
 void adamw_update(float* master, const float* grad, float* m, float* v, void* param_lowp, int64_t n,
                   const void* chunks, int c0, int c1, const void* wtab, int n_weights, const float* hyper,
                   const float* gscale_dev, double beta1, double beta2, float eps, hipStream_t st, int max_blocks) {
   if (c1 <= c0) return;
   const int grid = max_blocks > 0 ? std::min(c1 - c0, max_blocks) : c1 - c0;
-  // 1 - beta rounded once from double, as lamb_moments
   hipLaunchKernelGGL(adamw_kernel, dim3(grid), dim3(256), 0, st, master, grad, m, v, (bf16_t*)param_lowp, n,
                      (const LambChunk*)chunks, c0, c1, (const LambWeight*)wtab, n_weights, hyper, gscale_dev,
-                     (float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), eps);
+                     (float)beta1, one_minus(beta1), (float)beta2, one_minus(beta2), eps);
 }
 
 void lamb_moments(const float* master, const float* grad, float* m, float* v, int64_t n, const void* chunks,
                   int n_chunks, const void* wtab, int n_weights, const float* hyper, const float* gscale_dev,
                   double beta1, double beta2, float eps, float* partial, hipStream_t st) {
   if (n_chunks <= 0) return;
-  // 1 - beta rounded once from double (1.f - 0.999f is 4.7e-5 off 0.001)
   hipLaunchKernelGGL(lamb_moments_kernel, dim3(n_chunks), dim3(256), 0, st, master, grad, m, v, n,
                      (const LambChunk*)chunks, (const LambWeight*)wtab, n_weights, hyper, gscale_dev, (float)beta1,
-                     (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), eps, partial);
+                     one_minus(beta1), (float)beta2, one_minus(beta2), eps, partial);
 }
 void lamb_norms(const float* partial, int n_chunks, const void* wtab, int n_weights, int count, float* norms,
                 hipStream_t st) {

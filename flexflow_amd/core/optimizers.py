@@ -6,9 +6,15 @@ every weight shard of a replica group lives in one flat fp32 arena, so an update
 kernel per arena (multi-tensor apply) that also refreshes the bf16 compute copy. AdamW and LAMB
 (not in the reference) decay each weight by its own lambda: their kernels walk a chunk table of the
 arena (kernels.lamb_table), AdamW in one pass per update range, LAMB in two with the norms between.
+
+The runtime reads what an optimizer needs from what Optimizer declares, each with a default: ranged
+(step_range is implemented: the overlapped and the sharded update), two_phase (LAMB), chunk_table
+(AdamW: set_table), capturable (a captured whole step may hold the update, after use_device_alpha)
+and state_tensors(arena). AdamW and LAMB share _MomentOptimizer.
 """
 from __future__ import annotations
 
+import bisect
 import math
 
 import torch
@@ -27,6 +33,11 @@ def _resolve_clip_norm(ffmodel, clip_norm):
 
 
 class Optimizer:
+    # what the runtime (Executor, runtime/graph.py) asks; the defaults suit one that implements step() alone
+    two_phase = False     # the update is moments() / apply() with the norms' all-reduce between
+    chunk_table = False   # step_range runs over a chunk table the executor hands to set_table()
+    capturable = False    # a captured whole-step hipGraph may hold the update
+
     def __init__(self, ffmodel=None, lr=0.01, clip_norm=None):
         self.lr = lr
         self.ffmodel = ffmodel
@@ -46,6 +57,14 @@ class Optimizer:
     def init_state(self, arena):
         pass
 
+    def state_tensors(self, arena) -> tuple:
+        """The arena's state tensors, in checkpoint order (SGD: the momentum; the others: m, v)."""
+        st = self.state.get(id(arena))
+        return () if st is None else tuple(st) if isinstance(st, (tuple, list)) else (st,)
+
+    def use_device_alpha(self, device):
+        """Called before a whole step is captured: put what changes per step on the device."""
+
     def next(self):
         pass
 
@@ -56,6 +75,10 @@ class Optimizer:
         """Update elements [lo, hi) of the arena only (sharded optimizer: this rank's chunk; the
         overlapped update: one gradient bucket, launched with at most max_blocks workgroups)."""
         raise NotImplementedError
+
+    @property
+    def ranged(self) -> bool:  # step_range is implemented (with or without max_blocks)
+        return type(self).step_range is not Optimizer.step_range
 
 
 class SGDOptimizer(Optimizer):
@@ -81,6 +104,8 @@ class SGDOptimizer(Optimizer):
 
 
 class AdamOptimizer(Optimizer):
+    capturable = True
+
     def __init__(self, ffmodel=None, alpha=0.001, beta1=0.9, beta2=0.999, weight_decay=0.0, epsilon=1e-8,
                  clip_norm=None):
         super().__init__(ffmodel, alpha, clip_norm)
@@ -140,146 +165,20 @@ def _check_hyper(cls, **kw):
             raise ValueError(f"{cls}: invalid {name}={val!r}")
 
 
-class AdamWOptimizer(Optimizer):
-    """AdamW (Loshchilov & Hutter, "Decoupled Weight Decay Regularization", ICLR 2019), which is
-    torch.optim.AdamW with amsgrad=False: Adam moments of the (clipped) gradient alone, bias
-    correction inside epsilon, and the decay lambda_p * w added to the update, not to the gradient.
-    With exclude_1d, weights of one dimension or fewer (biases, LayerNorm / RMSNorm vectors) get
-    lambda_p = 0, the rule LAMBOptimizer uses; exclude_1d=False decays everything, as torch does
-    over one parameter group.
+class _MomentOptimizer(Optimizer):
+    """What AdamW and LAMB share: checked hyper-parameters, Adam moments (m, v) per arena, and
+    hyper_dev on the device, refreshed by next() and set_learning_rate(), so a captured whole-step
+    hipGraph replays the same launches. bias_correction=False keeps both corrections at 1."""
 
-    One HIP pass per update range (kernels.adamw_update) over a chunk table of the arena
-    (kernels.lamb_table) that the executor hands over at init_optimizer (set_table): a range
-    [lo, hi) is a run of consecutive chunks, found on the host and cached. The hyper-parameters live
-    on the device ([lr, 1 / (1 - beta1^t), 1 / (1 - beta2^t)], refreshed by next()), so a captured
-    whole-step hipGraph replays the same launches. State is (m, v) per arena, as Adam's."""
+    capturable = True
 
-    def __init__(self, ffmodel=None, lr=1e-3, beta1=0.9, beta2=0.999, weight_decay=0.01, epsilon=1e-8,
-                 exclude_1d=True, clip_norm=None):
-        _check_hyper("AdamWOptimizer", lr=lr, beta1=beta1, beta2=beta2, weight_decay=weight_decay, epsilon=epsilon)
+    def __init__(self, ffmodel, lr, beta1, beta2, weight_decay, epsilon, exclude_1d, clip_norm, bias_correction=True):
+        _check_hyper(type(self).__name__, lr=lr, beta1=beta1, beta2=beta2, weight_decay=weight_decay, epsilon=epsilon)
         super().__init__(ffmodel, float(lr), clip_norm)
         self.beta1, self.beta2 = float(beta1), float(beta2)
-        self.weight_decay = float(weight_decay)
-        self.epsilon = float(epsilon)
-        self.exclude_1d = bool(exclude_1d)
-        self.beta1_t = 1.0
-        self.beta2_t = 1.0
-        self.hyper_dev = None  # fp32 [3] on the arenas' device: lr, 1 / (1 - beta1^t), 1 / (1 - beta2^t)
-        # per arena: [entries, sorted cut points, tables (never freed: captured graphs hold their
-        # pointers), {(lo, hi): (table, c0, c1)}]
-        self._plans = {}
-
-    def _hyper(self):
-        if self.beta1_t == 1.0:  # before the first next(): no correction yet
-            return self.lr, 1.0, 1.0
-        return self.lr, 1.0 / (1.0 - self.beta1_t), 1.0 / (1.0 - self.beta2_t)
-
-    def _refresh(self):
-        if self.hyper_dev is not None:
-            for i, x in enumerate(self._hyper()):
-                self.hyper_dev[i].fill_(x)
-
-    def use_device_alpha(self, device):
-        """AdamW always reads its hyper-parameters from the device (the hook a captured step calls)."""
-        if self.hyper_dev is None:
-            self.hyper_dev = torch.zeros(3, device=device, dtype=torch.float32)
-            self._refresh()
-
-    def set_learning_rate(self, learning_rate):
-        self.lr = float(learning_rate)
-        self._refresh()
-
-    def weight_rule(self, shape):
-        """lambda_p of a weight of this (shard) shape."""
-        return 0.0 if self.exclude_1d and len(shape) <= 1 else self.weight_decay
-
-    def init_state(self, arena):
-        self.state[id(arena)] = (torch.zeros_like(arena.master), torch.zeros_like(arena.master))
-        self.use_device_alpha(arena.master.device)
-
-    def next(self):
-        self.beta1_t *= self.beta1
-        self.beta2_t *= self.beta2
-        self._refresh()
-
-    def set_table(self, arena, entries, cuts):
-        """entries: [(offset, numel, weight, lambda, False)] of the arena (kernels.lamb_table);
-        cuts: every bound (a multiple of 4) of a range step_range will be given. Builds the arena's
-        table; a table built earlier stays alive."""
-        old = self._plans.get(id(arena))
-        self._plans[id(arena)] = [list(entries), sorted(set(int(c) for c in cuts)), old[2] if old else [], {}]
-        self._build(arena)
-
-    def _build(self, arena):
-        entries, cuts, tabs, _ = self._plans[id(arena)]
-        size = arena.master.numel()
-        pts = sorted({0, size, *(c for c in cuts if 0 < c < size)})
-        tab = K.lamb_table(entries, list(zip(pts[:-1], pts[1:])), len(entries), size, arena.master.device)
-        starts = [int(s) for s in tab.chunks_host[:, 0]]
-        ends = [s + ln for s, ln, _ in tab.rows()]
-        tabs.append((tab, starts, ends))
-
-    def _resolve(self, arena, lo, hi):
-        plan = self._plans.get(id(arena))
-        if plan is None:
-            raise RuntimeError("AdamWOptimizer updates through a chunk table of the arena that "
-                               "Executor.init_optimizer() builds (FFModel.compile())")
-        lo, hi = int(lo), int(hi)
-        if not 0 <= lo <= hi <= arena.master.numel():
-            raise RuntimeError(f"AdamWOptimizer.step_range: [{lo}, {hi}) is outside the arena")
-        hit = plan[3].get((lo, hi))
-        if hit is not None:
-            return hit
-        import bisect
-        for _ in range(2):
-            tab, starts, ends = plan[2][-1]
-            c0, c1 = bisect.bisect_left(starts, lo), bisect.bisect_left(starts, hi)
-            # a bound is a cut when no chunk lies across it (the end of an entry is one, whatever its size)
-            across = [b for b, c in ((lo, c0), (hi, c1)) if c > 0 and ends[c - 1] > b]
-            if not across:
-                plan[3][(lo, hi)] = (tab, c0, c1)
-                return plan[3][(lo, hi)]
-            if any(b % 4 for b in across):
-                raise RuntimeError(f"AdamWOptimizer.step_range: [{lo}, {hi}) cuts a weight at an element that is "
-                                   "not a multiple of 4")
-            plan[1] = sorted(set(plan[1]) | set(across))  # a new range: one more table, built once
-            self._build(arena)
-        raise RuntimeError(f"AdamWOptimizer.step_range: no chunk run for [{lo}, {hi})")
-
-    def step(self, arena):
-        self.step_range(arena, 0, arena.master.numel() if arena is not None else 0)
-
-    def step_range(self, arena, lo, hi, max_blocks=0):
-        tab, c0, c1 = self._resolve(arena, lo, hi)
-        m, v = self.state[id(arena)]
-        K.adamw_update(arena.master, arena.grad, m, v, arena.lowp, tab, c0, c1, self.hyper_dev, self._gscale_dev(),
-                       self.beta1, self.beta2, self.epsilon, max_blocks=max_blocks)
-
-
-class LAMBOptimizer(Optimizer):
-    """LAMB (You et al., "Large Batch Optimization for Deep Learning", ICLR 2020): Adam moments,
-    decoupled weight decay and a trust ratio |w| / |update| per logical weight, taken over the
-    whole weight on every rank. With exclude_1d, weights of one dimension or fewer (biases,
-    LayerNorm gamma / beta) get no decay and no ratio: plain bias-corrected Adam.
-
-    An update is two passes with the norms in between (Executor._lamb_update): moments(),
-    the per-weight norms and their all-reduce, then apply(). The hyper-parameters live on the
-    device ([lr, 1 / (1 - beta1^t), 1 / (1 - beta2^t)], refreshed by next()), so a captured
-    whole-step hipGraph replays the same launches. State is (m, v) per arena, as Adam's."""
-
-    two_phase = True
-
-    def __init__(self, ffmodel=None, lr=1e-3, beta1=0.9, beta2=0.999, weight_decay=0.01, epsilon=1e-6,
-                 bias_correction=True, exclude_1d=True, clip_norm=None):
-        _check_hyper("LAMBOptimizer", lr=lr, beta1=beta1, beta2=beta2, weight_decay=weight_decay, epsilon=epsilon)
-        super().__init__(ffmodel, float(lr), clip_norm)
-        self.beta1, self.beta2 = float(beta1), float(beta2)
-        self.weight_decay = float(weight_decay)
-        self.epsilon = float(epsilon)
-        self.bias_correction = bool(bias_correction)
-        self.exclude_1d = bool(exclude_1d)
-        self.beta1_t = 1.0
-        self.beta2_t = 1.0
+        self.weight_decay, self.epsilon = float(weight_decay), float(epsilon)
+        self.bias_correction, self.exclude_1d = bool(bias_correction), bool(exclude_1d)
+        self.beta1_t = self.beta2_t = 1.0
         self.hyper_dev = None  # fp32 [3] on the arenas' device: lr, 1 / (1 - beta1^t), 1 / (1 - beta2^t)
 
     def _hyper(self):
@@ -292,8 +191,7 @@ class LAMBOptimizer(Optimizer):
             for i, x in enumerate(self._hyper()):
                 self.hyper_dev[i].fill_(x)
 
-    def use_device_alpha(self, device):
-        """LAMB always reads its hyper-parameters from the device (the hook a captured step calls)."""
+    def use_device_alpha(self, device):  # always on: the kernels read hyper_dev
         if self.hyper_dev is None:
             self.hyper_dev = torch.zeros(3, device=device, dtype=torch.float32)
             self._refresh()
@@ -301,12 +199,6 @@ class LAMBOptimizer(Optimizer):
     def set_learning_rate(self, learning_rate):
         self.lr = float(learning_rate)
         self._refresh()
-
-    def weight_rule(self, shape):
-        """(lambda_p, adapt_p) of a weight of this (shard) shape."""
-        if self.exclude_1d and len(shape) <= 1:
-            return 0.0, False
-        return self.weight_decay, True
 
     def init_state(self, arena):
         self.state[id(arena)] = (torch.zeros_like(arena.master), torch.zeros_like(arena.master))
@@ -316,6 +208,113 @@ class LAMBOptimizer(Optimizer):
         self.beta1_t *= self.beta1
         self.beta2_t *= self.beta2
         self._refresh()
+
+
+class _ChunkPlan:
+    """AdamW's chunk tables of one arena: the table entries, the sorted cut points, the tables built
+    so far as (table, chunk starts, chunk ends) — never freed: captured graphs hold their pointers —
+    and the cache {(lo, hi): (table, c0, c1)} of resolved ranges."""
+
+    def __init__(self, arena, entries, cuts, tables):
+        self.size, self.device = arena.master.numel(), arena.master.device
+        self.entries, self.tables, self.cache = list(entries), tables, {}
+        self.cuts = sorted(set(int(c) for c in cuts))
+        self.build()
+
+    def build(self):  # one more table, cut at every cut point
+        pts = sorted({0, self.size, *(c for c in self.cuts if 0 < c < self.size)})
+        tab = K.lamb_table(self.entries, list(zip(pts[:-1], pts[1:])), len(self.entries), self.size, self.device)
+        self.tables.append((tab, [int(s) for s in tab.chunks_host[:, 0]], [s + ln for s, ln, _ in tab.rows()]))
+
+    def resolve(self, lo, hi):
+        """(table, c0, c1): the run of whole chunks that is [lo, hi), on the newest table."""
+        lo, hi = int(lo), int(hi)
+        if not 0 <= lo <= hi <= self.size:
+            raise RuntimeError(f"AdamWOptimizer.step_range: [{lo}, {hi}) is outside the arena")
+        if (lo, hi) in self.cache:
+            return self.cache[(lo, hi)]
+        for _ in range(2):
+            tab, starts, ends = self.tables[-1]
+            c0, c1 = bisect.bisect_left(starts, lo), bisect.bisect_left(starts, hi)
+            # a bound is a cut when no chunk lies across it (the end of an entry is one, whatever its size)
+            across = [b for b, c in ((lo, c0), (hi, c1)) if c > 0 and ends[c - 1] > b]
+            if not across:
+                self.cache[(lo, hi)] = (tab, c0, c1)
+                return self.cache[(lo, hi)]
+            if any(b % 4 for b in across):
+                raise RuntimeError(f"AdamWOptimizer.step_range: [{lo}, {hi}) cuts a weight at an element that is "
+                                   "not a multiple of 4")
+            self.cuts = sorted(set(self.cuts) | set(across))  # a new range: one more table, built once
+            self.build()
+        raise RuntimeError(f"AdamWOptimizer.step_range: no chunk run for [{lo}, {hi})")
+
+
+class AdamWOptimizer(_MomentOptimizer):
+    """AdamW (Loshchilov & Hutter, "Decoupled Weight Decay Regularization", ICLR 2019), which is
+    torch.optim.AdamW with amsgrad=False: Adam moments of the (clipped) gradient alone, bias
+    correction inside epsilon, and the decay lambda_p * w added to the update, not to the gradient.
+    With exclude_1d, weights of one dimension or fewer (biases, LayerNorm / RMSNorm vectors) get
+    lambda_p = 0, the rule LAMBOptimizer uses; exclude_1d=False decays everything, as torch does
+    over one parameter group.
+
+    One HIP pass per update range (kernels.adamw_update) over a chunk table of the arena
+    (kernels.lamb_table) that the executor hands over at init_optimizer (set_table): a range
+    [lo, hi) is a run of consecutive chunks, found on the host and cached. The hyper-parameters live
+    on the device (_MomentOptimizer). State is (m, v) per arena, as Adam's."""
+
+    chunk_table = True
+
+    def __init__(self, ffmodel=None, lr=1e-3, beta1=0.9, beta2=0.999, weight_decay=0.01, epsilon=1e-8,
+                 exclude_1d=True, clip_norm=None):
+        super().__init__(ffmodel, lr, beta1, beta2, weight_decay, epsilon, exclude_1d, clip_norm)
+        self._plans = {}  # id(arena) -> _ChunkPlan
+
+    def weight_rule(self, shape):
+        """lambda_p of a weight of this (shard) shape."""
+        return 0.0 if self.exclude_1d and len(shape) <= 1 else self.weight_decay
+
+    def set_table(self, arena, entries, cuts):
+        """entries: [(offset, numel, weight, lambda, False)] of the arena (kernels.lamb_table);
+        cuts: every bound (a multiple of 4) of a range step_range will be given. Builds the arena's
+        table; a table built earlier stays alive."""
+        old = self._plans.get(id(arena))
+        self._plans[id(arena)] = _ChunkPlan(arena, entries, cuts, old.tables if old else [])
+
+    def step(self, arena):
+        self.step_range(arena, 0, arena.master.numel() if arena is not None else 0)
+
+    def step_range(self, arena, lo, hi, max_blocks=0):
+        plan = self._plans.get(id(arena))
+        if plan is None:
+            raise RuntimeError("AdamWOptimizer updates through a chunk table of the arena that "
+                               "Executor.init_optimizer() builds (FFModel.compile())")
+        tab, c0, c1 = plan.resolve(lo, hi)
+        m, v = self.state[id(arena)]
+        K.adamw_update(arena.master, arena.grad, m, v, arena.lowp, tab, c0, c1, self.hyper_dev, self._gscale_dev(),
+                       self.beta1, self.beta2, self.epsilon, max_blocks=max_blocks)
+
+
+class LAMBOptimizer(_MomentOptimizer):
+    """LAMB (You et al., "Large Batch Optimization for Deep Learning", ICLR 2020): Adam moments,
+    decoupled weight decay and a trust ratio |w| / |update| per logical weight, taken over the
+    whole weight on every rank. With exclude_1d, weights of one dimension or fewer (biases,
+    LayerNorm gamma / beta) get no decay and no ratio: plain bias-corrected Adam.
+
+    An update is two passes with the norms in between (Executor._lamb_update): moments(),
+    the per-weight norms and their all-reduce, then apply(). The hyper-parameters live on the
+    device (_MomentOptimizer). State is (m, v) per arena, as Adam's."""
+
+    two_phase = True
+
+    def __init__(self, ffmodel=None, lr=1e-3, beta1=0.9, beta2=0.999, weight_decay=0.01, epsilon=1e-6,
+                 bias_correction=True, exclude_1d=True, clip_norm=None):
+        super().__init__(ffmodel, lr, beta1, beta2, weight_decay, epsilon, exclude_1d, clip_norm, bias_correction)
+
+    def weight_rule(self, shape):
+        """(lambda_p, adapt_p) of a weight of this (shard) shape."""
+        if self.exclude_1d and len(shape) <= 1:
+            return 0.0, False
+        return self.weight_decay, True
 
     def moments(self, arena, table, partials):
         m, v = self.state[id(arena)]

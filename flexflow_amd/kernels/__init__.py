@@ -2089,9 +2089,7 @@ def adam_update(master, grad, m, v, lowp, alpha_t, b1, b2, wd, eps, gscale=1.0, 
         alpha_t = float(alpha_dev.item())
     if gscale_dev is not None:
         gscale = gscale * float(gscale_dev.item())
-    g = grad * gscale + wd * master
-    m.mul_(b1).add_((1 - b1) * g)
-    v.mul_(b2).add_((1 - b2) * g * g)
+    _moments_(m, v, grad * gscale + wd * master, b1, b2)
     master.sub_(alpha_t * m / (v.sqrt() + eps))
     if lowp is not None:
         lowp.copy_(master)
@@ -2117,6 +2115,9 @@ class LambTable:
         """[(start, len, weight)] of the chunks, for the CPU fallbacks."""
         c = self.chunks_host
         return [(int(s), int(p & 0xFFFFFFFF), int(p >> 32)) for s, p in c]
+
+    def lambdas(self):  # the per-weight lambdas as an fp32 CPU tensor [n_weights], for the CPU fallbacks
+        return torch.from_numpy(self.wtab_host[:, 0].copy()).view(torch.float32)
 
 
 def lamb_table(entries, ranges, n_weights, size, device, owned=()):
@@ -2165,6 +2166,11 @@ def _lamb_u(m, v, w, rc1, rc2, eps, lam):
     return (m * rc1) / ((v * rc2).sqrt() + eps) + lam * w
 
 
+def _moments_(m, v, g, b1, b2):  # the Adam moments of the (scaled) gradient g, in place
+    m.mul_(b1).add_((1 - b1) * g)
+    v.mul_(b2).add_((1 - b2) * g * g)
+
+
 def lamb_moments(master, grad, m, v, table, hyper, gscale_dev, b1, b2, eps, partials):
     """Stage 1 over the table's chunks: m, v updated in place from gscale_dev * grad, and per chunk
     (sum w^2, sum u^2) into partials [2 * n_chunks], u = m rc1 / (sqrt(v rc2) + eps) + lambda w.
@@ -2173,11 +2179,9 @@ def lamb_moments(master, grad, m, v, table, hyper, gscale_dev, b1, b2, eps, part
         ext().lamb_moments(master, grad, m, v, table.chunks, table.wtab, hyper, gscale_dev, b1, b2, eps, partials)
         return
     gs = gscale_dev[0] if gscale_dev is not None else 1.0
-    lam = torch.from_numpy(table.wtab_host[:, 0].copy()).view(torch.float32)
+    lam = table.lambdas()
     for i, (s, ln, wi) in enumerate(table.rows()):
-        g = grad[s:s + ln] * gs
-        m[s:s + ln].mul_(b1).add_((1 - b1) * g)
-        v[s:s + ln].mul_(b2).add_((1 - b2) * g * g)
+        _moments_(m[s:s + ln], v[s:s + ln], grad[s:s + ln] * gs, b1, b2)
         w = master[s:s + ln]
         u = _lamb_u(m[s:s + ln], v[s:s + ln], w, hyper[1], hyper[2], eps, lam[wi])
         partials[2 * i] = (w * w).sum(dtype=torch.float32)
@@ -2204,7 +2208,7 @@ def lamb_apply(master, m, v, lowp, table, hyper, eps, norms):
     if native(master):
         ext().lamb_apply(master, m, v, lowp, table.chunks, table.wtab, hyper, eps, norms)
         return
-    lam = torch.from_numpy(table.wtab_host[:, 0].copy()).view(torch.float32)
+    lam = table.lambdas()
     for s, ln, wi in table.rows():
         wn, un = norms[2 * wi].sqrt(), norms[2 * wi + 1].sqrt()
         r = wn / un if (table.wtab_host[wi, 1] & 1) and wn > 0 and un > 0 else 1.0
@@ -2257,11 +2261,9 @@ def adamw_update(master, grad, m, v, lowp, table, c0, c1, hyper, gscale_dev, b1,
     if not 0 <= c0 <= c1 <= table.n_chunks:
         raise RuntimeError(f"adamw_update: chunks [{c0}, {c1}) outside the table's {table.n_chunks}")
     gs = gscale_dev[0] if gscale_dev is not None else 1.0
-    lam = torch.from_numpy(table.wtab_host[:, 0].copy()).view(torch.float32)
+    lam = table.lambdas()
     for s, ln, wi in table.rows()[c0:c1]:
-        g = grad[s:s + ln] * gs
-        m[s:s + ln].mul_(b1).add_((1 - b1) * g)
-        v[s:s + ln].mul_(b2).add_((1 - b2) * g * g)
+        _moments_(m[s:s + ln], v[s:s + ln], grad[s:s + ln] * gs, b1, b2)
         w = master[s:s + ln]
         w.sub_(hyper[0] * _lamb_u(m[s:s + ln], v[s:s + ln], w, hyper[1], hyper[2], eps, lam[wi]))
         if lowp is not None:

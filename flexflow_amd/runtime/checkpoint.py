@@ -33,6 +33,11 @@ def _arenas(ex):
     return [(i, ar) for i, ar in enumerate(ex.arenas.values()) if ar.size]
 
 
+def _state(opt, ar):
+    """The optimizer's state tensors of the arena, saved as arena{i}.opt{j} in this order."""
+    return opt.state_tensors(ar) if opt is not None else ()
+
+
 def _used(ar) -> int:
     """Elements of the arena actually holding weights (the rest is alignment / ZeRO padding)."""
     return max((int(e[1]) + int(e[2]) for e in ar.entries), default=0)
@@ -46,17 +51,16 @@ def save_checkpoint(model, path: str):
         # sharded optimizer: every rank saves the full master AND the full optimizer state, so
         # the checkpoint is independent of the sharding geometry it was written under
         ex.sync_master()
-        ex.sync_optimizer_state(opt)
+        if opt is not None:
+            ex.sync_optimizer_state(opt)
     os.makedirs(path, exist_ok=True)
     tensors = {}
     layout = []
     wkeys = _weight_keys(model)
     for i, ar in _arenas(ex):
         tensors[f"arena{i}.master"] = ar.master.detach().contiguous().cpu()
-        st = getattr(opt, "state", {}).get(id(ar))
-        if st is not None:
-            for j, t in enumerate(st if isinstance(st, (tuple, list)) else (st,)):
-                tensors[f"arena{i}.opt{j}"] = t.detach().contiguous().cpu()
+        for j, t in enumerate(_state(opt, ar)):
+            tensors[f"arena{i}.opt{j}"] = t.detach().contiguous().cpu()
         layout.append({"arena": i, "size": int(ar.size), "used": _used(ar),
                        "entries": [[wkeys.get(e[0].guid, getattr(e[0], "name", str(e[0]))), int(e[1]), int(e[2]),
                                     list(e[3])] for e in ar.entries]})
@@ -117,8 +121,7 @@ def load_checkpoint(model, path: str, strict: bool = True):
                              "arena sizes differ from this job's; it cannot be mapped safely")
         for i, ar in arenas:
             ar.master.copy_(tensors[f"arena{i}.master"].to(ar.master.device))
-            st = getattr(opt, "state", {}).get(id(ar))
-            for j, t in enumerate(list(st) if isinstance(st, (tuple, list)) else ([st] if st is not None else [])):
+            for j, t in enumerate(_state(opt, ar)):
                 if f"arena{i}.opt{j}" in tensors:
                     t.copy_(tensors[f"arena{i}.opt{j}"].to(t.device))
             if ar.lowp is not None:
@@ -132,8 +135,7 @@ def load_checkpoint(model, path: str, strict: bool = True):
     wkeys = _weight_keys(model)
     for i, ar in (_arenas(ex) if md is not None else []):
         ar.master.zero_()
-        st = getattr(opt, "state", {}).get(id(ar))
-        st = list(st) if isinstance(st, (tuple, list)) else ([st] if st is not None else [])
+        st = _state(opt, ar)
         for t in st:
             t.zero_()
         for w, off, n, shape in ar.entries:

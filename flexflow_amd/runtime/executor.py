@@ -652,16 +652,25 @@ class Executor:
 
     def _overlap_possible(self):
         opt = self.model.optimizer
-        from ..core.optimizers import Optimizer
-        ranged = opt is not None and getattr(type(opt), "step_range", None) not in (None, Optimizer.step_range)
         # clipping by global norm needs every gradient before any weight moves: no overlapped update
         # (LAMB likewise: its per-weight norms need every gradient; it has no step_range either)
-        return (self.training and ranged and not self.zero
-                and not getattr(opt, "clip_norm", None) and not getattr(opt, "two_phase", False)
+        return (self.training and opt is not None and opt.ranged and not self.zero
+                and not getattr(opt, "clip_norm", None) and not opt.two_phase
                 and not self._sparse_plan(opt)
                 and not self.hooks and self.device.type == "cuda"
                 and not torch.cuda.is_current_stream_capturing()
                 and not any(L.attrs.get("regularizer") is not None for L in self.layers))
+
+    @staticmethod
+    def _update_pieces(b):
+        """The overlapped update of bucket b as [lo, hi) launches of at most FF_UPD_CHUNK elements
+        (default 4 Mi = 16 MB per fp32 stream, ~23 us): each full-grid sweep holds every wave slot of
+        every CU until it ends, so a compute-stream kernel queued behind it waited out the whole
+        64 MiB bucket (~93 us: col_reduce 5 -> 68 us, the persistent wgrad GEMM 125 -> 200 us);
+        between shorter launches the backward's kernels get the CUs. Same-box A/B, BERT-Large:
+        43.76 -> 43.43 ms (1 Mi: no gain, 8 Mi: -0.1; profiles/update_interference_r6.txt); 0 = whole bucket"""
+        ch = int(os.environ.get("FF_UPD_CHUNK", "4194304")) // 8 * 8
+        return [(a, min(a + ch, b["hi"])) for a in range(b["lo"], b["hi"], ch)] if ch > 0 else [(b["lo"], b["hi"])]
 
     def _on_bucket_ready(self, b, handle):
         """Overlapped update: bucket b's gradients are final (all-reduced when handle is set), so
@@ -686,16 +695,7 @@ class Executor:
             self._upd_stream.wait_event(ev)
             if handle is not None:
                 handle.wait()  # the side stream waits for the bucket's all-reduce
-            # the bucket's update as launches of at most FF_UPD_CHUNK elements (default 4 Mi = 16 MB
-            # per fp32 stream, ~23 us): each full-grid sweep holds every wave slot of every CU until
-            # it ends, so a compute-stream kernel queued behind it waited out the whole 64 MiB
-            # bucket (~93 us: col_reduce 5 -> 68 us, the persistent wgrad GEMM 125 -> 200 us);
-            # between shorter launches the backward's kernels get the CUs. Same-box A/B, BERT-Large:
-            # 43.76 -> 43.43 ms (1 Mi: no gain, 8 Mi: -0.1; profiles/update_interference_r6.txt); 0 = whole bucket
-            ch = int(os.environ.get("FF_UPD_CHUNK", "4194304")) // 8 * 8
-            pieces = [(a, min(a + ch, b["hi"])) for a in range(b["lo"], b["hi"], ch)] if ch > 0 else \
-                [(b["lo"], b["hi"])]
-            for lo, hi in pieces:
+            for lo, hi in self._update_pieces(b):
                 if self._upd_blocks:
                     self.model.optimizer.step_range(ar, lo, hi, max_blocks=self._upd_blocks)
                 else:  # plain call: user optimizers may implement step_range(arena, lo, hi) only
@@ -770,7 +770,7 @@ class Executor:
         self._opt_next_done = None
         self._bwd_since_update += 1
         if self._overlap_active:
-            if getattr(self.model.optimizer, "set_table", None) is not None:
+            if self.model.optimizer.chunk_table:
                 self._adamw_setup(self.model.optimizer)
             self.model.optimizer.next()  # this step's bias-corrected scalars, before any bucket update
             self._opt_next_done = self.model.optimizer
@@ -1160,15 +1160,15 @@ class Executor:
         # so this update runs dense (and zero_gradients then clears the whole table)
         multi_bwd = self._bwd_since_update > 1
         self._bwd_since_update = 0
-        if getattr(optimizer, "two_phase", False):
+        if optimizer.two_phase:
             self._lamb_update(optimizer)
-        if getattr(optimizer, "set_table", None) is not None:
+        if optimizer.chunk_table:
             self._adamw_setup(optimizer)  # a no-op unless weight_decay or exclude_1d changed
         for grp, ar in self.arenas.items():
             if not ar.size:
                 continue
             bs = self.zero_buckets.get(grp)
-            if getattr(optimizer, "two_phase", False):
+            if optimizer.two_phase:
                 if bs is not None:
                     self._zero_all_gather(grp, ar, bs)
                 continue
@@ -1186,15 +1186,7 @@ class Executor:
                 else:
                     optimizer.step(ar)
                 continue
-            g = self.comm.group(grp)
-            for i, b in enumerate(bs):
-                lo, hi = b["own"]
-                optimizer.step_range(ar, lo, hi)
-                # the compute copy (bf16, or the fp32 master itself) of the whole bucket, in place
-                src = ar.lowp if ar.lowp is not None else ar.master
-                self._ag_pending[(grp, i)] = dist.all_gather_into_tensor(src[b["lo"]:b["hi"]], src[lo:hi], group=g,
-                                                                          async_op=True)
-            self._master_stale |= ar.lowp is not None
+            self._zero_all_gather(grp, ar, bs, optimizer)
         if self._upd_stream is not None and self._upd_done:
             torch.cuda.current_stream(self.device).wait_stream(self._upd_stream)
         self._upd_done = set()
@@ -1202,16 +1194,29 @@ class Executor:
         self._opt_next_done = None
         self.step_idx += 1
 
-    def _zero_all_gather(self, grp, ar, bs):
+    def _zero_all_gather(self, grp, ar, bs, optimizer=None):
         """Sharded optimizer: the updated compute copy (bf16, or the fp32 master itself) of every
-        bucket is gathered from the ranks' own chunks, in place, while the next forward runs."""
+        bucket is gathered from the ranks' own chunks, in place, while the next forward runs.
+        With an optimizer, each bucket's own chunk is updated just before its gather is issued."""
         g = self.comm.group(grp)
         src = ar.lowp if ar.lowp is not None else ar.master
         for i, b in enumerate(bs):
             lo, hi = b["own"]
+            if optimizer is not None:
+                optimizer.step_range(ar, lo, hi)
             self._ag_pending[(grp, i)] = dist.all_gather_into_tensor(src[b["lo"]:b["hi"]], src[lo:hi], group=g,
                                                                       async_op=True)
         self._master_stale |= ar.lowp is not None
+
+    @staticmethod
+    def _table_entries(ar, optimizer, index):
+        """kernels.lamb_table's (offset, numel, weight, lambda, adapt) of the arena's entries: weight =
+        index(i, w) for entry i holding w, weight_rule gives lambda (AdamW: no trust ratio) or (lambda, adapt)."""
+        out = []
+        for i, (w, off, n, shape) in enumerate(ar.entries):
+            rule = optimizer.weight_rule(shape)
+            out.append((off, n, index(i, w), *(rule if isinstance(rule, tuple) else (rule, False))))
+        return out
 
     def _lamb_setup(self, optimizer):
         """LAMB's device tables, built once per optimizer and set of hyper-parameters the tables
@@ -1232,11 +1237,8 @@ class Executor:
         for grp, ar in self.arenas.items():
             if not ar.size:
                 continue
-            entries = []
-            for w, off, n, shape in ar.entries:
-                lam, adapt = optimizer.weight_rule(shape)
-                entries.append((off, n, slot[w.guid], lam, adapt))
-                held.add(slot[w.guid])
+            entries = self._table_entries(ar, optimizer, lambda i, w: slot[w.guid])
+            held.update(e[2] for e in entries)
             bs = self.zero_buckets.get(grp)
             ranges = [b["own"] for b in bs if b["own"][1] > b["own"][0]] if bs is not None else [(0, ar.size)]
             # a replicated arena counts on the lowest rank of its group, a ZeRO arena by each
@@ -1263,11 +1265,10 @@ class Executor:
         key = (id(optimizer), optimizer.weight_decay, optimizer.exclude_1d, os.environ.get("FF_UPD_CHUNK"))
         if getattr(self, "_adamw_key", None) == key:
             return
-        ch = int(os.environ.get("FF_UPD_CHUNK", "4194304")) // 8 * 8  # as _on_bucket_ready
         for grp, ar in self.arenas.items():
             if not ar.size:
                 continue
-            entries = [(off, n, i, optimizer.weight_rule(shape), False) for i, (_, off, n, shape) in enumerate(ar.entries)]
+            entries = self._table_entries(ar, optimizer, lambda i, w: i)
             cuts = set()
             for _, flat, buckets in self.bucketer.arenas:
                 if flat is not ar.grad:
@@ -1278,8 +1279,8 @@ class Executor:
                     cuts.update((b["lo"], (b["hi"] + 7) // 8 * 8))
                     if b.get("sharded"):
                         cuts.update(b["own"])
-                    elif ch > 0:
-                        cuts.update(range(b["lo"], b["hi"], ch))
+                    else:
+                        cuts.update(lo for lo, _ in self._update_pieces(b))
             optimizer.set_table(ar, entries, cuts)
         self._adamw_key = key
 
@@ -1359,11 +1360,8 @@ class Executor:
         self.wait_all_gathers()
         for grp, bs in self.zero_buckets.items():
             ar = self.arenas[grp]
-            st = getattr(optimizer, "state", {}).get(id(ar))
-            if st is None:
-                continue
             g = self.comm.group(grp)
-            for t in (st if isinstance(st, (tuple, list)) else (st,)):
+            for t in optimizer.state_tensors(ar):
                 for b in bs:
                     dist.all_gather_into_tensor(t[b["lo"]:b["hi"]], t[b["own"][0]:b["own"][1]], group=g)
 
@@ -1372,9 +1370,9 @@ class Executor:
             optimizer.init_state(ar)
         if getattr(optimizer, "clip_norm", None):
             self._clip_setup(optimizer)
-        if getattr(optimizer, "two_phase", False):
+        if optimizer.two_phase:
             self._lamb_setup(optimizer)
-        if getattr(optimizer, "set_table", None) is not None:  # AdamW: ranges over a chunk table
+        if optimizer.chunk_table:  # AdamW: ranges over a chunk table
             self._adamw_setup(optimizer)
 
     def _clip_setup(self, optimizer):

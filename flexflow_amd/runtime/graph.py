@@ -92,7 +92,7 @@ class StepGraph:
 
     def _full_step(self, m, ex) -> bool:
         """Capture the optimizer update too (its overlapped per-bucket launches on the side stream
-        included): one process, Adam (its launches read the per-step alpha_t from a device scalar
+        included): one process and an optimizer that declares itself capturable: Adam (its launches read the per-step alpha_t from a device scalar
         that next() refreshes before each replay; with clip_norm the captured update also holds the
         gradient's sum of squares, the coefficient kernel and the Adam launches that read it, all
         on the device), or LAMB and AdamW (all of their hyper-parameters, norms and trust ratios stay
@@ -101,10 +101,9 @@ class StepGraph:
         vs 1.670-1.682 ms, ResNet-50 7.58-7.60 vs 7.60 ms (profiles/graph_update_ab_r5.txt) — the
         eager update after the replay was not exposed enough for the overlap to pay."""
         import torch.distributed as dist
-        from ..core.optimizers import AdamOptimizer, AdamWOptimizer, LAMBOptimizer
         if ex.comm.distributed or getattr(ex.comm, "force", False) or (dist.is_available() and dist.is_initialized()):
             return False  # any process group (a forced world-1 RCCL one included): update() stays eager
-        return type(m.optimizer) in (AdamOptimizer, AdamWOptimizer, LAMBOptimizer) and os.environ.get("FF_GRAPH_UPDATE", "0") == "1"
+        return m.optimizer.capturable and os.environ.get("FF_GRAPH_UPDATE", "0") == "1"
 
     def step(self):
         m = self.model

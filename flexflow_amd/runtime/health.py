@@ -69,7 +69,8 @@ def determinism_check(model, steps: int = 1) -> bool:
     ex = model.executor
     opt = model.optimizer
     w0 = _snapshot(ex)
-    st0 = {k: tuple(t.clone() for t in v) for k, v in getattr(opt, "state", {}).items()}
+    state = [t for ar in ex.arenas.values() for t in opt.state_tensors(ar)]
+    st0 = [t.clone() for t in state]
     bt = (getattr(opt, "beta1_t", None), getattr(opt, "beta2_t", None))
 
     def restore():
@@ -77,9 +78,8 @@ def determinism_check(model, steps: int = 1) -> bool:
             ar.master.copy_(w)
             if ar.lowp is not None:
                 ar.lowp.copy_(w.to(ar.lowp.dtype))
-        for k, v in st0.items():
-            for dst, src in zip(opt.state[k], v):
-                dst.copy_(src)
+        for dst, src in zip(state, st0):
+            dst.copy_(src)
         if bt[0] is not None:
             opt.beta1_t, opt.beta2_t = bt
 

@@ -174,7 +174,7 @@ def test_step_range_resolves_cuts_and_builds_tables_for_new_ranges():
     opt.init_state(ar)
     cut = ent[7][0] + C + 400
     opt.set_table(ar, ent, [0, cut, size])
-    tabs = opt._plans[id(ar)][2]
+    tabs = opt._plans[id(ar)].tables
     assert len(tabs) == 1
     ar.master[real] = 1.0
     ar.grad[:] = 0.5  # the padding too: an update that touched it would move it
