@@ -1251,6 +1251,50 @@ void rmsnorm_bwd(Tensor x, Tensor w, Tensor dy, Tensor rstd, Tensor dx, optional
   ffk::rmsnorm_bwd(dtcode(x), x.data_ptr(), w.data_ptr(), dy.data_ptr(), rstd.data_ptr<float>(), dx.data_ptr(),
                    ptr<float>(dw), rows, d, cur_stream());
 }
+int64_t add_rmsnorm_bwd_waves(int64_t rows, int64_t d, int64_t elem_size) {
+  return ffk::add_rmsnorm_groups((int)rows, (int)d, (int)elem_size);
+}
+void add_rmsnorm_fwd(Tensor x, Tensor res, Tensor w, Tensor s, Tensor y, Tensor rstd, int64_t rows, int64_t d,
+                     double eps) {
+  check_dev(x, "x"); check_dev(res, "res"); check_dev(w, "w"); check_dev(s, "s"); check_dev(y, "y");
+  check_dev(rstd, "rstd");
+  TORCH_CHECK(d >= 1 && d <= 8192, "add_rmsnorm: last dimension must be in 1..8192");
+  TORCH_CHECK(x.is_contiguous() && res.is_contiguous() && s.is_contiguous() && y.is_contiguous() &&
+              w.is_contiguous() && x.numel() == rows * d && res.numel() == x.numel() && s.numel() == x.numel() &&
+              y.numel() == x.numel() && w.numel() == d, "add_rmsnorm_fwd: shapes");
+  TORCH_CHECK(res.scalar_type() == x.scalar_type() && w.scalar_type() == x.scalar_type() &&
+              s.scalar_type() == x.scalar_type() && y.scalar_type() == x.scalar_type(), "add_rmsnorm_fwd: dtypes");
+  TORCH_CHECK(rstd.scalar_type() == at::kFloat && rstd.is_contiguous() && rstd.numel() >= rows, "add_rmsnorm_fwd: rstd");
+  ffk::add_rmsnorm_fwd(dtcode(x), x.data_ptr(), res.data_ptr(), w.data_ptr(), s.data_ptr(), y.data_ptr(),
+                       rstd.data_ptr<float>(), rows, d, eps, cur_stream());
+}
+void add_rmsnorm_bwd(Tensor s, Tensor w, Tensor rstd, Tensor dy, optional<Tensor> ds, Tensor dx, optional<Tensor> dw,
+                     optional<Tensor> ws, int64_t rows, int64_t d) {
+  check_dev(s, "s"); check_dev(w, "w"); check_dev(rstd, "rstd"); check_dev(dy, "dy"); check_dev(dx, "dx");
+  TORCH_CHECK(d >= 1 && d <= 8192, "add_rmsnorm: last dimension must be in 1..8192");
+  TORCH_CHECK(s.is_contiguous() && dy.is_contiguous() && dx.is_contiguous() && w.is_contiguous() &&
+              s.numel() == rows * d && dy.numel() == s.numel() && dx.numel() == s.numel() && w.numel() == d,
+              "add_rmsnorm_bwd: shapes");
+  TORCH_CHECK(dy.scalar_type() == s.scalar_type() && w.scalar_type() == s.scalar_type() &&
+              dx.scalar_type() == s.scalar_type(), "add_rmsnorm_bwd: dtypes");
+  TORCH_CHECK(rstd.scalar_type() == at::kFloat && rstd.is_contiguous() && rstd.numel() >= rows, "add_rmsnorm_bwd: rstd");
+  const bool has_ds = ds.has_value() && ds->defined(), has_dw = dw.has_value() && dw->defined();
+  if (has_ds) {
+    check_dev(*ds, "ds");
+    TORCH_CHECK(ds->is_contiguous() && ds->numel() == s.numel() && ds->scalar_type() == s.scalar_type(),
+                "add_rmsnorm_bwd: ds");
+  }
+  if (has_dw) {
+    check_dev(*dw, "dw");
+    TORCH_CHECK(dw->scalar_type() == at::kFloat && dw->is_contiguous() && dw->numel() >= d, "add_rmsnorm_bwd: dw fp32");
+    TORCH_CHECK(ws.has_value() && ws->defined() && ws->is_cuda() && ws->scalar_type() == at::kFloat &&
+                ws->is_contiguous() && ws->numel() >= add_rmsnorm_bwd_waves(rows, d, s.element_size()) * d,
+                "add_rmsnorm_bwd: dw needs an fp32 workspace of add_rmsnorm_bwd_waves(rows, d, element size) * d");
+  }
+  ffk::add_rmsnorm_bwd(dtcode(s), s.data_ptr(), w.data_ptr(), rstd.data_ptr<float>(), dy.data_ptr(),
+                       has_ds ? ds->data_ptr() : nullptr, dx.data_ptr(), has_dw ? dw->data_ptr<float>() : nullptr,
+                       has_dw ? ws->data_ptr<float>() : nullptr, rows, d, cur_stream());
+}
 void channel_sum(Tensor dy, optional<Tensor> y, optional<Tensor> dz, optional<Tensor> db, Tensor ws, int64_t N,
                  int64_t C, int64_t HW, bool nhwc) {
   check_dev(dy, "dy");
@@ -1522,6 +1566,9 @@ PYBIND11_MODULE(_C, m) {
   m.def("bn_ws", &bn_ws);
   m.def("rmsnorm_fwd", &rmsnorm_fwd);
   m.def("rmsnorm_bwd", &rmsnorm_bwd);
+  m.def("add_rmsnorm_bwd_waves", &add_rmsnorm_bwd_waves);
+  m.def("add_rmsnorm_fwd", &add_rmsnorm_fwd);
+  m.def("add_rmsnorm_bwd", &add_rmsnorm_bwd);
   m.def("channel_sum", &channel_sum);
   m.def("pool2d_fwd", &pool2d_fwd);
   m.def("pool2d_bwd", &pool2d_bwd);

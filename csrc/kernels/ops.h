@@ -247,6 +247,15 @@ void rmsnorm_fwd(int dt, const void* x, const void* w, void* y, float* rstd, int
                  hipStream_t st);
 void rmsnorm_bwd(int dt, const void* x, const void* w, const void* dy, const float* rstd, void* dx, float* dw,
                  int rows, int d, hipStream_t st);
+// add_rmsnorm.hip: RMS norm of a sum, the sum an output: s = T(x + res), y = s * rstd * w with the
+// statistics of the rounded s (d <= 8192). Backward: dx = d/dx = d/dres, ds (may be null) the gradient
+// arriving on s; dw (fp32, may be null) += the weight gradient through `slab`, an fp32 workspace of
+// add_rmsnorm_groups(rows, d, element size) * d floats folded in a fixed order (no atomics).
+void add_rmsnorm_fwd(int dt, const void* x, const void* res, const void* w, void* s, void* y, float* rstd, int rows,
+                     int d, float eps, hipStream_t st);
+void add_rmsnorm_bwd(int dt, const void* s, const void* w, const float* rstd, const void* dy, const void* ds, void* dx,
+                     float* dw, float* slab, int rows, int d, hipStream_t st);
+int add_rmsnorm_groups(int rows, int d, int esz);
 // cnn.hip: batch norm (split Welford statistics, fused ReLU) and 2-D pooling of NCHW tensors, or
 // (nhwc = 1: bf16, C % 8 == 0) of channel-last tensors
 int bn_partial_floats(int N, int C, int HW);  // ws floats for batchnorm_fwd / batchnorm_bwd

@@ -14,6 +14,9 @@ sentence) and `position_ids` that restart at every sentence, which the rotation 
 `--window W` is sliding-window attention (`DecoderConfig.sliding_window`): every query sees the last W keys,
 itself included (`window=(W - 1, 0)`), with `--packed` and without.
 
+`--fused-norm` builds every residual add together with the RMSNorm behind it as one `add_rms_norm` layer
+(`DecoderConfig.fused_norm`): the same weights under the same names, one launch each way instead of two.
+
 `--optimizer adamw --weight-decay X` trains with AdamW (decoupled weight decay X on the matrices and the
 embedding table, none on the RMSNorm gains), as the recipes of these models do; the default stays Adam.
 
@@ -23,6 +26,7 @@ embedding table, none on the RMSNorm gains), as the recipes of these models do; 
     python examples/python/native/rope_decoder.py --small --iterations 8            # CPU-sized
     python examples/python/native/rope_decoder.py --small --packed --iterations 8
     python examples/python/native/rope_decoder.py --small --mlp swiglu --iterations 8
+    python examples/python/native/rope_decoder.py --small --fused-norm --iterations 8
 """
 import argparse
 import sys
@@ -45,6 +49,7 @@ def top_level_task(argv=None):
     ap.add_argument("--mlp", choices=("gelu", "swiglu", "geglu"), default="gelu")
     ap.add_argument("--fused-gate-up", action="store_true")
     ap.add_argument("--window", type=int, default=0)
+    ap.add_argument("--fused-norm", action="store_true")
     ap.add_argument("--optimizer", choices=("adam", "adamw"), default="adam")
     ap.add_argument("--weight-decay", type=float, default=0.01)
     args, rest = ap.parse_known_args(sys.argv[1:] if argv is None else argv)
@@ -54,6 +59,7 @@ def top_level_task(argv=None):
         DecoderConfig(hidden=512, heads=8, kv_heads=2, layers=4, ffn=2048, vocab=4096, seq=args.seq_length or 256)
     dc.mlp, dc.fused_gate_up = args.mlp, args.fused_gate_up
     dc.sliding_window = args.window
+    dc.fused_norm = args.fused_norm
     s = dc.seq
     seg = pos = None
     if args.packed:

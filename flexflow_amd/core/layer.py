@@ -114,3 +114,17 @@ Batch_Norm = OP_CLASSES.get(OperatorType.OP_BATCHNORM)
 
 def op_class(op_type: OperatorType) -> type:
     return OP_CLASSES.get(op_type, Layer)
+
+
+def weight_slots(layers):
+    """(weight, (position, slot)) over the layers in order: the identity that seeds a weight's default
+    initializer and keys it in a checkpoint. A layer that stands for two takes two positions and its
+    weights the second (OP_ADD_RMS_NORM: an `add` and the `rms_norm` behind it), so a graph built with such
+    layers and the same graph built without them number every weight alike, whatever is appended later;
+    positions only grow, so no two weights share one."""
+    pos = 0
+    for L in layers:
+        pos += L.op_type == OperatorType.OP_ADD_RMS_NORM
+        for i, w in enumerate(L.weights):
+            yield w, (pos, i)
+        pos += 1

@@ -286,6 +286,13 @@ class FFModel:
         """y = x * rsqrt(mean(x^2, -1) + eps) * weight (extension; ops/norm.py RMSNorm)."""
         return self._add(OperatorType.OP_RMS_NORM, [input], name, eps=float(eps)).outputs[0]
 
+    def add_rms_norm(self, x, residual, eps=1e-6, name=None):
+        """(sum, normed): sum = x + residual, normed = rms_norm(sum) with this layer's weight, in one kernel
+        each way (extension; ops/norm.py AddRMSNorm). The sum is returned because a pre-norm block's residual
+        stream is read again by the next block."""
+        outs = self._add(OperatorType.OP_ADD_RMS_NORM, [x, residual], name, eps=float(eps)).outputs
+        return outs[0], outs[1]
+
     def batch_matmul(self, A, B, a_seq_length_dim=None, b_seq_length_dim=None, name=None):
         return self._add(OperatorType.OP_BATCHMATMUL, [A, B], name, a_seq_length_dim=a_seq_length_dim,
                          b_seq_length_dim=b_seq_length_dim).outputs[0]

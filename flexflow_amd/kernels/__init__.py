@@ -2799,6 +2799,52 @@ def rmsnorm_bwd(x2d, w, dy2d, rstd, dw):
     return dx.to(x2d.dtype)
 
 
+# ------------------------------------------------------------------ RMS norm of a sum (add_rmsnorm.hip)
+@torch.no_grad()
+def add_rmsnorm_fwd(x2d, res2d, w, eps):
+    """s = (x + res) rounded to the tensors' dtype, y = s * rsqrt(mean(s^2) + eps) * w per row, the
+    statistics taken from the rounded s. Returns (s, y, rstd): one launch, two row reads, two row writes."""
+    rows, d = x2d.shape
+    if native(x2d):
+        s, y = torch.empty_like(x2d), torch.empty_like(x2d)
+        rstd = torch.empty(rows, device=x2d.device, dtype=torch.float32)
+        ext().add_rmsnorm_fwd(x2d, res2d, w, s, y, rstd, rows, d, eps)
+        return s, y, rstd
+    s = (x2d.float() + res2d.float()).to(x2d.dtype)
+    sf = s.float()
+    rstd = torch.rsqrt(sf.pow(2).mean(-1) + eps)
+    return s, (sf * rstd[:, None] * w.float()).to(x2d.dtype), rstd
+
+
+def add_rmsnorm_bwd_waves(rows, d, elem_size):
+    """Rows of the fp32 [waves, d] slab of weight-gradient partials add_rmsnorm_bwd's launch fills."""
+    return int(ext().add_rmsnorm_bwd_waves(rows, d, elem_size))
+
+
+@torch.no_grad()
+def add_rmsnorm_bwd(s2d, w, rstd, dy2d, ds2d, dw):
+    """dx = rstd g - rstd^3 s mean(g s) + ds with g = dy w: the gradient of x and of res alike. ds2d (may be
+    None) is the gradient arriving on the sum output; dw (fp32, may be None) += sum over rows of dy s rstd,
+    through per-wave partials folded in a fixed order: the same bits every run."""
+    rows, d = s2d.shape
+    if native(s2d):
+        dx = torch.empty_like(s2d)
+        ws = None
+        if dw is not None:
+            ws = torch.empty(add_rmsnorm_bwd_waves(rows, d, s2d.element_size()) * d, device=s2d.device,
+                             dtype=torch.float32)
+        ext().add_rmsnorm_bwd(s2d, w, rstd, dy2d, ds2d, dx, dw, ws, rows, d)
+        return dx
+    sf, dyf, r = s2d.float(), dy2d.float(), rstd[:, None]
+    g = dyf * w.float()
+    dx = r * g - (r ** 3) * sf * (g * sf).sum(-1, keepdim=True) / d
+    if ds2d is not None:
+        dx = dx + ds2d.float()
+    if dw is not None:
+        dw.add_((dyf * sf * r).sum(0))
+    return dx.to(s2d.dtype)
+
+
 # ------------------------------------------------------------------ mixture of experts (moe.hip)
 MOE_MAX_EXPERTS = 64
 

@@ -4,7 +4,10 @@ RMSNorm -> MLP -> residual; a final RMSNorm and a vocabulary projection with sof
 through the rotation of the query and key heads alone (ops/attention.py, `rotary`). The MLP is
 `DecoderConfig.mlp`: "gelu" (two dense layers, the default), or the gated FFN of those models,
 down(act(gate(x)) * up(x)) without biases (FFModel.gated_ffn): "swiglu" (silu) or "geglu" (gelu_tanh),
-with `fused_gate_up` the gate and up projections as one GEMM.
+with `fused_gate_up` the gate and up projections as one GEMM. With `fused_norm` every residual add is built
+together with the norm behind it as one `add_rms_norm` layer (FFModel.add_rms_norm) that carries the norm's
+name, so the weights, their initial values and their checkpoint keys (core/layer.py weight_slots) are those
+of the unfused model.
 """
 from __future__ import annotations
 
@@ -27,6 +30,7 @@ class DecoderConfig:
     mlp: str = "gelu"  # "gelu" | "swiglu" | "geglu"
     fused_gate_up: bool = False  # gated MLPs: gate and up as one dense of 2 * ffn outputs
     sliding_window: int = 0  # HuggingFace's convention: every query sees that many keys, itself included; 0: all
+    fused_norm: bool = False  # each residual add and the RMSNorm behind it as one add_rms_norm layer
 
     @staticmethod
     def tiny(seq=32):
@@ -51,21 +55,28 @@ def build_rope_decoder(ff, batch: int, cfg: DecoderConfig, segment_ids=None, pos
     window = (cfg.sliding_window - 1, 0) if cfg.sliding_window else None
     ids = ff.create_tensor([batch, S], DataType.DT_INT32, name="input_ids")
     x = ff.embedding(ids, cfg.vocab, H, AggrMode.AGGR_MODE_NONE, name="tok_emb")
+
+    def residual_norm(branch, x, add_name, norm_name):
+        """(stream, normed): the branch added into the stream x and the norm of the sum, as two layers or,
+        fused_norm, as one under the norm's name."""
+        if cfg.fused_norm:
+            return ff.add_rms_norm(branch, x, name=norm_name)
+        x = ff.add(branch, x, name=add_name)
+        return x, ff.rms_norm(x, name=norm_name)
+
+    n = ff.rms_norm(x, name="l0_norm1")
     for l in range(cfg.layers):
-        n = ff.rms_norm(x, name=f"l{l}_norm1")
         a = ff.multihead_attention(n, n, n, H, cfg.heads, bias=False, causal=True, name=f"l{l}_attn",
                                    num_kv_heads=cfg.kv_heads, segment_ids=segment_ids, rotary=rotary,
                                    rope_position_ids=position_ids, window=window)
-        x = ff.add(a, x, name=f"l{l}_res1")
-        n = ff.rms_norm(x, name=f"l{l}_norm2")
+        x, n = residual_norm(a, x, f"l{l}_res1", f"l{l}_norm2")
         if cfg.mlp == "gelu":
             h = ff.dense(n, cfg.ffn, ActiMode.AC_MODE_GELU, name=f"l{l}_ffn1")
             h = ff.dense(h, H, name=f"l{l}_ffn2")
         else:
             h = ff.gated_ffn(n, cfg.ffn, H, activation=GATED_MLPS[cfg.mlp], fused_gate_up=cfg.fused_gate_up,
                              name=f"l{l}_ffn")
-        x = ff.add(h, x, name=f"l{l}_res2")
-    x = ff.rms_norm(x, name="final_norm")
-    t = ff.dense(x, cfg.vocab, use_bias=False, name="lm_head")
+        x, n = residual_norm(h, x, f"l{l}_res2", f"l{l + 1}_norm1" if l + 1 < cfg.layers else "final_norm")
+    t = ff.dense(n, cfg.vocab, use_bias=False, name="lm_head")
     out = ff.softmax(t, name="lm_softmax")
     return ids, out

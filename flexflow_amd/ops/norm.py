@@ -11,6 +11,10 @@ semantics (csrc/kernels/cnn.hip).
 RMSNorm (extension: the T5 / LLaMA "LayerNorm" without centering, which the HuggingFace import
 path of the torch frontend meets) normalises the last dimension: y = x * rsqrt(mean(x^2) + eps) * w
 (csrc/kernels/norm.hip).
+
+AddRMSNorm (extension: the pre-norm decoder's residual add and the norm behind it as one op) takes x and a
+residual and returns (sum, normed): sum = x + residual in the tensors' dtype, normed = RMSNorm(sum). The sum
+is an output because the residual stream has a second reader, the next block (csrc/kernels/add_rmsnorm.hip).
 """
 from __future__ import annotations
 
@@ -175,3 +179,59 @@ class RMSNorm(OpImpl):
 
     def flops(self, in_shapes, out_shapes, w_shapes):
         return 5.0 * math.prod(out_shapes[0])
+
+
+@register(OperatorType.OP_ADD_RMS_NORM)
+class AddRMSNorm(OpImpl):
+    op_type = OperatorType.OP_ADD_RMS_NORM
+
+    def saves_output(self):
+        return False  # the sum it saves is its own first output, which no consumer overwrites (two outputs)
+
+    @classmethod
+    def infer(cls, attrs, in_dims, in_dtypes):
+        if len(in_dims) != 2 or tuple(in_dims[0]) != tuple(in_dims[1]):
+            raise ValueError(f"add_rms_norm: x and residual must have one shape, got {[tuple(d) for d in in_dims]}")
+        if in_dtypes[0] != in_dtypes[1]:
+            raise ValueError(f"add_rms_norm: x and residual must have one data type, got {in_dtypes}")
+        d = in_dims[0]
+        from ..core.initializers import ConstantInitializer
+        return [d, d], [in_dtypes[0]] * 2, [WeightSpec("weight", (d[-1],), in_dtypes[0], ConstantInitializer(1.0))]
+
+    def axis_kinds(self):
+        kinds = super().axis_kinds()
+        kinds[-1] = "none"
+        return kinds
+
+    def supports_axis(self, axis):
+        return axis != len(self.layer.outputs[0].dims) - 1
+
+    def output_maps(self):
+        return [tuple(range(len(o.dims))) for o in self.layer.outputs]
+
+    def weight_maps(self):
+        return [(None,)]
+
+    def forward(self, ctx, xs, ws):
+        x, res = xs[0].contiguous(), xs[1].contiguous()
+        d = x.shape[-1]
+        s, y, rstd = K.add_rmsnorm_fwd(x.reshape(-1, d), res.reshape(-1, d), ws[0].reshape(-1),
+                                       float(self.attrs.get("eps", 1e-6)))
+        if ctx.training:
+            ctx.saved.update(s=s, w=ws[0].reshape(-1), rstd=rstd)
+        return [s.reshape(x.shape), y.reshape(x.shape)]
+
+    def backward(self, ctx, douts):
+        sv = ctx.saved
+        s, w, rstd = sv.pop("s"), sv.pop("w"), sv.pop("rstd")
+        ds, dy = douts[0], douts[1]
+        if dy is None:  # only the sum was read: the op was an add
+            return [ds, ds]
+        dw = ctx.wgrads[0].reshape(-1) if ctx.wgrads else None
+        dx = K.add_rmsnorm_bwd(s, w, rstd, dy.reshape(s.shape).contiguous(),
+                               ds.reshape(s.shape).contiguous() if ds is not None else None, dw)
+        dx = dx.reshape(dy.shape)
+        return [dx, dx]
+
+    def flops(self, in_shapes, out_shapes, w_shapes):
+        return 6.0 * math.prod(out_shapes[0])

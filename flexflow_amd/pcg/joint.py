@@ -49,10 +49,10 @@ def snapshot(model):
 def stamp_init_slots(model):
     """Record each weight's (layer position, slot) in the graph as written: the seed of its default
     initializer. Rewrites move layers, and a rewritten graph must initialise like the original."""
-    for li, L in enumerate(model.layers):
-        for i, w in enumerate(L.weights):
-            if getattr(w, "_init_slot", None) is None:
-                w._init_slot = (li, i)
+    from ..core.layer import weight_slots
+    for w, slot in weight_slots(model.layers):
+        if getattr(w, "_init_slot", None) is None:
+            w._init_slot = slot
 
 
 def restore(model, snap):

@@ -21,11 +21,15 @@ from safetensors.torch import load_file, save_file
 
 
 def _weight_keys(model):
-    """Sharding- and arena-order-independent identity of every weight: (layer position, slot)."""
+    """Sharding- and arena-order-independent identity of every weight: (layer position, slot), with the
+    positions of core/layer.py weight_slots (a fused add_rms_norm layer counts as the two layers it stands
+    for, so the decoder with and without fused_norm keys its weights alike)."""
+    from ..core.layer import weight_slots
     keys = {}
-    for li, L in enumerate(model.layers):
-        for i, w in enumerate(L.weights):
-            keys.setdefault(w.guid, f"{li}:{i}")
+    for w, (pos, i) in weight_slots(model.layers):
+        keys.setdefault(w.guid, f"{pos}:{i}")
+    if len(set(keys.values())) != len(keys):
+        raise ValueError("checkpoint: two weights share one key")
     return keys
 
 

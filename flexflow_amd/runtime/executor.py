@@ -319,11 +319,16 @@ class Executor:
         layers, the reference's Op.init)."""
         from ..core.initializers import BlockInitializer, default_initializer
 
-        def resolve(w, li=None, i=None):
-            # model-local seed (layer position, weight slot): identical in every process and
-            # independent of how many models were built before. Graph rewrites stamp the slot of
-            # the graph as written (w._init_slot) so that rewritten graphs initialise identically.
-            slot = getattr(w, "_init_slot", None) or (li, i)
+        from ..core.layer import weight_slots
+        slots = {}
+        for w, slot in weight_slots(self.layers):
+            slots.setdefault(w.guid, slot)
+
+        def resolve(w):
+            # model-local seed (layer position, weight slot; core/layer.py weight_slots): identical in
+            # every process and independent of how many models were built before. Graph rewrites stamp
+            # the slot of the graph as written (w._init_slot) so that rewritten graphs initialise identically.
+            slot = getattr(w, "_init_slot", None) or slots[w.guid]
             seed = seed_base + 1009 * slot[0] + slot[1]
             init = w.initializer or default_initializer(getattr(w, "short_name", w.name), seed)
             if getattr(init, "seed", 0) is None:  # an explicit initializer asking for the model-local seed
@@ -335,16 +340,16 @@ class Executor:
             return init
 
         done = set()
-        for li, L in enumerate(self.layers):
+        for L in self.layers:
             if only is not None and L not in only:
                 continue
-            for i, w in enumerate(L.weights):
+            for w in L.weights:
                 if w.guid not in self.weight_loc or w.guid in done:
                     continue
                 done.add(w.guid)
                 ar, idx = self.weight_loc[w.guid]
                 m, _, c = ar.views(idx)
-                init = resolve(w, li, i)
+                init = resolve(w)
                 full = torch.empty(w.dims, dtype=torch.float32, device=self.device)
                 init.fill_full(full, w.dims)
                 wl = self.weight_layout[w.guid]
