@@ -940,6 +940,113 @@ void rope(Tensor q, Tensor q_out, std::vector<int64_t> qs, int64_t Hq, int64_t S
   ffk::rope(a, cur_stream());
 }
 
+// QK-norm fused with rotary (ops.h QkNormArgs). Every tensor is a flat buffer read as [B][H][S][D] through
+// (batch, head, row) element strides, one set for the pre-norm heads x and one for y (forward: the
+// output; backward: dz in, dx out). qt / kt: [x, y, w, rstd(, dw)] of the query and (optional) key side.
+int64_t qk_norm_groups(int64_t tokens, int64_t H0, int64_t H1, int64_t D) {
+  return ffk::qk_norm_groups(tokens, (int)H0, (int)H1, (int)D);
+}
+static void qk_norm_rope_run(bool bwd, Tensor xq, Tensor yq, std::vector<int64_t> xqs, std::vector<int64_t> yqs, int64_t Hq,
+                             int64_t Sq, Tensor wq, Tensor rq, optional<Tensor> dwq, optional<Tensor> xk,
+                             optional<Tensor> yk, std::vector<int64_t> xks, std::vector<int64_t> yks, int64_t Hk, int64_t Sk,
+                             optional<Tensor> wk, optional<Tensor> rk, optional<Tensor> dwk, int64_t B, int64_t D,
+                             int64_t rd, double eps, optional<Tensor> table, optional<Tensor> pos, bool interleaved,
+                             optional<Tensor> slab) {
+  const char* fn = bwd ? "qk_norm_rope_bwd" : "qk_norm_rope_fwd";
+  check_dev(xq, "q");
+  const bool has_k = xk.has_value() && xk->defined();
+  TORCH_CHECK(D >= 2 && D % 2 == 0 && D <= 256, fn, ": the head dim (", D, ") must be even and in [2, 256]");
+  TORCH_CHECK(rd >= 0 && rd % 2 == 0 && rd <= D, fn, ": the rotated width (", rd, ") must be even and in [0, ", D, "]");
+  TORCH_CHECK(B >= 0 && B < (1ll << 31), fn, ": extents out of range");
+  TORCH_CHECK(bwd || (eps > 0 && std::isfinite(eps)), fn, ": eps must be positive");
+  ffk::QkNormArgs a;
+  a.dt = dtcode(xq);
+  a.B = (int)B, a.D = (int)D, a.rd = (int)rd, a.eps = (float)eps, a.interleaved = interleaved;
+  if (rd > 0) {
+    TORCH_CHECK(table.has_value() && table->defined() && table->scalar_type() == at::kFloat && table->is_contiguous() &&
+                    table->dim() == 3 && table->size(0) >= 1 && table->size(0) < (1ll << 31) && table->size(1) == rd / 2 &&
+                    table->size(2) == 2 && table->device() == xq.device(),
+                fn, ": table must be a contiguous fp32 [max_positions, ", rd / 2, ", 2] tensor on q's device");
+    a.table = table->data_ptr<float>();
+    a.max_pos = (int)table->size(0);
+  }
+  a.wdt = wq.scalar_type() == at::kFloat ? ffk::DT_F32 : ffk::DT_BF16;
+  int64_t smax = Sq;
+  auto set = [&](ffk::QkNormTensor& t, const Tensor& x, const Tensor& y, const std::vector<int64_t>& xs,
+                 const std::vector<int64_t>& ys, int64_t H, int64_t S, const Tensor& w, const Tensor& rstd,
+                 const optional<Tensor>& dw, const char* what) {
+    TORCH_CHECK(xs.size() == 3 && ys.size() == 3, fn, ": ", what, " takes 3 + 3 strides");
+    for (int i = 0; i < 3; ++i) TORCH_CHECK(xs[i] >= 0 && ys[i] >= 0, fn, ": ", what, " strides must be >= 0");
+    TORCH_CHECK(H >= 0 && S >= 0 && H < (1ll << 31) && S < (1ll << 31), fn, ": ", what, " extents out of range");
+    TORCH_CHECK(y.is_cuda() && y.device() == xq.device() && x.device() == xq.device() &&
+                    x.scalar_type() == xq.scalar_type() && y.scalar_type() == xq.scalar_type(),
+                fn, ": ", what, " buffers must share q's device and dtype");
+    TORCH_CHECK(x.is_contiguous() && y.is_contiguous(), fn, ": ", what, " buffers must be contiguous (flat)");
+    TORCH_CHECK(bwd || x.data_ptr() != y.data_ptr(), fn, ": ", what, " the forward is out of place");
+    if (B > 0 && H > 0 && S > 0) {  // the last element any lane touches lies inside both buffers
+      const int64_t nx = (B - 1) * xs[0] + (H - 1) * xs[1] + (S - 1) * xs[2] + D;
+      const int64_t ny = (B - 1) * ys[0] + (H - 1) * ys[1] + (S - 1) * ys[2] + D;
+      TORCH_CHECK(x.numel() >= nx && y.numel() >= ny, fn, ": ", what, " buffers hold ", x.numel(), " / ", y.numel(),
+                  " elements, the strides reach ", nx, " / ", ny);
+    }
+    TORCH_CHECK(w.device() == xq.device() && w.is_contiguous() && w.numel() == D && w.scalar_type() == wq.scalar_type() &&
+                    (w.scalar_type() == at::kFloat || w.scalar_type() == at::kBFloat16),
+                fn, ": ", what, " weight must be a contiguous fp32 or bf16 [", D, "] tensor, both of one dtype");
+    TORCH_CHECK(rstd.device() == xq.device() && rstd.scalar_type() == at::kFloat && rstd.is_contiguous() &&
+                    rstd.numel() >= B * S * H,
+                fn, ": ", what, " rstd must be a contiguous fp32 [B, S, H] tensor");
+    t.x = x.data_ptr(), t.y = y.data_ptr();
+    t.xsb = xs[0], t.xsh = xs[1], t.xss = xs[2], t.ysb = ys[0], t.ysh = ys[1], t.yss = ys[2];
+    t.H = (int)H, t.S = (int)S;
+    t.w = w.data_ptr(), t.rstd = rstd.data_ptr<float>();
+    if (dw.has_value() && dw->defined()) {
+      TORCH_CHECK(bwd && dw->device() == xq.device() && dw->scalar_type() == at::kFloat && dw->is_contiguous() &&
+                      dw->numel() == D,
+                  fn, ": ", what, " dw must be a contiguous fp32 [", D, "] tensor");
+      t.dw = dw->data_ptr<float>();
+    }
+  };
+  set(a.t[0], xq, yq, xqs, yqs, Hq, Sq, wq, rq, dwq, "q");
+  if (has_k) {
+    TORCH_CHECK(yk.has_value() && yk->defined() && wk.has_value() && wk->defined() && rk.has_value() && rk->defined(),
+                fn, ": k needs its output, weight and rstd");
+    set(a.t[1], *xk, *yk, xks, yks, Hk, Sk, *wk, *rk, dwk, "k");
+    a.nt = 2;
+    smax = std::max(Sq, Sk);
+  }
+  if (pos.has_value() && pos->defined()) {
+    TORCH_CHECK(rd > 0, fn, ": position ids need a rotated width");
+    TORCH_CHECK(!has_k || Sq == Sk, fn, ": position ids need equal query and key lengths, got ", Sq, " and ", Sk);
+    TORCH_CHECK(pos->scalar_type() == at::kInt && pos->is_contiguous() && pos->numel() == B * Sq && pos->device() == xq.device(),
+                fn, ": position ids must be a contiguous int32 [B, S] tensor on q's device");
+    a.pos = pos->data_ptr<int>();
+  }
+  if (a.t[0].dw || a.t[1].dw) {
+    const int64_t need = 2 * (int64_t)ffk::qk_norm_groups(B * smax, a.t[0].H, a.nt > 1 ? a.t[1].H : 0, (int)D) * D;
+    TORCH_CHECK(slab.has_value() && slab->defined() && slab->device() == xq.device() && slab->scalar_type() == at::kFloat &&
+                    slab->is_contiguous() && slab->numel() >= need,
+                fn, ": dw needs an fp32 workspace of 2 * qk_norm_groups(...) * D = ", need, " floats");
+    a.slab = slab->data_ptr<float>();
+  }
+  if (bwd) ffk::qk_norm_rope_bwd(a, cur_stream());
+  else ffk::qk_norm_rope_fwd(a, cur_stream());
+}
+void qk_norm_rope_fwd(Tensor xq, Tensor yq, std::vector<int64_t> xqs, std::vector<int64_t> yqs, int64_t Hq, int64_t Sq,
+                      Tensor wq, Tensor rq, optional<Tensor> xk, optional<Tensor> yk, std::vector<int64_t> xks,
+                      std::vector<int64_t> yks, int64_t Hk, int64_t Sk, optional<Tensor> wk, optional<Tensor> rk, int64_t B,
+                      int64_t D, int64_t rd, double eps, optional<Tensor> table, optional<Tensor> pos, bool interleaved) {
+  qk_norm_rope_run(false, xq, yq, xqs, yqs, Hq, Sq, wq, rq, {}, xk, yk, xks, yks, Hk, Sk, wk, rk, {}, B, D, rd, eps, table,
+                   pos, interleaved, {});
+}
+void qk_norm_rope_bwd(Tensor xq, Tensor gq, std::vector<int64_t> xqs, std::vector<int64_t> gqs, int64_t Hq, int64_t Sq,
+                      Tensor wq, Tensor rq, optional<Tensor> dwq, optional<Tensor> xk, optional<Tensor> gk,
+                      std::vector<int64_t> xks, std::vector<int64_t> gks, int64_t Hk, int64_t Sk, optional<Tensor> wk,
+                      optional<Tensor> rk, optional<Tensor> dwk, int64_t B, int64_t D, int64_t rd, optional<Tensor> table,
+                      optional<Tensor> pos, bool interleaved, optional<Tensor> slab) {
+  qk_norm_rope_run(true, xq, gq, xqs, gqs, Hq, Sq, wq, rq, dwq, xk, gk, xks, gks, Hk, Sk, wk, rk, dwk, B, D, rd, 1.0, table,
+                   pos, interleaved, slab);
+}
+
 // Gated linear units (ops.h GluArgs): every tensor is a [rows, F] view with a contiguous last dim and
 // its own row stride (two tensors, the halves of a packed [rows, 2F] buffer, views into wider ones).
 int64_t glu_row_stride(const Tensor& t, const Tensor& g, bool output, const char* fn, const char* name) {
@@ -1545,6 +1652,16 @@ PYBIND11_MODULE(_C, m) {
   m.def("rope", &rope, py::arg("q"), py::arg("q_out"), py::arg("qs"), py::arg("Hq"), py::arg("Sq"), py::arg("k"),
         py::arg("k_out"), py::arg("ks"), py::arg("Hk"), py::arg("Sk"), py::arg("B"), py::arg("D"), py::arg("rd"),
         py::arg("table"), py::arg("pos") = py::none(), py::arg("interleaved") = false, py::arg("inverse") = false);
+  m.def("qk_norm_groups", &qk_norm_groups);
+  m.def("qk_norm_rope_fwd", &qk_norm_rope_fwd, py::arg("xq"), py::arg("yq"), py::arg("xqs"), py::arg("yqs"), py::arg("Hq"),
+        py::arg("Sq"), py::arg("wq"), py::arg("rq"), py::arg("xk"), py::arg("yk"), py::arg("xks"), py::arg("yks"),
+        py::arg("Hk"), py::arg("Sk"), py::arg("wk"), py::arg("rk"), py::arg("B"), py::arg("D"), py::arg("rd"),
+        py::arg("eps"), py::arg("table") = py::none(), py::arg("pos") = py::none(), py::arg("interleaved") = false);
+  m.def("qk_norm_rope_bwd", &qk_norm_rope_bwd, py::arg("xq"), py::arg("gq"), py::arg("xqs"), py::arg("gqs"), py::arg("Hq"),
+        py::arg("Sq"), py::arg("wq"), py::arg("rq"), py::arg("dwq"), py::arg("xk"), py::arg("gk"), py::arg("xks"),
+        py::arg("gks"), py::arg("Hk"), py::arg("Sk"), py::arg("wk"), py::arg("rk"), py::arg("dwk"), py::arg("B"),
+        py::arg("D"), py::arg("rd"), py::arg("table") = py::none(), py::arg("pos") = py::none(),
+        py::arg("interleaved") = false, py::arg("slab") = py::none());
   m.def("glu_fwd", &glu_fwd, py::arg("g"), py::arg("u"), py::arg("y"), py::arg("act"), py::arg("max_blocks") = 0);
   m.def("glu_bwd", &glu_bwd, py::arg("g"), py::arg("u"), py::arg("dy"), py::arg("dg"), py::arg("du"), py::arg("act"),
         py::arg("max_blocks") = 0);

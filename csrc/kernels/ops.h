@@ -80,6 +80,43 @@ struct RopeArgs {
 };
 void rope(const RopeArgs& a, hipStream_t st);
 
+// qknorm.hip: QK-norm (per-head RMSNorm of the projected Q and K head rows) fused with the rotation
+// above, for up to two strided tensors in one launch. Each tensor is a [B][H][S][D] view with
+// contiguous D (D even, <= 256) through element strides, one set for x and one for y.
+// Forward, fp32 arithmetic with one rounding to the storage type: per head row
+//   rstd = rsqrt(mean_d(x^2) + eps),  yhat[d] = x[d] * rstd * w[d]   (w: this tensor's [D] weight),
+// then the first rd columns of the unrounded yhat rotate exactly as rope() defines (rd = 0: no
+// rotation and no table); y <- the result, rstd[b][s][h] <- rstd. x is never written and y is
+// another buffer. Backward: y holds dz, the gradient of the normed and rotated heads, and receives dx
+// in place: g = R^-1 dz, xhat = x * rstd, dw[d] += sum_rows g[d] xhat[d] (per tensor; dw may be null),
+// dx = rstd * (g w - xhat * mean_d(g w xhat)). dw goes through `slab`, an fp32 workspace of
+// 2 * qk_norm_groups(B * max S, H0, H1, D) * D floats folded in a fixed order (no atomics).
+struct QkNormTensor {
+  const void* x = nullptr;  // the pre-norm heads
+  void* y = nullptr;        // forward: out; backward: dz in, dx out
+  int64_t xsb = 0, xsh = 0, xss = 0;
+  int64_t ysb = 0, ysh = 0, yss = 0;
+  int H = 0, S = 0;
+  const void* w = nullptr;  // [D], dtype QkNormArgs::wdt
+  float* rstd = nullptr;    // [B][S][H]: written by the forward, read by the backward
+  float* dw = nullptr;      // backward: fp32 [D] accumulated into, or null
+};
+struct QkNormArgs {
+  QkNormTensor t[2];
+  int nt = 1;
+  int dt = DT_BF16, wdt = DT_BF16;
+  int B = 0, D = 0, rd = 0;
+  float eps = 1e-6f;
+  const int* pos = nullptr;      // as RopeArgs
+  const float* table = nullptr;  // as RopeArgs; null with rd = 0
+  int max_pos = 0;
+  int interleaved = 0;
+  float* slab = nullptr;  // backward, when a dw is given
+};
+void qk_norm_rope_fwd(const QkNormArgs& a, hipStream_t st);
+void qk_norm_rope_bwd(const QkNormArgs& a, hipStream_t st);
+int qk_norm_groups(int64_t tokens, int H0, int H1, int D);
+
 // glu.hip: gated linear units. y[r][c] = act(g[r][c]) * u[r][c] for r < rows, c < F, and the backward
 // dg = dy * u * act'(g), du = dy * act(g), one launch each. Every operand is addressed as base + r *
 // its own row stride (elements) + c, so g / u (and dg / du) may be two tensors, the halves of one

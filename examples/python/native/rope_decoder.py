@@ -20,7 +20,12 @@ itself included (`window=(W - 1, 0)`), with `--packed` and without.
 `--optimizer adamw --weight-decay X` trains with AdamW (decoupled weight decay X on the matrices and the
 embedding table, none on the RMSNorm gains), as the recipes of these models do; the default stays Adam.
 
+`--qk-norm` norms every query and key head before the rotation (`DecoderConfig.qk_norm`, Qwen3 / Gemma 3: a
+per-head RMSNorm with one learned weight vector for the query heads and one for the key heads), fused with
+the rotation into one launch each way; with `--packed` and without.
+
     python examples/python/native/rope_decoder.py -b 8 --iterations 20
+    python examples/python/native/rope_decoder.py --small --qk-norm --packed --iterations 8
     python examples/python/native/rope_decoder.py --small --iterations 8 --optimizer adamw --weight-decay 0.1
     python examples/python/native/rope_decoder.py --small --packed --window 8 --iterations 8
     python examples/python/native/rope_decoder.py --small --iterations 8            # CPU-sized
@@ -50,6 +55,7 @@ def top_level_task(argv=None):
     ap.add_argument("--fused-gate-up", action="store_true")
     ap.add_argument("--window", type=int, default=0)
     ap.add_argument("--fused-norm", action="store_true")
+    ap.add_argument("--qk-norm", action="store_true")
     ap.add_argument("--optimizer", choices=("adam", "adamw"), default="adam")
     ap.add_argument("--weight-decay", type=float, default=0.01)
     args, rest = ap.parse_known_args(sys.argv[1:] if argv is None else argv)
@@ -60,6 +66,7 @@ def top_level_task(argv=None):
     dc.mlp, dc.fused_gate_up = args.mlp, args.fused_gate_up
     dc.sliding_window = args.window
     dc.fused_norm = args.fused_norm
+    dc.qk_norm = args.qk_norm
     s = dc.seq
     seg = pos = None
     if args.packed:

@@ -307,8 +307,13 @@ class FFModel:
     def multihead_attention(self, query, key, value, embed_dim, num_heads, kdim=0, vdim=0, dropout=0.0, bias=True,
                             add_bias_kv=False, add_zero_attn=False, kernel_initializer=None, causal=False, name=None,
                             key_lengths=None, attn_bias=None, segment_ids=None, num_kv_heads=None, rotary=None,
-                            rope_position_ids=None, window=None):
-        """window: sliding-window (local) attention, flash-attention's window_size convention: None, an
+                            rope_position_ids=None, window=None, qk_norm=False):
+        """qk_norm: QK-norm (Qwen3, Gemma 3): False (default: the layer built as ever), True or dict(eps=1e-6).
+        Every projected query and key head row goes through an RMSNorm over its kdim columns before the
+        rotation, with the learned weights q_norm_weight (kdim,) for all query heads and k_norm_weight
+        (kdim,) for all key heads, initialised to ones and created behind the layer's other weights; one
+        fused launch per direction (ops/attention.py). It composes with everything rotary composes with.
+        window: sliding-window (local) attention, flash-attention's window_size convention: None, an
         int w (w keys on either side) or (left, right); query i sees key j iff i - left <= j <= i + right
         (and j <= i with causal, and both in one run with segment_ids). None or -1 is unbounded. A side
         >= seq - 1 is unbounded and causal drops the right side; a window that bounds nothing builds the
@@ -363,6 +368,10 @@ class FFModel:
         if attn_bias is not None:  # the last input, marked by the attribute; a graph without it is built as ever
             ins.append(attn_bias)
             kw["attn_bias"] = True
+        from .. import kernels as K
+        eps = K.qk_norm_config("multihead_attention", qk_norm)
+        if eps is not None:  # a plain, hashable attribute: the cost key sees it
+            kw["qk_norm_eps"] = eps
         return self._add(OperatorType.OP_MULTIHEAD_ATTENTION, ins, name, embed_dim=int(embed_dim),
                          num_heads=int(num_heads), kdim=int(kdim), vdim=int(vdim), dropout=float(dropout), bias=bias,
                          add_bias_kv=add_bias_kv, add_zero_attn=add_zero_attn, kernel_init=kernel_initializer,

@@ -1445,6 +1445,122 @@ def rope(q, qs, k, ks, B, H, Hkv, Sq, Sk, D, rd, table, pos=None, interleaved=Fa
         o.as_strided((B, H_, S_, D), (st[0], st[1], st[2], 1)).copy_(y)
 
 
+# ------------------------------------------------------------------ QK-norm fused with rotary (qknorm.hip)
+def qk_norm_config(what, qk_norm):
+    """`qk_norm` (False / None, True, or a dict with eps) of an attention layer, checked: the eps of the
+    per-head RMSNorm of the projected query and key heads, or None for a layer without it."""
+    if not qk_norm:
+        return None
+    cfg = {} if qk_norm is True else dict(qk_norm)
+    unknown = set(cfg) - {"eps"}
+    if unknown:
+        raise ValueError(f"{what}: unknown qk_norm keys {sorted(unknown)}")
+    eps = float(cfg.get("eps", 1e-6))
+    if not (eps > 0 and math.isfinite(eps)):
+        raise ValueError(f"{what}: qk_norm eps must be positive and finite, got {eps}")
+    return eps
+
+
+def _view_bhsd(t, st, B, H, S, D):
+    return t.as_strided((B, H, S, D), (st[0], st[1], st[2], 1), t.storage_offset())
+
+
+def qk_norm_rope_ref(x, w, eps, table=None, pos=None, rd=0, interleaved=False):
+    """Plain-torch QK-norm of x [B, H, S, D] (any strides) by the definition qknorm.hip implements, in fp32
+    with one rounding to x's dtype: per head row rstd = rsqrt(mean(x^2) + eps), y = x * rstd * w, then the
+    first rd columns of the unrounded y rotated as rope_ref does (rd = 0: none). Returns (y, rstd [B, S, H])."""
+    xf = x.float()
+    rstd = torch.rsqrt(xf.pow(2).mean(-1) + eps)  # [B, H, S]
+    y = xf * rstd[..., None] * w.float()
+    if rd:
+        y = rope_ref(y, table, pos, rd, interleaved)
+    return y.to(x.dtype), rstd.permute(0, 2, 1).contiguous()
+
+
+def qk_norm_rope_bwd_ref(x, dz, w, rstd, dw=None, table=None, pos=None, rd=0, interleaved=False):
+    """Backward of qk_norm_rope_ref: dz [B, H, S, D] the gradient of the normed and rotated heads, rstd
+    [B, S, H]. g = R^-1 dz, xhat = x * rstd, dw (fp32 [D], may be None) += sum over rows of g * xhat,
+    returns dx = rstd * (g w - xhat * mean(g w xhat)) in x's dtype."""
+    g = dz.float()
+    if rd:
+        g = rope_ref(g, table, pos, rd, interleaved, inverse=True)
+    r = rstd.permute(0, 2, 1)[..., None]
+    xh = x.float() * r
+    if dw is not None:
+        dw.add_((g * xh).sum((0, 1, 2)))
+    gw = g * w.float()
+    return (r * (gw - xh * (gw * xh).mean(-1, keepdim=True))).to(x.dtype)
+
+
+def _qk_norm_pos(pos, k, B, Sq, Sk, rd, table, dev):
+    if pos is not None:
+        if not rd:
+            raise ValueError("qk_norm_rope: position ids need a rotated width")
+        if k is not None and Sq != Sk:
+            raise ValueError(f"qk_norm_rope: position ids need Sq == Sk, got {Sq} and {Sk}")
+        if tuple(pos.shape) != (B, Sq) or pos.dtype != torch.int32:
+            raise ValueError(f"qk_norm_rope: position ids must be int32 [{B}, {Sq}], got {pos.dtype} {list(pos.shape)}")
+        if pos.device != dev or not pos.is_contiguous():
+            pos = pos.to(dev).contiguous()
+    elif rd and table.shape[0] < max(Sq, Sk if k is not None else 0):
+        raise ValueError(f"qk_norm_rope: the table holds {table.shape[0]} positions, the sequence has {max(Sq, Sk)}")
+    return pos
+
+
+@torch.no_grad()
+def qk_norm_rope(q, qs, q_out, qos, wq, k, ks, k_out, kos, wk, B, H, Hkv, Sq, Sk, D, eps, rd=0, table=None, pos=None,
+                 interleaved=False):
+    """QK-norm of the head rows of q (and of k unless it is None) and their rotation in ONE launch
+    (qknorm.hip), out of place: q / k are flat buffers read as [B, H | Hkv, Sq | Sk, D] through (batch, head,
+    row) element strides qs / ks, q_out / k_out flat buffers written through qos / kos; wq / wk the [D]
+    norm weights (fp32 or bf16). rd: rotated width (0: the norm alone), table / pos / interleaved as in
+    rope(). Returns (rstd_q [B, Sq, H], rstd_k [B, Sk, Hkv] or None), fp32. Without a native device the
+    same definition runs as qk_norm_rope_ref."""
+    pos = _qk_norm_pos(pos, k, B, Sq, Sk, rd, table, q.device)
+    if native(q):
+        rq = torch.empty(B, Sq, H, device=q.device, dtype=torch.float32)
+        rk = torch.empty(B, Sk, Hkv, device=q.device, dtype=torch.float32) if k is not None else None
+        none3 = [0, 0, 0]
+        ext().qk_norm_rope_fwd(q, q_out, list(qs), list(qos), H, Sq, wq, rq, k, k_out, list(ks) if k is not None else none3,
+                               list(kos) if k is not None else none3, Hkv, Sk, wk, rk, B, D, rd, float(eps),
+                               table if rd else None, pos, bool(interleaved))
+        return rq, rk
+    rs = []
+    for t, o, st, ost, w, H_, S_ in ((q, q_out, qs, qos, wq, H, Sq), (k, k_out, ks, kos, wk, Hkv, Sk)):
+        if t is None:
+            rs.append(None)
+            continue
+        y, r = qk_norm_rope_ref(_view_bhsd(t, st, B, H_, S_, D), w, eps, table, pos, rd, interleaved)
+        _view_bhsd(o, ost, B, H_, S_, D).copy_(y)
+        rs.append(r)
+    return rs[0], rs[1]
+
+
+@torch.no_grad()
+def qk_norm_rope_bwd(q, qs, dq, dqs, wq, rq, dwq, k, ks, dk, dks, wk, rk, dwk, B, H, Hkv, Sq, Sk, D, rd=0, table=None,
+                     pos=None, interleaved=False):
+    """Backward of qk_norm_rope in ONE launch: q / k the saved pre-norm heads, rq / rk the saved rstd; dq / dk
+    (flat, strides dqs / dks) hold the gradient of the normed and rotated heads and receive dx in place. dwq /
+    dwk (fp32 [D], may be None) are added into through per-workgroup partials folded in a fixed order: the
+    same bits every run."""
+    pos = _qk_norm_pos(pos, k, B, Sq, Sk, rd, table, q.device)
+    if native(q):
+        slab = None
+        if dwq is not None or dwk is not None:
+            groups = int(ext().qk_norm_groups(B * max(Sq, Sk if k is not None else 0), H, Hkv if k is not None else 0, D))
+            slab = torch.empty(2 * groups * D, device=q.device, dtype=torch.float32)
+        none3 = [0, 0, 0]
+        ext().qk_norm_rope_bwd(q, dq, list(qs), list(dqs), H, Sq, wq, rq, dwq, k, dk, list(ks) if k is not None else none3,
+                               list(dks) if k is not None else none3, Hkv, Sk, wk, rk, dwk, B, D, rd,
+                               table if rd else None, pos, bool(interleaved), slab)
+        return
+    for t, g, st, gst, w, r, dw, H_, S_ in ((q, dq, qs, dqs, wq, rq, dwq, H, Sq), (k, dk, ks, dks, wk, rk, dwk, Hkv, Sk)):
+        if t is None:
+            continue
+        gv = _view_bhsd(g, gst, B, H_, S_, D)
+        gv.copy_(qk_norm_rope_bwd_ref(_view_bhsd(t, st, B, H_, S_, D), gv, w, r, dw, table, pos, rd, interleaved))
+
+
 # ---------------------------------------------------------------------------- layer norm
 def layernorm_fwd(x2d, res2d, gamma, beta, eps, save_sum):
     """y = LN(x + res). Returns (y, sum_or_x, mean, rstd)."""

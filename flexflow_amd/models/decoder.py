@@ -7,7 +7,8 @@ down(act(gate(x)) * up(x)) without biases (FFModel.gated_ffn): "swiglu" (silu) o
 with `fused_gate_up` the gate and up projections as one GEMM. With `fused_norm` every residual add is built
 together with the norm behind it as one `add_rms_norm` layer (FFModel.add_rms_norm) that carries the norm's
 name, so the weights, their initial values and their checkpoint keys (core/layer.py weight_slots) are those
-of the unfused model.
+of the unfused model. With `qk_norm` every attention layer norms its query and key heads before rotating
+them (multihead_attention's `qk_norm`); a model without it has the weights and checkpoint keys it had.
 """
 from __future__ import annotations
 
@@ -31,6 +32,7 @@ class DecoderConfig:
     fused_gate_up: bool = False  # gated MLPs: gate and up as one dense of 2 * ffn outputs
     sliding_window: int = 0  # HuggingFace's convention: every query sees that many keys, itself included; 0: all
     fused_norm: bool = False  # each residual add and the RMSNorm behind it as one add_rms_norm layer
+    qk_norm: bool = False  # per-head RMSNorm of the query and key heads before the rotation (Qwen3, Gemma 3)
 
     @staticmethod
     def tiny(seq=32):
@@ -68,7 +70,7 @@ def build_rope_decoder(ff, batch: int, cfg: DecoderConfig, segment_ids=None, pos
     for l in range(cfg.layers):
         a = ff.multihead_attention(n, n, n, H, cfg.heads, bias=False, causal=True, name=f"l{l}_attn",
                                    num_kv_heads=cfg.kv_heads, segment_ids=segment_ids, rotary=rotary,
-                                   rope_position_ids=position_ids, window=window)
+                                   rope_position_ids=position_ids, window=window, qk_norm=cfg.qk_norm)
         x, n = residual_norm(a, x, f"l{l}_res1", f"l{l}_norm2")
         if cfg.mlp == "gelu":
             h = ff.dense(n, cfg.ffn, ActiMode.AC_MODE_GELU, name=f"l{l}_ffn1")

@@ -90,6 +90,21 @@ sum dq / dk columns before they are rotated back, and linear_bwd sums it instead
 gradient, are sharded with the batch and replicated over the heads axis; the rotation is per head row,
 so a shard needs nothing but its rows. The (cos, sin) table is built on the host in float64
 (kernels.rope_table) when the executor sets the layer up, outside any captured region.
+
+QK-norm (attribute `qk_norm_eps`, set by the builder's `qk_norm=`; absent otherwise, and then the attributes,
+weights, graph and every launch are what they were): every projected query and key head row goes through
+an RMSNorm over its kdim columns with a learned weight, `q_norm_weight` (kdim,) for all query heads and
+`k_norm_weight` (kdim,) for all key heads (Qwen3, Gemma 3), before the rotation. ONE launch
+(kernels.qk_norm_rope, qknorm.hip) norms and, with rotary, rotates Q and K; it takes the place of the rope
+launch. It is out of place: the projection's output (the pre-norm heads) is kept for the backward, the
+attention core reads a second buffer with the same strides (for a fused QKV projection a buffer of the
+fused shape whose V third is never touched; V is read from the projection's output). Saved: the pre-norm
+heads, the normed and rotated heads, and rstd [B, S, H] per tensor. The backward is ONE launch behind the
+attention core's (kernels.qk_norm_rope_bwd): it rotates dq / dk back, adds the two weight gradients
+(deterministic: per-workgroup partials folded in a fixed order) and writes dx over dq / dk where they
+lie; the flash kernel's fused QKV bias gradient is off, as with rotary. Both weights are created behind
+the existing ones and are replicated over the heads axis: every shard adds the gradient of its heads and
+the executor sums the shards' gradients of a replicated weight like those of data-parallel replicas.
 """
 from __future__ import annotations
 
@@ -453,6 +468,14 @@ class MultiHeadAttention(OpImpl):
         ws.append(WeightSpec("o_weight", (E, H, vd), dt, kinit))
         if attrs.get("bias", True):
             ws.append(WeightSpec("o_bias", (E,), dt, ZeroInitializer()))
+        if attrs.get("qk_norm_eps") is not None:  # behind the existing weights: their order and names stay
+            from ..core.initializers import ConstantInitializer
+            if not attrs["qk_norm_eps"] > 0:
+                raise ValueError(f"multihead_attention: qk_norm eps must be positive, got {attrs['qk_norm_eps']}")
+            if kd % 2 or kd > 256:
+                raise ValueError(f"multihead_attention: qk_norm needs an even head dim up to 256, got {kd}")
+            ws += [WeightSpec("q_norm_weight", (kd,), dt, ConstantInitializer(1.0)),
+                   WeightSpec("k_norm_weight", (kd,), dt, ConstantInitializer(1.0))]
         return [tuple(q[:-1]) + (E,)], [dt], ws
 
     # axes: 0 batch, 1 seq, 2 embed, 3 heads
@@ -496,6 +519,30 @@ class MultiHeadAttention(OpImpl):
         K.rope(qb, qs, kb, ks, B, Hl, Hkv, Sq, Sk, kd, rope[0], rope_table_of(rope, qb.device), pos=pos,
                interleaved=rope[2], inverse=inverse)
 
+    def _qk_norm(self, pos, W, fused, qv, kv, B, Hl, Hkv, Sq, Sk, kd, qs, ks):
+        """One launch that norms (and, with rotary, rotates) the Q and K head rows of qv / kv into new
+        buffers with the same strides: (q_out, k_out, rstd_q, rstd_k)."""
+        rope = rope_attrs(self.attrs)
+        if fused:  # one buffer of the fused shape, so that Q, K and their gradients keep one set of strides
+            qn = torch.empty_like(qv)
+            kn = qn[Hl * kd:]
+        else:
+            qn, kn = torch.empty_like(qv), torch.empty_like(kv)
+        rq, rk = K.qk_norm_rope(qv, qs, qn, qs, W["q_norm_weight"], kv, ks, kn, ks, W["k_norm_weight"], B, Hl, Hkv, Sq, Sk,
+                                kd, self.attrs["qk_norm_eps"], rd=rope[0] if rope else 0,
+                                table=rope_table_of(rope, qv.device) if rope else None, pos=pos,
+                                interleaved=bool(rope and rope[2]))
+        return qn, kn, rq, rk
+
+    def _qk_norm_bwd(self, s, W, dq, dk, dwq, dwk, B, Hl, Hkv, Sq, Sk, kd, qs, ks):
+        """The backward of _qk_norm in one launch: dx over dq / dk, the norm weights' gradients added."""
+        rope = rope_attrs(self.attrs)
+        xq, xk, rq, rk = s["qk_pre"]
+        K.qk_norm_rope_bwd(xq, qs, dq, qs, W["q_norm_weight"], rq, dwq, xk, ks, dk, ks, W["k_norm_weight"], rk, dwk, B, Hl,
+                           Hkv, Sq, Sk, kd, rd=rope[0] if rope else 0,
+                           table=rope_table_of(rope, dq.device) if rope else None, pos=s.get("rope_pos"),
+                           interleaved=bool(rope and rope[2]))
+
     def needs_input_grad(self, i):
         return i < 3
 
@@ -513,7 +560,7 @@ class MultiHeadAttention(OpImpl):
                 out.append((3, None))
             elif n == "o_weight":
                 out.append((None, 3, None))
-            else:  # o_bias
+            else:  # o_bias, q_norm_weight, k_norm_weight: replicated
                 out.append((None,))
         return out
 
@@ -584,7 +631,12 @@ class MultiHeadAttention(OpImpl):
             ks = [Sk * Hkv * kd, kd, Hkv * kd]
             vs = [Sk * Hkv * vd, vd, Hkv * vd]
             s.update(q=qv, k=kv, v=vv)
-        if rope is not None:  # q and k are rotated where they lie; what is saved above is the rotated heads
+        if self.attrs.get("qk_norm_eps") is not None:
+            # normed (and rotated) into new buffers the core reads; the pre-norm heads stay for the backward
+            xq, xk = qv, kv
+            qv, kv, rq, rk = self._qk_norm(pos, W, fused, xq, xk, B, Hl, Hkv, Sq, Sk, kd, qs, ks)
+            s.update(qk_pre=(xq, xk, rq, rk), qk_w=(W["q_norm_weight"], W["k_norm_weight"]), qn=qv, kn=kv)
+        elif rope is not None:  # q and k are rotated where they lie; what is saved above is the rotated heads
             self._rope(pos, False, qv, kv, B, Hl, Hkv, Sq, Sk, kd, qs, ks)
         o = torch.empty(B, Sq, Hl, vd, device=q_in.device, dtype=q_in.dtype)
         os_ = [Sq * Hl * vd, vd, Hl * vd]
@@ -603,7 +655,8 @@ class MultiHeadAttention(OpImpl):
         return [y.view(B, Sq, E)]
 
     def overwrites_wgrad(self, i):
-        return not self.layer.weights[i].short_name.endswith("bias")  # projection GEMMs use dw_beta = wb
+        n = self.layer.weights[i].short_name  # projection GEMMs use dw_beta = wb; biases and norm weights add
+        return not (n.endswith("bias") or n.endswith("norm_weight"))
 
     def _grad_index(self):
         return {w.short_name: i for i, w in enumerate(self.layer.weights)}
@@ -640,13 +693,20 @@ class MultiHeadAttention(OpImpl):
         # itself, sparing linear_bwd a pass over dqkv (bias_act_bwd + fold); never with a score bias
         # nor with rotary: the kernel would sum dq / dk columns before they are rotated back
         rope = rope_attrs(self.attrs)
-        dbq = gw("qkv_bias") if (fused and rope is None and os.environ.get("FF_ATTN_BIAS_FUSION", "1") == "1") else None
+        qkn = "qk_pre" in s
+        if qkn:  # the core ran on the normed heads
+            qv, kv = s["qn"], s["kn"]
+        dbq = gw("qkv_bias") if (fused and rope is None and not qkn and os.environ.get("FF_ATTN_BIAS_FUSION", "1") == "1") else None
         if dbq is not None and not (dbq.dtype == torch.float32 and dbq.is_contiguous()):
             dbq = None
         bias_done = attn_core_bwd(s, qv, qs, kv, ks, vv, vs, o, os_, do, os_, dq, dk, dv, B, Hl, Sq, Sk, kd, vd, scale,
                                   causal, kl, drop, s.get("sbias"), dbq.view(-1) if dbq is not None else None,
                                   seg=s.get("seg"), Hkv=s.get("Hkv"))
-        if rope is not None:  # the rotation's backward: dq / dk rotated by the negated angle, in place
+        if qkn:  # rotation and norm backward in one launch: dx over dq / dk, the norm weights' gradients
+            wq, wk = s["qk_w"]
+            self._qk_norm_bwd(s, {"q_norm_weight": wq, "k_norm_weight": wk}, dq, dk, gw("q_norm_weight"),
+                              gw("k_norm_weight"), B, Hl, s.get("Hkv") or Hl, Sq, Sk, kd, qs, ks)
+        elif rope is not None:  # the rotation's backward: dq / dk rotated by the negated angle, in place
             self._rope(s.get("rope_pos"), True, dq, dk, B, Hl, s.get("Hkv") or Hl, Sq, Sk, kd, qs, ks)
         if fused:
             dw = gw("qkv_weight")
@@ -681,11 +741,16 @@ class MultiHeadAttention(OpImpl):
     def accum_may_alias_douts(self):
         return True  # dy is consumed by the output projection before the QKV dgrad writes
 
+    def _local_heads(self, w_shapes):
+        """This part's query heads, from o_weight (E, Hl, vd): the last weight, or in front of o_bias."""
+        ws = w_shapes[:-2] if self.attrs.get("qk_norm_eps") is not None else w_shapes  # the norm weights are last
+        return ws[-2][1] if len(ws[-1]) == 1 else ws[-1][1]
+
     def flops(self, in_shapes, out_shapes, w_shapes):
         B, Sq, Eq = in_shapes[0]
         Sk = in_shapes[1][1]
         kd, vd = self.attrs["kdim"], self.attrs["vdim"]
-        Hl = w_shapes[-2][1] if len(w_shapes[-1]) == 1 else w_shapes[-1][1]
+        Hl = self._local_heads(w_shapes)
         E = self.attrs["embed_dim"]
         H = self.attrs["num_heads"]
         Hkv = Hl * (self.attrs.get("num_kv_heads") or H) // H  # this part's KV heads: the smaller K / V projections
@@ -694,7 +759,17 @@ class MultiHeadAttention(OpImpl):
         win = window_attrs(self.attrs)
         if win is not None:  # the band's pairs only (the flash kernels skip the tiles outside it)
             att = 2.0 * B * Hl * window_pairs(Sq, win, bool(self.attrs.get("causal"))) * (kd + vd)
+        if self.attrs.get("qk_norm_eps") is not None:  # squares and their sum, two scalings per element
+            att += 4.0 * B * (Sq * Hl + Sk * Hkv) * kd
         return proj + att
+
+    def mem_bytes(self, in_shapes, out_shapes, w_shapes, elem=2):
+        by = super().mem_bytes(in_shapes, out_shapes, w_shapes, elem)
+        if self.attrs.get("qk_norm_eps") is not None:  # one read and one write of the Q and K heads
+            B, Sq, _ = in_shapes[0]
+            Sk, kd, H, Hl = in_shapes[1][1], self.attrs["kdim"], self.attrs["num_heads"], self._local_heads(w_shapes)
+            by += 2.0 * elem * B * (Sq * Hl + Sk * Hl * (self.attrs.get("num_kv_heads") or H) // H) * kd
+        return by
 
     def uses_mfma(self):
         return True
