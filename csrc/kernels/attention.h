@@ -53,7 +53,7 @@ struct AttnArgs {
   // attn_bwd1b_kernel have none, so attn_bwd then leaves the fused bias gradient to the caller).
   // An element of -inf, or one so negative that sbias * log2(e) overflows fp32 (finfo.min masks),
   // removes that key; a query row with no key left gives o = 0, lse = +inf and zero gradients. +inf
-  // and NaN are the caller's problem. The score bias takes no gradient.
+  // and NaN are the caller's problem.
   const float* sbias = nullptr;
   int64_t sbias_sb = 0, sbias_sh = 0;
   // packed sequences: the run [seg_lo[b][i], seg_hi[b][i]) that position i of row b belongs to,
@@ -92,6 +92,13 @@ struct AttnArgs {
   int Hkv = 0;
   int G = 1;
   uint16_t* kv_part = nullptr;
+  // gradient of the score bias (backward only), fp32 with the shape and strides of sbias, or null
+  // (the last member: the layout the other kernels read is what it was):
+  // dsbias[bb][hb][q][k] = sum over the batch / head indices the bias broadcasts over of
+  // dS = P0 (dP' - delta), no factor scale (the bias is added behind it). Written, not added to, every
+  // element once, by attn_dbias_kernel (attn_dbias.hip), which attn_bwd launches behind its own kernels;
+  // the same bits on every run. Without sbias, or with segments, attn_bwd launches nothing and fails.
+  float* dsbias = nullptr;
 };
 
 // lo / hi [B][S] (int32) from segment ids [B][S]: a segment is a maximal run of equal ids >= 0 and
@@ -120,6 +127,9 @@ void attn_dropout_mask(uint8_t* out, int B, int H, int Sq, int Sk, int b0, int h
 
 void attn_fwd(AttnArgs a, hipStream_t st);
 bool attn_bwd(AttnArgs a, hipStream_t st);
+// the score-bias gradient a.dsbias (attn_dbias.hip) from a.lse2 / a.delta as attn_bwd_pre_kernel left
+// them; G filled in. attn_bwd calls it (D = 64 / 128, like every kernel here)
+void attn_dbias(const AttnArgs& a, hipStream_t st);
 // Hkv (0 or H: none) adds the two expanded dK / dV buffers of grouped-query attention
 int64_t attn_bwd_workspace_floats(int B, int H, int Sq, int Sk, int D, int Hkv = 0);
 int64_t attn_bwd_slab_floats(int B, int H, int Sq, int Sk, int D);  // offset of delta in the workspace

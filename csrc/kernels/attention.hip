@@ -20,6 +20,7 @@
 #include "common.h"
 #include "ops.h"
 #include "attention.h"
+#include "attn_tile.h"
 #include "attn_dropout.h"
 #include <cstdio>
 #include <type_traits>
@@ -27,87 +28,7 @@
 
 namespace ffk {
 
-constexpr float LOG2E = 1.4426950408889634f;
-constexpr float LN2 = 0.6931471805599453f;
-
-template <int D>
-__device__ __forceinline__ int aswz(int row) {
-  if (D == 64) return (((row >> 1) & 1) << 2) | ((row >> 3) & 1) | (((row >> 4) & 1) << 1);
-  else return ((row & 3) << 2) | ((row >> 2) & 3);
-}
-// byte offset of element (row, col) of a [rows][D] bf16 tile image
-template <int D>
-__device__ __forceinline__ int aoff(int row, int col) {
-  const int ch = col >> 3;
-  return row * (D * 2) + ((ch ^ aswz<D>(row)) << 4) + ((col & 7) << 1);
-}
-
-// 2^x as the bare v_exp_f32. exp2f() lowers to v_exp_f32 wrapped in a denormal range fix-up
-// (v_cmp + 2 v_cndmask + v_add + v_ldexp: six VALU ops per score element instead of one); softmax
-// probabilities below 2^-126 are irrelevant (they flush to 0, exp2(-inf) stays 0).
-__device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-
-typedef short v4s __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ bf16x4 tr_read(const char* lds, int off) {
-  v4s v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s*)(lds + off));
-  return __builtin_bit_cast(bf16x4, v);
-}
-
-// Stage a [ROWS][D] bf16 tile (rows r0.., clamp at rlim) from global (row stride ss) into regs.
-template <int D, int ROWS, int NTH>
-struct TileStage {
-  static constexpr int CH = ROWS * D / 8 / NTH;  // 16-B chunks per thread
-  uint4 r[CH];
-  __device__ __forceinline__ void load(const bf16_t* g, int64_t ss, int r0, int rlim, int tid) {
-#pragma unroll
-    for (int i = 0; i < CH; ++i) {
-      const int id = tid + i * NTH;
-      const int row = id / (D / 8), c = id % (D / 8);
-      if (r0 + row < rlim) r[i] = *reinterpret_cast<const uint4*>(g + (int64_t)(r0 + row) * ss + c * 8);
-      else r[i] = make_uint4(0, 0, 0, 0);
-    }
-  }
-  __device__ __forceinline__ void store(char* lds, int tid) {
-#pragma unroll
-    for (int i = 0; i < CH; ++i) {
-      const int id = tid + i * NTH;
-      const int row = id / (D / 8), c = id % (D / 8);
-      *reinterpret_cast<uint4*>(lds + aoff<D>(row, c * 8)) = r[i];
-    }
-  }
-  template <class F>
-  __device__ __forceinline__ void store(char* lds, int tid, F off) {  // image given by off(row, col)
-#pragma unroll
-    for (int i = 0; i < CH; ++i) {
-      const int id = tid + i * NTH;
-      const int row = id / (D / 8), c = id % (D / 8);
-      *reinterpret_cast<uint4*>(lds + off(row, c * 8)) = r[i];
-    }
-  }
-};
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-// Same [64][D] tile image as TileStage::store, written by the LDS-DMA path (buffer_load ... lds):
-// no staging registers, so the forward needs 32 fewer VGPRs (4 workgroups per CU instead of 3 at
-// D = 64). Each wave instruction fills one 1-KiB piece, lane l landing at piece + 16 l; the XOR
-// swizzle is applied on the global side (lane l of slot s fetches chunk (s % CPR) ^ aswz(row)).
-// Rows past the sequence end read as zero (buffer range check), like TileStage's clamp.
-template <int D, int NWAVES>
-__device__ __forceinline__ void dma_tile(__amdgpu_buffer_rsrc_t rs, char* lds_tile, int64_t ss, int r0, int wave,
-                                         int lane) {
-  constexpr int PIECES = 64 * D * 2 / 1024, CPR = D / 8;
-#pragma unroll
-  for (int i = 0; i < PIECES / NWAVES; ++i) {
-    const int piece = i * NWAVES + wave;
-    const int slot = piece * 64 + lane;
-    const int row = slot / CPR;
-    const int ch = (slot % CPR) ^ aswz<D>(row);
-    const int off = (int)(((int64_t)(r0 + row) * ss + ch * 8) * 2);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)(lds_tile + piece * 1024), 16, off, 0, 0, 0);
-  }
-}
+// the tile image (aswz / aoff), TileStage, dma_tile, tr_read, fast_exp2 and key_limit: attn_tile.h
 
 __device__ __forceinline__ bf16x8 cat8(bf16x4 lo, bf16x4 hi) {
   bf16x8 r;
@@ -121,16 +42,6 @@ __device__ __forceinline__ bf16x8 pack8(const f32x16& a, int base) {
 #pragma unroll
   for (int j = 0; j < 8; ++j) o[j] = (__bf16)a[base + j];
   return o;
-}
-
-// Keys of sample b that take part: clamp(key_lens[b], 0, Sk), or Sk without lengths. One scalar
-// load per workgroup (b is wave-uniform); only the MASK = true instantiations look at it.
-template <bool MASK>
-__device__ __forceinline__ int key_limit(const AttnArgs& a, int b) {
-  if constexpr (MASK) {
-    if (a.key_lens) return __builtin_amdgcn_readfirstlane(min(max(a.key_lens[b], 0), a.Sk));
-  }
-  return a.Sk;
 }
 
 // ------------------------------------------------------------------------------------ forward
@@ -816,7 +727,8 @@ __device__ __forceinline__ unsigned pack_bf2(float x, float y) {
 //  * BIAS (score bias, AttnArgs.sbias; always MASK = true): P = exp2(S*sl2 + bias*LOG2E - lse2). The
 //    lane owns one key, so the 16 bias elements of a 32-query block are 4-B loads that the lanes of
 //    a half-wave coalesce along a bias row; they are requested ahead of the block's S / dP MFMAs
-//    and predicated on key < Sk and q < Sq. The bias takes no gradient (dS is not written out).
+//    and predicated on key < Sk and q < Sq. dS is not written out here: the bias's gradient is
+//    attn_dbias_kernel's (attn_dbias.hip), launched behind this one when AttnArgs.dsbias is set.
 //  * SEG (packed sequences and sliding windows, AttnArgs.seg_lo / seg_hi and the key side seg_klo /
 //    seg_khi; always MASK = true, never BIAS): the lane tests the query index against its own key's
 //    interval, a key block runs only the query tiles whose dQ chain
@@ -2179,6 +2091,10 @@ bool attn_bwd(AttnArgs a, hipStream_t st) {
     fprintf(stderr, "attn_bwd: seg_lo / seg_hi and seg_klo / seg_khi come in pairs, the key side beside the query side; nothing launched\n");
     return false;
   }
+  if (a.dsbias && (!a.sbias || a.seg_lo)) {
+    fprintf(stderr, "attn_bwd: dsbias needs the score bias it is the gradient of, and there is none with segments; nothing launched\n");
+    return false;
+  }
   // no key-side intervals given: the relation is symmetric (runs), the key side is the query side
   if (a.seg_lo && !a.seg_klo) {
     a.seg_klo = a.seg_lo;
@@ -2253,6 +2169,8 @@ bool attn_bwd(AttnArgs a, hipStream_t st) {
   if (bias_done)
     hipLaunchKernelGGL(attn_bias_fold_kernel, dim3((unsigned)(3 * a.H)), dim3(1024), 0, st, a.dbp, a.dbias, a.B, a.H,
                        a.D, nkb);
+  // the score-bias gradient: its own kernel, behind the others on the stream (reads lse2 / delta)
+  if (a.dsbias) attn_dbias(a, st);
   return bias_done;
 }
 

@@ -1184,7 +1184,8 @@ bool attn_bwd(Tensor q, std::vector<int64_t> qs, Tensor k, std::vector<int64_t> 
               double scale, bool causal, optional<Tensor> dbias, optional<Tensor> key_lens, int64_t drop_thr,
               optional<Tensor> rng_step, int64_t rng_seed, int64_t b0, int64_t h0, int64_t H_total,
               optional<Tensor> sbias, int64_t sbias_sb, int64_t sbias_sh, optional<Tensor> seg_lo,
-              optional<Tensor> seg_hi, int64_t Hkv, optional<Tensor> seg_klo, optional<Tensor> seg_khi) {
+              optional<Tensor> seg_hi, int64_t Hkv, optional<Tensor> seg_klo, optional<Tensor> seg_khi,
+              optional<Tensor> dsbias) {
   TORCH_CHECK(D == 64 || D == 128, "flash attention supports head_dim 64/128");
   TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.numel() >= ffk::attn_bwd_workspace_floats(B, H, Sq, Sk, D, Hkv),
               "attn_bwd: workspace too small");
@@ -1219,6 +1220,16 @@ bool attn_bwd(Tensor q, std::vector<int64_t> qs, Tensor k, std::vector<int64_t> 
   attn_drop_args(a, q, drop_thr, rng_step, rng_seed, b0, h0, H_total, H);
   attn_sbias_args(a, q, sbias, sbias_sb, sbias_sh, B, H, Sq, Sk);
   attn_seg_args(a, q, seg_lo, seg_hi, B, Sq, Sk, seg_klo, seg_khi);
+  if (dsbias.has_value() && dsbias->defined()) {  // the score bias's gradient: laid out as sbias, written not added to
+    TORCH_CHECK(a.sbias != nullptr, "attn_bwd: dsbias is the gradient of sbias, which is missing");
+    TORCH_CHECK(a.seg_lo == nullptr, "attn_bwd: no score bias gradient with segments");
+    TORCH_CHECK(dsbias->scalar_type() == at::kFloat && dsbias->device() == q.device() && dsbias->dim() >= 2 &&
+                    dsbias->size(-1) == Sk && dsbias->size(-2) == Sq && dsbias->stride(-1) == 1 && dsbias->stride(-2) == Sk,
+                "attn_bwd: dsbias must be fp32 [.., Sq, Sk] with contiguous rows on the device of q");
+    TORCH_CHECK(((sbias_sb ? B : 1) - 1) * sbias_sb + ((sbias_sh ? H : 1) - 1) * sbias_sh + Sq * Sk <= dsbias->numel(),
+                "attn_bwd: dsbias is too short for the strides of sbias");
+    a.dsbias = dsbias->data_ptr<float>();
+  }
   return ffk::attn_bwd(a, cur_stream());
 }
 
@@ -1646,7 +1657,7 @@ PYBIND11_MODULE(_C, m) {
         py::arg("rng_step") = py::none(), py::arg("rng_seed") = 0, py::arg("b0") = 0, py::arg("h0") = 0,
         py::arg("H_total") = 0, py::arg("sbias") = py::none(), py::arg("sbias_sb") = 0, py::arg("sbias_sh") = 0,
         py::arg("seg_lo") = py::none(), py::arg("seg_hi") = py::none(), py::arg("Hkv") = 0,
-        py::arg("seg_klo") = py::none(), py::arg("seg_khi") = py::none());
+        py::arg("seg_klo") = py::none(), py::arg("seg_khi") = py::none(), py::arg("dsbias") = py::none());
   m.def("attn_seg_bounds", &attn_seg_bounds);
   m.def("attn_band_bounds", &attn_band_bounds);
   m.def("rope", &rope, py::arg("q"), py::arg("q_out"), py::arg("qs"), py::arg("Hq"), py::arg("Sq"), py::arg("k"),

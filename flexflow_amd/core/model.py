@@ -75,6 +75,17 @@ def _ensure_dist(config: FFConfig):
         torch.cuda.set_device(config.local_rank % torch.cuda.device_count())
 
 
+def _check_bias_grad(what, attn_bias_grad, attn_bias, segment_ids, window):
+    """attn_bias_grad=True: there must be a score bias to differentiate, and segment / window calls take none."""
+    if not attn_bias_grad:
+        return {}
+    if attn_bias is None:
+        raise ValueError(f"{what}: attn_bias_grad=True needs attn_bias")
+    if segment_ids is not None or window is not None:
+        raise ValueError(f"{what}: attn_bias_grad cannot be combined with segment_ids / window (they take no attn_bias)")
+    return {"attn_bias_grad": True}
+
+
 def _check_segment_args(what, key_lengths, attn_bias):
     if key_lengths is not None:
         raise ValueError(f"{what}: segment_ids cannot be combined with key_lengths (mark padding with a negative id)")
@@ -307,8 +318,13 @@ class FFModel:
     def multihead_attention(self, query, key, value, embed_dim, num_heads, kdim=0, vdim=0, dropout=0.0, bias=True,
                             add_bias_kv=False, add_zero_attn=False, kernel_initializer=None, causal=False, name=None,
                             key_lengths=None, attn_bias=None, segment_ids=None, num_kv_heads=None, rotary=None,
-                            rope_position_ids=None, window=None, qk_norm=False):
-        """qk_norm: QK-norm (Qwen3, Gemma 3): False (default: the layer built as ever), True or dict(eps=1e-6).
+                            rope_position_ids=None, window=None, qk_norm=False, attn_bias_grad=False):
+        """attn_bias_grad: True makes attn_bias trainable: the backward returns its gradient (dS summed over
+        the batch / head dims the bias broadcasts over, in the bias's dtype and shape), computed by a flash
+        kernel of its own behind the backward, and only when something upstream of the bias can use it.
+        False (default): the graph, the attributes and every launch are those of a call without it. Needs
+        attn_bias; not with segment_ids / window (ops/attention.py).
+        qk_norm: QK-norm (Qwen3, Gemma 3): False (default: the layer built as ever), True or dict(eps=1e-6).
         Every projected query and key head row goes through an RMSNorm over its kdim columns before the
         rotation, with the learned weights q_norm_weight (kdim,) for all query heads and k_norm_weight
         (kdim,) for all key heads, initialised to ones and created behind the layer's other weights; one
@@ -337,13 +353,14 @@ class FFModel:
         key_lengths: optional int32 tensor [batch] (or [batch, 1]) of a right-padded batch: sample b
         attends to its first key_lengths[b] keys only (ops/attention.py).
         attn_bias: optional float tensor [1|batch, 1|heads, Sq, Sk] added to the scaled scores before the
-        softmax (ALiBi, relative-position biases, 0 / -inf masks); it takes no gradient (ops/attention.py).
+        softmax (ALiBi, relative-position biases, 0 / -inf masks); it takes a gradient only with
+        attn_bias_grad=True (ops/attention.py).
         dropout: attention-probability dropout rate in [0, 1), torch's dropout_p semantics; applied in
         training forwards only, at the effective rate round(256 p) / 256 (ops/attention.py)."""
         if not 0.0 <= float(dropout) < 1.0:
             raise ValueError(f"multihead_attention: dropout must be in [0, 1), got {dropout}")
         ins = [query, key, value] + ([key_lengths] if key_lengths is not None else [])
-        kw = {}
+        kw = _check_bias_grad("multihead_attention", attn_bias_grad, attn_bias, segment_ids, window)
         if num_kv_heads is not None and int(num_kv_heads) != int(num_heads):  # else: the graph built as ever
             if int(num_kv_heads) <= 0 or int(num_heads) % int(num_kv_heads):
                 raise ValueError(f"multihead_attention: num_kv_heads ({num_kv_heads}) must divide num_heads ({num_heads})")
@@ -378,15 +395,17 @@ class FFModel:
                          causal=causal, self_attn=(query is key and key is value), **kw).outputs[0]
 
     def scaled_dot_product_attention(self, q, k, v, attn_bias=None, key_lengths=None, scale=None, causal=False,
-                                     dropout=0.0, name=None, segment_ids=None, enable_gqa=False, window=None):
+                                     dropout=0.0, name=None, segment_ids=None, enable_gqa=False, window=None,
+                                     attn_bias_grad=False):
         """softmax(scale * q.k^T + attn_bias) . v on projected heads: q [B, H, Sq, D], k [B, H, Sk, D],
         v [B, H, Sk, Dv] -> [B, H, Sq, Dv] (extension; ops/sdpa.py). attn_bias, key_lengths, causal and
-        dropout, segment_ids and window are those of multihead_attention; scale=None means 1 / sqrt(D).
+        dropout, segment_ids, window and attn_bias_grad are those of multihead_attention; scale=None means
+        1 / sqrt(D).
         enable_gqa (torch's): k and v may have Hkv heads, Hkv dividing H; query head h reads KV head
         h // (H // Hkv)."""
         if not 0.0 <= float(dropout) < 1.0:
             raise ValueError(f"scaled_dot_product_attention: dropout must be in [0, 1), got {dropout}")
-        ins, kw = [q, k, v], {}
+        ins, kw = [q, k, v], _check_bias_grad("scaled_dot_product_attention", attn_bias_grad, attn_bias, segment_ids, window)
         if key_lengths is not None:
             ins.append(key_lengths)
             kw["key_lengths"] = True

@@ -1256,8 +1256,8 @@ def attn_score_bias(bias, B, H, Sq, Sk, device):
     """The additive score bias as the kernels take it: fp32 [Bb, Hb, Sq, Sk] with Bb in {1, B} and Hb in
     {1, H}, contiguous, on `device` (cast / copied once here when it is not), or None. Scores are
     scale * q.k + bias; -inf (or anything so negative that bias * log2(e) overflows fp32, such as
-    finfo.min) removes the key, a row with no key left gives zero output and zero gradients. The bias
-    takes no gradient."""
+    finfo.min) removes the key, a row with no key left gives zero output and zero gradients. Its
+    gradient is flash_attn_bwd's / attn_f32_bwd's `dbias_out`."""
     if bias is None:
         return None
     if bias.dim() != 4 or bias.shape[0] not in (1, B) or bias.shape[1] not in (1, H) or \
@@ -1277,6 +1277,17 @@ def _sbias_kw(bias, B, H, Sq, Sk, device):
         return {}
     Bb, Hb = bias.shape[:2]
     return dict(sbias=bias, sbias_sb=Hb * Sq * Sk if Bb > 1 else 0, sbias_sh=Sq * Sk if Hb > 1 else 0)
+
+
+def _check_dbias_out(dbias_out, bias, segments):
+    """dbias_out of flash_attn_bwd / attn_f32_bwd against the score bias as the kernels take it."""
+    if bias is None or segments is not None:
+        raise ValueError("attention: dbias_out is the gradient of the score bias; it needs `bias` and there is none "
+                         "with segments / a window")
+    if dbias_out.shape != bias.shape or dbias_out.dtype != torch.float32 or dbias_out.device != bias.device or \
+            not dbias_out.is_contiguous():
+        raise ValueError(f"attention: dbias_out must be a contiguous fp32 {list(bias.shape)} tensor on the bias's "
+                         f"device, got {dbias_out.dtype} {list(dbias_out.shape)}")
 
 
 def attn_kv_heads(H, Hkv):
@@ -1306,7 +1317,7 @@ def flash_attn_fwd(q, qs, k, ks, v, vs, o, os_, B, H, Sq, Sk, D, scale, causal, 
 
 
 def flash_attn_bwd(q, qs, k, ks, v, vs, o, os_, do, dos, lse, dq, dqs, dk, dks, dv, dvs, B, H, Sq, Sk, D, scale,
-                   causal, dbias=None, key_lens=None, drop=None, bias=None, segments=None, Hkv=None):
+                   causal, dbias=None, key_lens=None, drop=None, bias=None, segments=None, Hkv=None, dbias_out=None):
     """Hkv: as in flash_attn_fwd; dk / dv and dks / dvs hold Hkv heads, each the sum over its group of
     query heads (fp32, one rounding, the same bits on every run), and the bias gradient is never fused
     (a dbias given with Hkv < H is left untouched, returns False).
@@ -1314,8 +1325,13 @@ def flash_attn_bwd(q, qs, k, ks, v, vs, o, os_, do, dos, lse, dq, dqs, dk, dks, 
     and the segment kernels never fuse the bias gradient (returns False).
     key_lens: as in flash_attn_fwd; dk / dv rows at or past a sample's length are written as zeros.
     drop: as in flash_attn_fwd, with the counter value the forward saw; the dropout kernels never fuse
-    the bias gradient (returns False). bias: the forward's score bias; it takes no gradient, and the
-    score bias kernels never fuse the (QKV projection's) bias gradient either.
+    the bias gradient (returns False). bias: the forward's score bias; the score bias kernels never
+    fuse the (QKV projection's) bias gradient either.
+    dbias_out: optional fp32 contiguous tensor of bias's shape [1|B, 1|H, Sq, Sk] that receives the
+    gradient of the SCORE bias: dS = P0 (dP' - delta), summed over the batch / head indices the bias
+    broadcasts over (attn_dbias.hip, launched behind the backward kernels; written, not added to; the
+    same bits on every run). Needs `bias`, and there is none with segments. Not to be confused with
+    `dbias`, which is the gradient of the QKV projection's bias vector:
     dbias: optional contiguous fp32 [3*H*D] bias gradient of a fused [B,S,3,H,D] QKV projection
     (dq/dk/dv inside one dqkv buffer). Returns True when the kernel added the column sums of dq / dk /
     dv into it (attn_bwd1b_kernel, non-causal); False: the caller still owes that bias gradient."""
@@ -1326,10 +1342,12 @@ def flash_attn_bwd(q, qs, k, ks, v, vs, o, os_, do, dos, lse, dq, dqs, dk, dks, 
     if Hkv < H:
         dbias = None  # laid out for [3][H][D]: the caller sums the projection biases, as with dropout
     ws = DeviceContext.get(q.device).workspace("attn_bwd", X.attn_bwd_ws(B, H, Sq, Sk, D, Hkv))
+    skw = _sbias_kw(bias, B, H, Sq, Sk, q.device)
+    if dbias_out is not None:
+        _check_dbias_out(dbias_out, skw.get("sbias"), segments)
     return bool(X.attn_bwd(q, qs, k, ks, v, vs, o, os_, do, dos, lse, dq, dqs, dk, dks, dv, dvs, ws, B, H, Sq, Sk, D,
                            scale, causal, dbias, attn_key_lens(key_lens, B, q.device), **_drop_kw(drop),
-                           **_sbias_kw(bias, B, H, Sq, Sk, q.device), **_seg_kw(segments, key_lens, bias, Sq, Sk),
-                           Hkv=Hkv))
+                           **skw, **_seg_kw(segments, key_lens, bias, Sq, Sk), Hkv=Hkv, dsbias=dbias_out))
 
 
 # ------------------------------------------------------------------ rotary position embedding (rope.hip)
@@ -3068,14 +3086,15 @@ def attn_f32_fwd(q, qs, k, ks, v, vs, o, os_, B, H, Sq, Sk, kd, vd, scale, causa
 
 
 def attn_f32_bwd(q, qs, k, ks, v, vs, do, dos, P, dq, dk, dv, B, H, Sq, Sk, kd, vd, scale, key_lens=None, drop=None,
-                 bias=None, segments=None, Hkv=None):
+                 bias=None, segments=None, Hkv=None, dbias_out=None):
     """Backward of attn_f32_fwd: dP = dO.V^T, dS = scale * P * (dP - rowsum(dP * P)), dQ = dS.K,
     dK = dS^T.Q, dV = P^T.dO (dq / dk / dv share q / k / v's strides). key_lens needs no work here:
     the forward left P = 0 in the masked columns, so dS is 0 there and the dK / dV rows at or past a
     sample's length come out as zeros (all of a length-0 sample's gradients do). drop (with the
     counter value of the forward): dP and the P of the dV GEMM go through attn_dropout_f32. bias needs
-    no work either: it is inside P, dS = scale * P * (..) stays the gradient of the raw q.k, and the
-    bias itself takes no gradient. segments need none: P is 0 outside the runs. Hkv (as in attn_f32_fwd):
+    no work either: it is inside P, dS = scale * P * (..) stays the gradient of the raw q.k. dbias_out
+    (as in flash_attn_bwd) receives the bias's own gradient: each sample's dS / scale, summed over the
+    dims the bias broadcasts over. segments need none: P is 0 outside the runs. Hkv (as in attn_f32_fwd):
     dK / dV of the H query heads go to a per-sample buffer and each group's sum to dk / dv."""
     X = ext()
     Hkv = attn_kv_heads(H, Hkv)
@@ -3084,6 +3103,9 @@ def attn_f32_bwd(q, qs, k, ks, v, vs, do, dos, P, dq, dk, dv, B, H, Sq, Sk, kd, 
         dkx = torch.empty(H, Sk, kd, device=q.device, dtype=torch.float32)
         dvx = torch.empty(H, Sk, vd, device=q.device, dtype=torch.float32)
     dkw = _drop_kw(drop)
+    if dbias_out is not None:
+        _check_dbias_out(dbias_out, attn_score_bias(bias, B, H, Sq, Sk, q.device), segments)
+        dbias_out.zero_()
     Pd = torch.empty(H, Sq, Sk, device=q.device, dtype=torch.float32) if dkw else None
     q, k, v, do = q.reshape(-1), k.reshape(-1), v.reshape(-1), do.reshape(-1)
     dq, dk, dv = dq.reshape(-1), dk.reshape(-1), dv.reshape(-1)
@@ -3102,6 +3124,9 @@ def attn_f32_bwd(q, qs, k, ks, v, vs, do, dos, P, dq, dk, dv, B, H, Sq, Sk, kd, 
             X.attn_dropout_f32(P[b], Pd, *da)
             Pb = Pd
         X.softmax_bwd(P[b], dP, dS, H * Sq, Sk, scale, False)
+        if dbias_out is not None:  # b ascending: one order of additions
+            g = dS if dbias_out.shape[1] == H else dS.sum(0, keepdim=True)
+            dbias_out[b if dbias_out.shape[0] == B else 0].add_(g, alpha=1.0 / scale)
         X.gemm_f32(dS, kb, dq[b * qs[0]:], None, None, Sq, kd, Sk, Sk, kss, qs[2], Sq * Sk, ksh,
                    qs[1], H, True, False, 1.0, 0.0, ACT_NONE)
         X.gemm_f32(dS, q[b * qs[0]:], dkb, None, None, Sk, kd, Sq, Sk, qs[2], kss, Sq * Sk, qs[1],

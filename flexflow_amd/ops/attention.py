@@ -26,8 +26,14 @@ read it as fp32 (cast once per forward when it is not) while they compute the sc
 Sq, Sk] tensor is built. An element of -inf, or one so negative that bias * log2(e) overflows fp32
 (HuggingFace's finfo.min masks), removes that key; a query row with no key left gives a zero output
 row and zero gradients (the key-length convention; torch gives NaN). +inf and NaN are the caller's
-problem. The bias takes no gradient, and with it the flash backward leaves the QKV bias gradient to
-the projection's own backward. It is sharded with the batch where its first extent is B and with the
+problem. With the bias the flash backward leaves the QKV bias gradient to the projection's own
+backward. The bias itself takes a gradient only with the attribute `attn_bias_grad=True` (learned
+relative-position tables, pair biases, ALiBi slopes): backward then returns, for the bias input, dS =
+P0 (dP' - delta) summed over the batch / head dims the bias broadcasts over, in the input's dtype and
+shape. A flash kernel of its own (csrc/kernels/attn_dbias.hip) computes it behind the backward, fp32,
+without atomics and without a [B, H, Sq, Sk] tensor, and only when the executor found a use for the
+gradient upstream (ctx.extra["in_grad"]). On a sharded batch or heads axis a broadcast extent is a
+replicated input, whose partial gradients the executor's backward transfer sums. It is sharded with the batch where its first extent is B and with the
 heads where its second is H, replicated elsewhere. The same core (attn_core_fwd / attn_core_bwd) serves
 `scaled_dot_product_attention` (ops/sdpa.py).
 
@@ -241,11 +247,12 @@ def attn_core_fwd(s, name, qv, qs, kv, ks, vv, vs, o, os_, B, Hl, Sq, Sk, kd, vd
 
 
 def attn_core_bwd(s, qv, qs, kv, ks, vv, vs, o, os_, do, dos, dq, dk, dv, B, Hl, Sq, Sk, kd, vd, scale, causal, kl, drop,
-                  bias, dbq=None, seg=None, Hkv=None):
+                  bias, dbq=None, seg=None, Hkv=None, dsb=None):
     """Backward of attn_core_fwd on the path it took: dq / dk / dv (buffers with q / k / v's strides)
     from do (strides dos) and what the forward left in `s`. dbq: the fp32 [3*H*D] bias gradient of a fused
     QKV projection the flash kernel may add into; returns whether it did. Hkv: as in attn_core_fwd; dk /
-    dv hold Hkv heads, each the sum over its group of query heads."""
+    dv hold Hkv heads, each the sum over its group of query heads. dsb: optional fp32 tensor of bias's
+    shape (as kernels.attn_score_bias returned it) that receives the gradient of the score bias."""
     Hkv = K.attn_kv_heads(Hl, Hkv)
     if "pad" in s:
         Dp, pq, pk, pv, po = s["pad"]
@@ -255,30 +262,35 @@ def attn_core_bwd(s, qv, qs, kv, ks, vv, vs, o, os_, do, dos, dq, dk, dv, B, Hl,
         pst = [Sq * Hl * Dp, Dp, Hl * Dp]
         kst = [Sk * Hkv * Dp, Dp, Hkv * Dp]
         K.flash_attn_bwd(pq, pst, pk, kst, pv, kst, po, pst, pdo, pst, s["lse"], pdq, pst, pdk, kst, pdv, kst,
-                         B, Hl, Sq, Sk, Dp, scale, causal, key_lens=kl, drop=drop, bias=bias, segments=seg, Hkv=Hkv)
+                         B, Hl, Sq, Sk, Dp, scale, causal, key_lens=kl, drop=drop, bias=bias, segments=seg, Hkv=Hkv,
+                         dbias_out=dsb)
         for g, st, pg, S_, d, H_ in ((dq, qs, pdq, Sq, kd, Hl), (dk, ks, pdk, Sk, kd, Hkv), (dv, vs, pdv, Sk, vd, Hkv)):
             _view4(g, st, B, H_, S_, d).copy_(pg[..., :d].permute(0, 2, 1, 3))
     elif "lse" in s:
         if dbq is not None and Hkv == Hl:
             return K.flash_attn_bwd(qv, qs, kv, ks, vv, vs, o, os_, do, dos, s["lse"], dq, qs, dk, ks, dv, vs,
                                     B, Hl, Sq, Sk, kd, scale, causal, dbias=dbq, key_lens=kl, drop=drop, bias=bias,
-                                    segments=seg)
+                                    segments=seg, dbias_out=dsb)
         K.flash_attn_bwd(qv, qs, kv, ks, vv, vs, o, os_, do, dos, s["lse"], dq, qs, dk, ks, dv, vs,
-                         B, Hl, Sq, Sk, kd, scale, causal, key_lens=kl, drop=drop, bias=bias, segments=seg, Hkv=Hkv)
+                         B, Hl, Sq, Sk, kd, scale, causal, key_lens=kl, drop=drop, bias=bias, segments=seg, Hkv=Hkv,
+                         dbias_out=dsb)
     elif "P" in s:
         K.attn_f32_bwd(qv, qs, kv, ks, vv, vs, do.contiguous().view(-1), dos, s["P"], dq.view(-1), dk.view(-1),
                        dv.view(-1), B, Hl, Sq, Sk, kd, vd, scale, key_lens=kl, drop=drop, bias=bias, segments=seg,
-                       Hkv=Hkv)
+                       Hkv=Hkv, dbias_out=dsb)
     else:
         q4 = _view4(qv, qs, B, Hl, Sq, kd).detach().float().requires_grad_()
         k4 = _view4(kv, ks, B, Hkv, Sk, kd).detach().float().requires_grad_()
         v4 = _view4(vv, vs, B, Hkv, Sk, vd).detach().float().requires_grad_()
+        b4 = bias.detach().float().requires_grad_() if dsb is not None else bias  # the bias as a leaf
         with torch.enable_grad():
             out = _attn_ref(q4, _repeat_kv(k4, Hl // Hkv), _repeat_kv(v4, Hl // Hkv), scale, causal, kl, s.get("keep"),
-                            256.0 / (256 - drop[0]) if drop else 1.0, bias, seg[0] if seg is not None else None,
+                            256.0 / (256 - drop[0]) if drop else 1.0, b4, seg[0] if seg is not None else None,
                             seg.window if seg is not None else None)
         g4 = _view4(do, dos, B, Hl, Sq, vd).float()
-        gq, gk, gv = torch.autograd.grad(out, (q4, k4, v4), g4)
+        gq, gk, gv, *gb = torch.autograd.grad(out, (q4, k4, v4) + ((b4,) if dsb is not None else ()), g4)
+        if dsb is not None:
+            dsb.copy_(gb[0])
         _view4(dq, qs, B, Hl, Sq, kd).copy_(gq)
         _view4(dk, ks, B, Hkv, Sk, kd).copy_(gk)
         _view4(dv, vs, B, Hkv, Sk, vd).copy_(gv)
@@ -390,6 +402,28 @@ def check_rope_ids_dims(what, dims, dtype, B, Sq, Sk):
         raise ValueError(f"{what}: rope_position_ids must be an int32 tensor, got {dtype}")
 
 
+def check_attn_bias_grad(what, attrs):
+    """attn_bias_grad=True needs a score bias to differentiate, and the segment / window kernels take none."""
+    if not attrs.get("attn_bias_grad"):
+        return
+    if not attrs.get("attn_bias"):
+        raise ValueError(f"{what}: attn_bias_grad=True needs attn_bias")
+    if attrs.get("segment_ids") or window_attrs(attrs) is not None:
+        raise ValueError(f"{what}: attn_bias_grad cannot be combined with segment_ids / window (they take no attn_bias)")
+
+
+def attn_bias_grad_out(impl, ctx, bias):
+    """The fp32 buffer attn_core_bwd fills with the score bias's gradient (the shape of `bias` as the
+    kernels took it: this part's [1|B, 1|H, Sq, Sk]), or None: the attribute is off, or the executor found
+    nothing upstream that can use the gradient (ctx.extra["in_grad"], one flag per input, as need_dx0)."""
+    if not impl.attrs.get("attn_bias_grad") or bias is None:
+        return None
+    used = ctx.extra.get("in_grad")
+    if used is not None and not used[len(impl.layer.inputs) - 1]:
+        return None
+    return torch.empty_like(bias)
+
+
 def attn_bias_map(dims, B, H, batch_axis, heads_axis):
     """input_maps entry of a score bias: with the batch where its first extent is B, with the heads
     where its second is H, replicated elsewhere."""
@@ -404,6 +438,7 @@ class MultiHeadAttention(OpImpl):
     def infer(cls, attrs, in_dims, in_dtypes):
         nb = 1 if attrs.get("attn_bias") else 0
         nr = 1 if attrs.get("rope_positions") else 0
+        check_attn_bias_grad("multihead_attention", attrs)
         if len(in_dims) - nb - nr not in (3, 4):
             raise ValueError("multihead_attention takes query, key, value[, key_lengths][, rope_position_ids]"
                              f"[, attn_bias]; got {len(in_dims)} inputs" + (" with attn_bias=True" if nb else "")
@@ -544,7 +579,7 @@ class MultiHeadAttention(OpImpl):
                            interleaved=bool(rope and rope[2]))
 
     def needs_input_grad(self, i):
-        return i < 3
+        return i < 3 or bool(self.attrs.get("attn_bias_grad") and i == len(self.layer.inputs) - 1)
 
     def weight_maps(self):
         out = []
@@ -651,7 +686,7 @@ class MultiHeadAttention(OpImpl):
         if ctx.training:
             s.update(o=o, wo=wo, has_bo=bo is not None, shape=(B, Sq, Sk, Hl, kd, vd, E), fused=fused,
                      qs=qs, ks=ks, vs=vs, os=os_, scale=scale, causal=causal, key_lens=kl, drop=drop, sbias=bias,
-                     seg=seg, Hkv=Hkv, rope_pos=pos)
+                     seg=seg, Hkv=Hkv, rope_pos=pos, sbias_dtype=xs[-1].dtype if has_bias else None)
         return [y.view(B, Sq, E)]
 
     def overwrites_wgrad(self, i):
@@ -680,7 +715,9 @@ class MultiHeadAttention(OpImpl):
         fused = s["fused"]
         kl = s["key_lens"]
         drop = s["drop"]  # the counter is read on the device again: the next forward advances it, not this backward
-        no_kl_grad = [None] * (len(self.layer.inputs) - 3)  # the lengths and the score bias take no gradient
+        # the lengths take no gradient; the score bias (the last input) only with attn_bias_grad
+        no_kl_grad = [None] * (len(self.layer.inputs) - 3)
+        dsb = attn_bias_grad_out(self, ctx, s.get("sbias"))
         if fused:
             qkv = s["qkv"]
             qv, kv, vv = qkv.view(-1), qkv.view(-1)[Hl * kd:], qkv.view(-1)[2 * Hl * kd:]
@@ -701,7 +738,9 @@ class MultiHeadAttention(OpImpl):
             dbq = None
         bias_done = attn_core_bwd(s, qv, qs, kv, ks, vv, vs, o, os_, do, os_, dq, dk, dv, B, Hl, Sq, Sk, kd, vd, scale,
                                   causal, kl, drop, s.get("sbias"), dbq.view(-1) if dbq is not None else None,
-                                  seg=s.get("seg"), Hkv=s.get("Hkv"))
+                                  seg=s.get("seg"), Hkv=s.get("Hkv"), dsb=dsb)
+        if dsb is not None:
+            no_kl_grad[-1] = dsb.to(s["sbias_dtype"])
         if qkn:  # rotation and norm backward in one launch: dx over dq / dk, the norm weights' gradients
             wq, wk = s["qk_w"]
             self._qk_norm_bwd(s, {"q_norm_weight": wq, "k_norm_weight": wk}, dq, dk, gw("q_norm_weight"),
@@ -761,6 +800,8 @@ class MultiHeadAttention(OpImpl):
             att = 2.0 * B * Hl * window_pairs(Sq, win, bool(self.attrs.get("causal"))) * (kd + vd)
         if self.attrs.get("qk_norm_eps") is not None:  # squares and their sum, two scalings per element
             att += 4.0 * B * (Sq * Hl + Sk * Hkv) * kd
+        if self.attrs.get("attn_bias_grad"):  # the score-bias gradient recomputes S and dP in the backward
+            att += 2.0 * B * Hl * Sq * Sk * (kd + vd)
         return proj + att
 
     def mem_bytes(self, in_shapes, out_shapes, w_shapes, elem=2):

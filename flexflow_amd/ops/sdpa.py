@@ -5,7 +5,9 @@ out[b, h] = softmax(scale * q[b, h] . k[b, h]^T + attn_bias[b, h], masks) . v[b,
 k [B, H, Sk, D], v [B, H, Sk, Dv] -> [B, H, Sq, Dv]. No weights. Inputs after q, k, v: `key_lengths`
 (attribute `key_lengths=True`; int32 [B] or [B, 1]) and then `attn_bias` (attribute `attn_bias=True`;
 float [1|B, 1|H, Sq, Sk]), with the semantics of ops/attention.py: a -inf (or overflowing) bias element
-removes a key, a query row with no key left gives zeros, the bias and the lengths take no gradient.
+removes a key, a query row with no key left gives zeros, the lengths take no gradient and the bias takes
+one only with the attribute `attn_bias_grad=True` (ops/attention.py: dS summed over the dims the bias
+broadcasts over, in the input's dtype and shape).
 `segment_ids` (attribute `segment_ids=True`; int32 [B, S], the 4th input, for Sq == Sk == S) packs several
 sequences into a row as in ops/attention.py; not combined with `key_lengths` or `attn_bias`.
 `scale` defaults to 1 / sqrt(D); `causal` and `dropout` are those of multihead_attention (the same
@@ -27,8 +29,8 @@ import torch
 
 from .. import kernels as K
 from ..type import DataType, OperatorType
-from .attention import (attn_bias_map, attn_core_bwd, attn_core_fwd, attn_drop_args, attn_keep_ref,
-                        check_attn_bias_dims, check_segment_ids_dims, check_window_dims, setup_window, window_attrs,
+from .attention import (attn_bias_grad_out, attn_bias_map, attn_core_bwd, attn_core_fwd, attn_drop_args, attn_keep_ref,
+                        check_attn_bias_dims, check_attn_bias_grad, check_segment_ids_dims, check_window_dims, setup_window, window_attrs,
                         window_pairs)
 from .base import OpImpl, register
 
@@ -42,6 +44,7 @@ class ScaledDotProductAttention(OpImpl):
     def infer(cls, attrs, in_dims, in_dtypes):
         nk, nb = (1 if attrs.get("key_lengths") else 0), (1 if attrs.get("attn_bias") else 0)
         ns = 1 if attrs.get("segment_ids") else 0
+        check_attn_bias_grad("scaled_dot_product_attention", attrs)
         if ns and nk:
             raise ValueError("scaled_dot_product_attention: segment_ids cannot be combined with key_lengths")
         if len(in_dims) != 3 + nk + nb + ns:
@@ -93,7 +96,7 @@ class ScaledDotProductAttention(OpImpl):
         return maps
 
     def needs_input_grad(self, i):
-        return i < 3
+        return i < 3 or bool(self.attrs.get("attn_bias_grad") and i == len(self.layer.inputs) - 1)
 
     def setup_device(self, device):
         """Called once by the executor, outside any captured region: a sliding window's bound arrays."""
@@ -126,7 +129,8 @@ class ScaledDotProductAttention(OpImpl):
                       Hkv=Hkv)
         if ctx.training:
             s.update(q=q, k=k, v=v, o=o, shape=(B, Hl, Sq, Sk, kd, vd), st=(qs, ks, vs, os_), scale=scale,
-                     causal=causal, key_lens=kl, drop=drop, sbias=bias, seg=seg, Hkv=Hkv)
+                     causal=causal, key_lens=kl, drop=drop, sbias=bias, seg=seg, Hkv=Hkv,
+                     sbias_dtype=xs[-1].dtype if has_bias else None)
         return [o]
 
     def backward(self, ctx, douts):
@@ -136,10 +140,15 @@ class ScaledDotProductAttention(OpImpl):
         q, k, v, o = s["q"], s["k"], s["v"], s["o"]
         do = douts[0].contiguous()
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        dsb = attn_bias_grad_out(self, ctx, s["sbias"])
         attn_core_bwd(s, q.view(-1), qs, k.view(-1), ks, v.view(-1), vs, o, os_, do, os_, dq, dk, dv, B, Hl, Sq, Sk, kd,
-                      vd, s["scale"], s["causal"], s["key_lens"], s["drop"], s["sbias"], seg=s.get("seg"), Hkv=s.get("Hkv"))
+                      vd, s["scale"], s["causal"], s["key_lens"], s["drop"], s["sbias"], seg=s.get("seg"), Hkv=s.get("Hkv"),
+                      dsb=dsb)
+        rest = [None] * (len(self.layer.inputs) - 3)
+        if dsb is not None:
+            rest[-1] = dsb.to(s["sbias_dtype"])
         ctx.saved.clear()
-        return [dq, dk, dv] + [None] * (len(self.layer.inputs) - 3)
+        return [dq, dk, dv] + rest
 
     def flops(self, in_shapes, out_shapes, w_shapes):
         B, H, Sq, D = in_shapes[0]
@@ -147,7 +156,8 @@ class ScaledDotProductAttention(OpImpl):
         win = window_attrs(self.attrs)
         if win is not None:  # the band's pairs only
             return 2.0 * B * H * window_pairs(Sq, win, bool(self.attrs.get("causal"))) * (D + Dv)
-        return 2.0 * B * H * Sq * Sk * (D + Dv)
+        # the score-bias gradient recomputes S and dP: two more GEMMs in the backward
+        return 2.0 * B * H * Sq * Sk * (D + Dv) * (2 if self.attrs.get("attn_bias_grad") else 1)
 
     def uses_mfma(self):
         return True

@@ -190,6 +190,8 @@ class Executor:
             if L.name in self.ctx:
                 # first Linear-like ops whose input needs no grad skip the dgrad GEMM
                 self.ctx[L.name].extra["need_dx0"] = bool(L.inputs) and self.in_grad.get((L.name, 0), False)
+                # every input's flag (a score bias's gradient kernel runs only where it is set)
+                self.ctx[L.name].extra["in_grad"] = tuple(self.in_grad.get((L.name, j), False) for j in range(len(L.inputs)))
                 lo = self.lay[L.name]
                 if lo.inputs:
                     p = lo.inputs[0].parts_on(self.rank)
