@@ -698,6 +698,83 @@ std::vector<void*> ptr_list(const std::vector<optional<Tensor>>& ts, at::ScalarT
   return out;
 }
 
+// ------------------------------------------------------------------ grouped expert GEMMs (experts.hip)
+// Each returns false when the launcher refuses the shape / alignment (the caller falls back).
+bool experts_load_ok(const Tensor& load, size_t n) {
+  return load.is_cuda() && load.scalar_type() == at::kInt && load.is_contiguous() && (size_t)load.numel() == n;
+}
+
+bool experts_fwd(std::vector<optional<Tensor>> xs, Tensor w, optional<Tensor> bias, Tensor load, Tensor y,
+                 optional<Tensor> z, int64_t act, int64_t tile_m) {
+  check_dev(w, "w"); check_dev(y, "y");
+  const int64_t n = (int64_t)xs.size();
+  TORCH_CHECK(w.dim() == 3 && w.size(0) == n && w.is_contiguous() && w.scalar_type() == at::kBFloat16, "experts_fwd: w");
+  const int64_t N = w.size(1), K = w.size(2);
+  TORCH_CHECK(y.scalar_type() == at::kBFloat16 && y.is_contiguous() && y.dim() == 3 && y.size(0) == n && y.size(2) == N,
+              "experts_fwd: y must be a bf16 slab [n, cap, N]");
+  const int64_t cap = y.size(1);
+  TORCH_CHECK(experts_load_ok(load, n), "experts_fwd: load must be int32 [n] on the device");
+  if (z.has_value() && z->defined())
+    TORCH_CHECK(z->scalar_type() == at::kBFloat16 && z->is_contiguous() && z->sizes() == y.sizes(), "experts_fwd: z");
+  int bias_bf16 = 0;
+  if (bias.has_value() && bias->defined()) {
+    check_dev(*bias, "bias");
+    TORCH_CHECK(bias->numel() == n * N && bias->is_contiguous() &&
+                (bias->scalar_type() == at::kBFloat16 || bias->scalar_type() == at::kFloat), "experts_fwd: bias");
+    bias_bf16 = bias->scalar_type() == at::kBFloat16;
+  }
+  if (n > ffk::kMoeMaxExperts) return false;
+  auto px = ptr_list(xs, at::kBFloat16, cap * K);
+  return ffk::experts_fwd(px.data(), (int)n, w.data_ptr(), ptr(bias), bias_bf16, load.data_ptr<int>(), y.data_ptr(),
+                          ptr(z), (int)cap, (int)N, (int)K, (int)act, (int)tile_m, cur_stream());
+}
+
+bool experts_bwd_data(std::vector<optional<Tensor>> dzs, Tensor w, Tensor load, Tensor dx, int64_t tile_m) {
+  check_dev(w, "w"); check_dev(dx, "dx");
+  const int64_t n = (int64_t)dzs.size();
+  TORCH_CHECK(w.dim() == 3 && w.size(0) == n && w.is_contiguous() && w.scalar_type() == at::kBFloat16,
+              "experts_bwd_data: w");
+  const int64_t N = w.size(1), K = w.size(2);
+  TORCH_CHECK(dx.scalar_type() == at::kBFloat16 && dx.is_contiguous() && dx.dim() == 3 && dx.size(0) == n &&
+              dx.size(2) == K, "experts_bwd_data: dx must be a bf16 slab [n, cap, K]");
+  TORCH_CHECK(experts_load_ok(load, n), "experts_bwd_data: load must be int32 [n] on the device");
+  if (n > ffk::kMoeMaxExperts) return false;
+  const int64_t cap = dx.size(1);
+  auto pz = ptr_list(dzs, at::kBFloat16, cap * N);
+  return ffk::experts_bwd_data(pz.data(), (int)n, w.data_ptr(), load.data_ptr<int>(), dx.data_ptr(), (int)cap, (int)N,
+                               (int)K, (int)tile_m, cur_stream());
+}
+
+bool experts_bwd_weight(std::vector<optional<Tensor>> dzs, std::vector<optional<Tensor>> xs, Tensor load, Tensor dw,
+                        optional<Tensor> db, int64_t cap) {
+  check_dev(dw, "dw");
+  const int64_t n = (int64_t)dzs.size();
+  TORCH_CHECK(xs.size() == dzs.size() && dw.dim() == 3 && dw.size(0) == n && dw.is_contiguous() &&
+              dw.scalar_type() == at::kFloat, "experts_bwd_weight: dw must be fp32 [n, N, K]");
+  const int64_t N = dw.size(1), K = dw.size(2);
+  TORCH_CHECK(experts_load_ok(load, n), "experts_bwd_weight: load must be int32 [n] on the device");
+  if (db.has_value() && db->defined())
+    TORCH_CHECK(db->is_cuda() && db->scalar_type() == at::kFloat && db->is_contiguous() && db->numel() == n * N,
+                "experts_bwd_weight: db must be fp32 [n * N]");
+  if (n > ffk::kMoeMaxExperts) return false;
+  auto pz = ptr_list(dzs, at::kBFloat16, cap * N);
+  auto px = ptr_list(xs, at::kBFloat16, cap * K);
+  return ffk::experts_bwd_weight(pz.data(), px.data(), (int)n, load.data_ptr<int>(), dw.data_ptr<float>(),
+                                 ptr<float>(db), (int)cap, (int)N, (int)K, cur_stream());
+}
+
+bool experts_act_bwd(std::vector<optional<Tensor>> dys, Tensor z, Tensor dz, Tensor load, int64_t act) {
+  check_dev(z, "z"); check_dev(dz, "dz");
+  const int64_t n = (int64_t)dys.size();
+  TORCH_CHECK(z.dim() == 3 && z.size(0) == n && z.is_contiguous() && z.scalar_type() == at::kBFloat16 &&
+              dz.is_contiguous() && dz.scalar_type() == at::kBFloat16 && dz.sizes() == z.sizes(), "experts_act_bwd: z / dz");
+  TORCH_CHECK(experts_load_ok(load, n), "experts_act_bwd: load must be int32 [n] on the device");
+  if (n > ffk::kMoeMaxExperts) return false;
+  auto py = ptr_list(dys, at::kBFloat16, z.size(1) * z.size(2));
+  return ffk::experts_act_bwd(py.data(), (int)n, z.data_ptr(), dz.data_ptr(), load.data_ptr<int>(), (int)z.size(1),
+                              (int)z.size(2), (int)act, cur_stream());
+}
+
 void topk_fwd(Tensor x, Tensor vals, Tensor idx, int64_t k) {
   check_dev(x, "x");
   TORCH_CHECK(x.is_contiguous() && vals.is_contiguous() && idx.is_contiguous() && idx.scalar_type() == at::kInt);
@@ -1639,6 +1716,11 @@ PYBIND11_MODULE(_C, m) {
   m.def("moe_route_ws_ints", &moe_route_ws_ints);
   m.def("moe_route", &moe_route);
   m.def("groupby_fwd", &groupby_fwd);
+  m.def("experts_tile_m", [](int64_t cap) { return (int64_t)ffk::experts_tile_m((int)cap); });
+  m.def("experts_fwd", &experts_fwd);
+  m.def("experts_bwd_data", &experts_bwd_data);
+  m.def("experts_bwd_weight", &experts_bwd_weight);
+  m.def("experts_act_bwd", &experts_act_bwd);
   m.def("groupby_bwd", &groupby_bwd);
   m.def("aggregate_fwd", &aggregate_fwd);
   m.def("aggregate_bwd", &aggregate_bwd);

@@ -180,6 +180,24 @@ void aggregate_bwd(int dt, const void* dout, const void* gate, void* const* exps
                    int cap, const int* expert, const int* pos, const int* assign, const int* true_assign,
                    const int* load, float lambda_bal, void* dgate, void* dfull, int B, int k, int D, hipStream_t st);
 
+// experts.hip: the Linears of all n experts as one grouped bf16 MFMA GEMM per direction. xs / dzs /
+// dys: n device pointers to [cap][.] bf16 tensors (null = an expert without rows); w [n][N][K] bf16;
+// y / z / dx / dz: slabs [n][cap][.] bf16; load[n]: the router's device-side row counts, clamped to
+// [0, cap] where they are read. Rows at or beyond the load are written as zeros (y, z, dx) and never
+// read. tile_m: 0 = experts_tile_m(cap), or 64 / 128. False = refused (n > kMoeMaxExperts, N % 8,
+// K % 8, a base not 16-B aligned): nothing was launched.
+int experts_tile_m(int cap);
+bool experts_fwd(const void* const* xs, int n, const void* w, const void* bias, int bias_bf16, const int* load,
+                 void* y, void* z, int cap, int N, int K, int act, int tile_m, hipStream_t st);
+bool experts_bwd_data(const void* const* dzs, int n, const void* w, const int* load, void* dx, int cap, int N, int K,
+                      int tile_m, hipStream_t st);
+// dw [n][N][K] and db (optional) [n][N] fp32, both +=; deterministic; an expert with no rows is left alone
+bool experts_bwd_weight(const void* const* dzs, const void* const* xs, int n, const int* load, float* dw, float* db,
+                        int cap, int N, int K, hipStream_t st);
+// dz_e[r] = dy_e[r] * act'(z_e[r]) for the live rows (the others are not written)
+bool experts_act_bwd(const void* const* dys, int n, const void* z, void* dz, const int* load, int cap, int N, int act,
+                     hipStream_t st);
+
 // norm.hip
 void layernorm_fwd(int dt, const void* x, const void* res, void* sum_out, const void* gamma, const void* beta,
                    void* y, float* mean, float* rstd, int rows, int cols, float eps, hipStream_t st);

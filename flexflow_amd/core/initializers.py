@@ -102,6 +102,27 @@ def default_initializer(weight_name: str, seed: int) -> Initializer:
     return GlorotUniformInitializer(seed)
 
 
+class PerExpertInitializer(Initializer):
+    """Initializer of a stacked expert weight [n, out, in] (ops/misc.py ExpertsDense): slice e is filled
+    as a dense layer's [out, in] weight would be (fan-in and fan-out per expert, not over the 3-D
+    tensor) by `inner` (default Glorot uniform), each expert with a seed of its own. seed None: the
+    model-local seed of the weight (Executor.init_weights)."""
+
+    def __init__(self, inner=None):
+        self.inner = inner
+        self.seed = None
+
+    def fill_full(self, t, shape):
+        import copy
+        for e in range(shape[0]):
+            init = copy.copy(self.inner) if self.inner is not None else GlorotUniformInitializer(None)
+            base = self.seed if getattr(init, "seed", 0) is None else getattr(init, "seed", 0)
+            init.seed = int(base or 0) + 7919 * e
+            blk = torch.empty(tuple(shape[1:]), dtype=t.dtype, device=t.device)
+            init.fill_full(blk, tuple(shape[1:]))
+            t[e].copy_(blk)
+
+
 class BlockInitializer(Initializer):
     """Initializer of a weight that a graph rewrite built by stacking other weights along axis 0
     (pcg/joint.py MergeSiblings). Each row block is filled exactly as its original weight would

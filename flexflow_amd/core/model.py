@@ -544,15 +544,57 @@ class FFModel:
         L.attrs["score_f"] = score_f
         return L.outputs[0]
 
-    def moe(self, input, num_exp, num_select, expert_hidden_size, alpha, lambda_bal):
-        """reference FFModel::moe (src/ops/moe.cc): gate -> top_k -> group_by -> experts -> aggregate."""
+    def experts_dense(self, inputs, assign, out_dim, activation=ActiMode.AC_MODE_NONE, use_bias=True,
+                      kernel_initializer=None, bias_initializer=None, name=None):
+        """The dense layer of every expert as one layer (extension; ops/misc.py ExpertsDense): inputs are the n
+        tensors [cap, in_dim] of group_by (or of a previous experts_dense), assign the [B, k] top-k indices that
+        routed them. Returns n tensors [cap, out_dim]: activation(x_e . W_e^T + b_e) on the rows the router
+        filled, zeros after. Weights: kernel (n, out_dim, in_dim), each expert's slice initialised as dense
+        would initialise an (out_dim, in_dim) weight, and bias (n * out_dim,). One grouped GEMM launch per
+        direction instead of one per expert, computing the routed rows only."""
+        inputs = list(inputs)
+        if not inputs:
+            raise ValueError("experts_dense: needs at least one expert input")
+        if int(out_dim) < 1:
+            raise ValueError(f"experts_dense: out_dim must be positive, got {out_dim}")
+        L = self._add(OperatorType.OP_EXPERTS_DENSE, inputs + [assign], name, out_dim=int(out_dim),
+                      activation=activation, use_bias=bool(use_bias), kernel_init=kernel_initializer,
+                      bias_init=bias_initializer)
+        return list(L.outputs)
+
+    def moe(self, input, num_exp, num_select, expert_hidden_size, alpha, lambda_bal, fused_experts=False):
+        """reference FFModel::moe (src/ops/moe.cc): gate -> top_k -> group_by -> experts -> aggregate.
+        fused_experts: the num_exp dense layers as one experts_dense (the softmaxes and the aggregate stay)."""
         gate = self.dense(input, num_exp, ActiMode.AC_MODE_RELU)
         topk_v, topk_i = self.top_k(gate, num_select, False)
         exp_t = self.group_by(input, topk_i, num_exp, alpha)
         agg = [self.softmax(topk_v), topk_i, topk_i, gate]
+        if fused_experts:
+            exp_t = self.experts_dense(exp_t, topk_i, expert_hidden_size, ActiMode.AC_MODE_RELU)
+            agg += [self.softmax(e) for e in exp_t]
+            return self.aggregate(agg, num_exp, lambda_bal)
         for e in exp_t:
             agg.append(self.softmax(self.dense(e, expert_hidden_size, ActiMode.AC_MODE_RELU)))
         return self.aggregate(agg, num_exp, lambda_bal)
+
+    def moe_ffn(self, input, num_exp, num_select, ffn_dim, alpha=2.0, lambda_bal=0.0,
+                activation=ActiMode.AC_MODE_GELU, name=None):
+        """The mixture-of-experts FFN of current decoders (extension): a linear gate, top-k routing with
+        softmax weights over the picks, and per expert down(activation(up(x))) with up [ffn_dim, D] and down
+        [D, ffn_dim], summed with the routing weights. input [B, D] -> [B, D]. Built from dense (gate), top_k,
+        group_by, two experts_dense and aggregate (layers {name}_gate, _topk, _group, _up, _down, _agg): two
+        grouped GEMM layers, no layer per expert."""
+        if int(ffn_dim) < 1:
+            raise ValueError(f"moe_ffn: ffn_dim must be positive, got {ffn_dim}")
+        n = (lambda s: None) if name is None else (lambda s: f"{name}_{s}")
+        D = input.dims[-1]
+        gate = self.dense(input, num_exp, name=n("gate"))
+        topk_v, topk_i = self.top_k(gate, num_select, False, name=n("topk"))
+        exp_t = self.group_by(input, topk_i, num_exp, alpha, name=n("group"))
+        h = self.experts_dense(exp_t, topk_i, int(ffn_dim), activation, name=n("up"))
+        y = self.experts_dense(h, topk_i, D, name=n("down"))
+        return self.aggregate([self.softmax(topk_v, name=n("weights")), topk_i, topk_i, gate] + y, num_exp,
+                              lambda_bal, name=n("agg"))
 
     # ---- explicit parallel ops (ops/parallel_ops.py): identity compute, pinned output layout
     def repartition(self, input, dim, degree, name=None):

@@ -3017,6 +3017,102 @@ def moe_route(assign: torch.Tensor, n: int, cap: int):
     return expert, pos, load
 
 
+# ------------------------------------------------------------- grouped expert GEMMs (experts.hip)
+# The Linears of all n experts of a layer in one launch per direction. xs / dz / dy: n tensors
+# [cap, .] (group_by's outputs; None = an expert without rows); w [n, N, K]; b [n * N] or None;
+# load: the router's int32 [n] row counts, read on the device and clamped to [0, cap]. Outputs are one
+# slab [n, cap, .]; its rows at or beyond the load are zeros, and nothing depends on what the inputs
+# hold there. The HIP kernels take bf16 device tensors with N % 8 == K % 8 == 0 and at most
+# MOE_MAX_EXPERTS experts; everything else (fp32, CPU, refused shapes) runs the per-expert torch loops
+# below, which are the definition of the ops.
+def _experts_dev(n, w, *groups):
+    """The HIP path: at most MOE_MAX_EXPERTS experts, w a contiguous bf16 device tensor, every group of
+    n expert tensors bf16 on the device (None = an expert without rows, but not all of them)."""
+    return (n <= MOE_MAX_EXPERTS and native(w) and w.dtype == torch.bfloat16 and w.is_contiguous()
+            and all(len(g) == n and any(t is not None for t in g)
+                    and all(t is None or (native(t) and t.dtype == torch.bfloat16) for t in g) for g in groups))
+
+
+def _experts_cont(ts):
+    return [None if t is None else t.contiguous() for t in ts]
+
+
+def _experts_live(load, cap, dev):
+    """[n, cap, 1] mask of the live rows, without a host sync."""
+    r = load.to(dev).long().clamp(0, cap)
+    return (torch.arange(cap, device=dev)[None, :] < r[:, None])[:, :, None]
+
+
+def _experts_stack(ts, cap, width, dev):
+    """n tensors (None = zeros) as one fp32 [n, cap, width] with non-finite padding left in place."""
+    return torch.stack([torch.zeros(cap, width, device=dev) if t is None else t.float() for t in ts])
+
+
+def experts_fwd(xs, w, b, load, act, save_z=False, tile_m=0):
+    """slab[e, r] = act(xs[e][r] . w[e]^T + b[e]) for r < load[e], zeros after. Returns (slab, z): z is the
+    bf16 pre-activation slab when save_z and there is an activation, else None."""
+    n, N, Kd = w.shape
+    like = next(t for t in xs if t is not None)
+    cap, dev = like.shape[0], like.device
+    want_z = save_z and act != ACT_NONE
+    if _experts_dev(n, w, xs):
+        y = torch.empty(n, cap, N, device=dev, dtype=torch.bfloat16)
+        z = torch.empty_like(y) if want_z else None
+        if ext().experts_fwd(_experts_cont(xs), w, b, load, y, z, act, tile_m):
+            return y, z
+    live = _experts_live(load, cap, dev)
+    x = torch.where(live, _experts_stack(xs, cap, Kd, dev), 0.0)
+    r = torch.einsum("erk,enk->ern", x, w.float())
+    if b is not None:
+        r = r + b.float().view(n, 1, N)
+    y = torch.where(live, act_ref(r, act), 0.0).to(w.dtype)
+    return y, (torch.where(live, r, 0.0).to(w.dtype) if want_z else None)
+
+
+def experts_act_bwd(dys, z, load, act):
+    """dz slab [n, cap, N]: dys[e][r] * act'(z[e, r]) for r < load[e] (other rows: unspecified on the HIP
+    path, zeros on the fallback; no consumer reads them)."""
+    n, cap, N = z.shape
+    if _experts_dev(n, z, dys):
+        dz = torch.empty_like(z)
+        if ext().experts_act_bwd(_experts_cont(dys), z, dz, load, act):
+            return dz
+    live = _experts_live(load, cap, z.device)
+    dy = torch.where(live, _experts_stack(dys, cap, N, z.device), 0.0)
+    return torch.where(live, dy * act_grad_ref(z.float(), act), 0.0).to(z.dtype)
+
+
+def experts_bwd_data(dz, w, load, tile_m=0):
+    """slab[e, r] = dz[e][r] . w[e] for r < load[e], zeros after."""
+    n, N, Kd = w.shape
+    like = next(t for t in dz if t is not None)
+    cap, dev = like.shape[0], like.device
+    if _experts_dev(n, w, dz):
+        dx = torch.empty(n, cap, Kd, device=dev, dtype=torch.bfloat16)
+        if ext().experts_bwd_data(_experts_cont(dz), w, load, dx, tile_m):
+            return dx
+    g = torch.where(_experts_live(load, cap, dev), _experts_stack(dz, cap, N, dev), 0.0)
+    return torch.einsum("ern,enk->erk", g, w.float()).to(w.dtype)
+
+
+def experts_bwd_weight(dz, xs, load, dw, db):
+    """dw[e] += sum_{r < load[e]} dz[e][r]^T xs[e][r] (fp32 [n, N, K]); db[e * N ..] += the column sums of
+    those rows (fp32 [n * N] or None). Deterministic; an expert without rows leaves its slices alone."""
+    n, N, Kd = dw.shape
+    like = next(t for t in xs if t is not None)
+    cap, dev = like.shape[0], like.device
+    if _experts_dev(n, like.contiguous(), dz, xs) and native(dw) and dw.dtype == torch.float32 \
+            and dw.is_contiguous() and (db is None or db.is_contiguous()):
+        if ext().experts_bwd_weight(_experts_cont(dz), _experts_cont(xs), load, dw, db, cap):
+            return
+    live = _experts_live(load, cap, dev)
+    g = torch.where(live, _experts_stack(dz, cap, N, dev), 0.0)
+    x = torch.where(live, _experts_stack(xs, cap, Kd, dev), 0.0)
+    dw.add_(torch.einsum("ern,erk->enk", g, x).to(dw.dtype))
+    if db is not None:
+        db.add_(g.sum(1).reshape(-1).to(db.dtype))
+
+
 # ------------------------------------------------------------------ fp32 attention (our kernels)
 def attn_f32_supported(x) -> bool:
     return native(x) and x.dtype == torch.float32

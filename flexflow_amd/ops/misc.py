@@ -1,5 +1,5 @@
 """BatchMatmul, reductions, TopK and the mixture-of-experts family (GroupBy / Aggregate /
-AggregateSpec / Cache).
+AggregateSpec / ExpertsDense / Cache).
 
 Reference: src/ops/batch_matmul.cc, reduce.cc, mean.cc (a stub that asserts in the reference),
 topk.cc, group_by.cc, aggregate.cc, aggregate_spec.cc, cache.cc (also a stub there).
@@ -14,8 +14,8 @@ import math
 import torch
 
 from .. import kernels as K
-from ..type import DataType, OperatorType
-from .base import OpImpl, register
+from ..type import ActiMode, DataType, OperatorType
+from .base import OpImpl, WeightSpec, register
 
 
 @register(OperatorType.OP_BATCHMATMUL)
@@ -316,6 +316,91 @@ class Aggregate(OpImpl):
 
     def needs_input_grad(self, i):
         return i not in (1, 2)
+
+
+@register(OperatorType.OP_EXPERTS_DENSE)
+class ExpertsDense(OpImpl):
+    """The Linear of every expert in one layer: inputs x_0 .. x_{n-1} [cap, in] (group_by's outputs or a
+    previous experts_dense's) and the [B, k] assignment; outputs y_e = act(x_e . W_e^T + b_e) [cap, out]
+    for the rows the router filled (row < load[e]), zeros after. Weights: kernel [n, out, in], bias
+    [n * out] (1-D, so the optimizers keep treating it as a bias). One grouped MFMA GEMM per direction
+    (csrc/kernels/experts.hip) whose row counts are the device-side load of K.moe_route: no launch per
+    expert, no work on the capacity's empty rows, no host synchronisation. Replicated, like GroupBy."""
+    op_type = OperatorType.OP_EXPERTS_DENSE
+
+    @classmethod
+    def infer(cls, attrs, in_dims, in_dtypes):
+        from ..core.initializers import PerExpertInitializer
+        exps = in_dims[:-1]
+        n, out = len(exps), attrs["out_dim"]
+        if n < 1 or any(len(d) != 2 or tuple(d) != tuple(exps[0]) for d in exps):
+            raise ValueError(f"experts_dense: the expert inputs must be n tensors of one shape [cap, in], got {exps}")
+        cap, din = exps[0]
+        attrs["n"], attrs["cap"] = n, cap
+        dt = in_dtypes[0]
+        ws = [WeightSpec("kernel", (n, out, din), dt, PerExpertInitializer(attrs.get("kernel_init")))]
+        if attrs.get("use_bias", True):
+            ws.append(WeightSpec("bias", (n * out,), dt, attrs.get("bias_init")))
+        return [(cap, out)] * n, [dt] * n, ws
+
+    def axis_kinds(self):
+        return ["none"] * len(self.layer.outputs[0].dims)
+
+    def input_maps(self):
+        return [tuple([None] * len(t.dims)) for t in self.layer.inputs]
+
+    def output_maps(self):
+        return [tuple([None] * len(o.dims)) for o in self.layer.outputs]
+
+    @property
+    def act(self):
+        return self.attrs.get("activation", ActiMode.AC_MODE_NONE).value
+
+    def saves_output(self):
+        return False  # backward reads the inputs and the saved pre-activation only
+
+    def forward(self, ctx, xs, ws):
+        exps, assign = list(xs[:-1]), xs[-1]
+        n, cap = self.attrs["n"], self.attrs["cap"]
+        w = ws[0]
+        b = ws[1] if len(ws) > 1 else None
+        if K.moe_on_device(exps[0], n):
+            load = K.moe_route(assign, n, cap)[2]
+        else:  # what moe_route counts: the pairs per (clamped) expert id; no host synchronisation either
+            flat = assign.reshape(-1).long().clamp(0, n - 1)
+            load = torch.nn.functional.one_hot(flat, n).sum(0).to(torch.int32)
+        exps = [x.to(w.dtype) for x in exps]
+        y, z = K.experts_fwd(exps, w, b, load, self.act, save_z=ctx.training)
+        if ctx.training:
+            ctx.saved.update(xs=exps, w=w, z=z, load=load)
+        return list(y.unbind(0))
+
+    def backward(self, ctx, douts):
+        s = ctx.saved
+        exps, w, z, load = s["xs"], s["w"], s["z"], s["load"]
+        n = len(exps)
+        ctx.saved.clear()
+        if all(d is None for d in douts):
+            return [None] * (n + 1)
+        dz = [None if d is None else d.to(w.dtype) for d in douts]
+        if self.act != K.ACT_NONE:
+            slab = K.experts_act_bwd(dz, z, load, self.act)
+            dz = [None if d is None else slab[e] for e, d in enumerate(dz)]
+        dx = K.experts_bwd_data(dz, w, load)
+        dw = ctx.wgrads[0] if ctx.wgrads else None
+        if dw is not None:
+            K.experts_bwd_weight(dz, exps, load, dw, ctx.wgrads[1] if len(ctx.wgrads) > 1 else None)
+        return list(dx.unbind(0)) + [None]
+
+    def needs_input_grad(self, i):
+        return i < self.attrs["n"]
+
+    def flops(self, in_shapes, out_shapes, w_shapes):
+        """2 * n * cap * in * out: the capacity, an upper bound (the kernels compute the load's rows only)."""
+        return 2.0 * self.attrs["n"] * self.attrs["cap"] * in_shapes[0][-1] * self.attrs["out_dim"]
+
+    def uses_mfma(self):
+        return True
 
 
 @register(OperatorType.OP_CACHE)

@@ -172,6 +172,7 @@ class OperatorType(IntEnum):
     OP_SILU = 104  # extension: x * sigmoid(x), element-unary (ops/elementwise.py)
     OP_GLU = 105  # extension: gated linear unit act(gate) * up: SwiGLU / GeGLU / ReGLU / GLU (ops/glu.py)
     OP_ADD_RMS_NORM = 106  # extension: RMS norm of x + residual with the sum as a second output (ops/norm.py)
+    OP_EXPERTS_DENSE = 107  # extension: the Linears of all n experts as one grouped GEMM (ops/misc.py)
 
 
 class OpType(Enum):
