@@ -775,6 +775,54 @@ bool experts_act_bwd(std::vector<optional<Tensor>> dys, Tensor z, Tensor dz, Ten
                               (int)z.size(2), (int)act, cur_stream());
 }
 
+// w [n, 2F, K] (gate rows, then up rows, per expert), h [n, cap, F], z (optional) [n, cap, 2F]; act: a GluAct code;
+// epilogue: 0 = the default, 1 = staged through LDS, 2 = direct
+bool experts_glu_fwd(std::vector<optional<Tensor>> xs, Tensor w, optional<Tensor> bias, Tensor load, Tensor h,
+                     optional<Tensor> z, int64_t act, int64_t tile_m, int64_t epilogue) {
+  check_dev(w, "w"); check_dev(h, "h");
+  const int64_t n = (int64_t)xs.size();
+  TORCH_CHECK(w.dim() == 3 && w.size(0) == n && w.size(1) % 2 == 0 && w.is_contiguous() &&
+              w.scalar_type() == at::kBFloat16, "experts_glu_fwd: w must be bf16 [n, 2F, K]");
+  const int64_t F = w.size(1) / 2, K = w.size(2);
+  TORCH_CHECK(h.scalar_type() == at::kBFloat16 && h.is_contiguous() && h.dim() == 3 && h.size(0) == n && h.size(2) == F,
+              "experts_glu_fwd: h must be a bf16 slab [n, cap, F]");
+  const int64_t cap = h.size(1);
+  TORCH_CHECK(experts_load_ok(load, n), "experts_glu_fwd: load must be int32 [n] on the device");
+  TORCH_CHECK(act >= 0 && act < 5, "experts_glu_fwd: act must be a GLU activation code");
+  TORCH_CHECK(epilogue >= 0 && epilogue <= 2, "experts_glu_fwd: epilogue must be 0, 1 or 2");
+  if (z.has_value() && z->defined()) {
+    check_dev(*z, "z");
+    TORCH_CHECK(z->scalar_type() == at::kBFloat16 && z->is_contiguous() && z->dim() == 3 && z->size(0) == n &&
+                z->size(1) == cap && z->size(2) == 2 * F, "experts_glu_fwd: z must be a bf16 slab [n, cap, 2F]");
+  }
+  int bias_bf16 = 0;
+  if (bias.has_value() && bias->defined()) {
+    check_dev(*bias, "bias");
+    TORCH_CHECK(bias->numel() == n * 2 * F && bias->is_contiguous() &&
+                (bias->scalar_type() == at::kBFloat16 || bias->scalar_type() == at::kFloat), "experts_glu_fwd: bias");
+    bias_bf16 = bias->scalar_type() == at::kBFloat16;
+  }
+  if (n > ffk::kMoeMaxExperts) return false;
+  auto px = ptr_list(xs, at::kBFloat16, cap * K);
+  return ffk::experts_glu_fwd(px.data(), (int)n, w.data_ptr(), ptr(bias), bias_bf16, load.data_ptr<int>(), h.data_ptr(),
+                              ptr(z), (int)cap, (int)F, (int)K, (int)act, (int)tile_m, (int)epilogue, cur_stream());
+}
+
+bool experts_glu_bwd(std::vector<optional<Tensor>> dhs, Tensor z, Tensor dz, Tensor load, int64_t act) {
+  check_dev(z, "z"); check_dev(dz, "dz");
+  const int64_t n = (int64_t)dhs.size();
+  TORCH_CHECK(z.dim() == 3 && z.size(0) == n && z.size(2) % 2 == 0 && z.is_contiguous() &&
+              z.scalar_type() == at::kBFloat16 && dz.is_contiguous() && dz.scalar_type() == at::kBFloat16 &&
+              dz.sizes() == z.sizes(), "experts_glu_bwd: z / dz must be bf16 slabs [n, cap, 2F]");
+  TORCH_CHECK(experts_load_ok(load, n), "experts_glu_bwd: load must be int32 [n] on the device");
+  TORCH_CHECK(act >= 0 && act < 5, "experts_glu_bwd: act must be a GLU activation code");
+  if (n > ffk::kMoeMaxExperts) return false;
+  const int64_t F = z.size(2) / 2;
+  auto ph = ptr_list(dhs, at::kBFloat16, z.size(1) * F);
+  return ffk::experts_glu_bwd(ph.data(), (int)n, z.data_ptr(), dz.data_ptr(), load.data_ptr<int>(), (int)z.size(1),
+                              (int)F, (int)act, cur_stream());
+}
+
 void topk_fwd(Tensor x, Tensor vals, Tensor idx, int64_t k) {
   check_dev(x, "x");
   TORCH_CHECK(x.is_contiguous() && vals.is_contiguous() && idx.is_contiguous() && idx.scalar_type() == at::kInt);
@@ -1721,6 +1769,9 @@ PYBIND11_MODULE(_C, m) {
   m.def("experts_bwd_data", &experts_bwd_data);
   m.def("experts_bwd_weight", &experts_bwd_weight);
   m.def("experts_act_bwd", &experts_act_bwd);
+  m.def("experts_glu_fwd", &experts_glu_fwd, py::arg("xs"), py::arg("w"), py::arg("bias"), py::arg("load"), py::arg("h"),
+        py::arg("z"), py::arg("act"), py::arg("tile_m"), py::arg("epilogue") = 0);
+  m.def("experts_glu_bwd", &experts_glu_bwd);
   m.def("groupby_bwd", &groupby_bwd);
   m.def("aggregate_fwd", &aggregate_fwd);
   m.def("aggregate_bwd", &aggregate_bwd);

@@ -33,9 +33,16 @@
 //   * staging: global_load_dwordx4 into registers for tile t + 1 issued before the MFMAs of tile t,
 //     ds_write after them, double-buffered LDS, one barrier per K-tile; LDS images, fragment reads and
 //     tile order are gemm_tile.h's (shared with gemm.hip), the masked staging is this kernel's own.
+//   * gated experts (experts_glu_rows_kernel, experts_glu_bwd_kernel): W_e [2F][K] holds F gate rows, then F
+//     up rows. H_e = act(X_e Wg_e^T + bg_e) * (X_e Wu_e^T + bu_e) from one BM x 64 tile per workgroup whose
+//     B stage is the 64 gate rows and the 64 up rows of its output columns: both fp32 sums of an element
+//     sit in the same lane and the product is the epilogue (optional Z = (zg | zu) [cap][2F] for the
+//     backward), written through LDS as whole 16-B row chunks. The gate backward is one elementwise launch
+//     over the live rows into dZ [cap][2F], which the two gradient kernels above take with N = 2F.
 // Launchers refuse (return false) K % 8, N % 8, more than kMoeMaxExperts experts or a base that is not
 // 16-B aligned; the caller then runs its per-expert fallback.
 #include "gemm_tile.h"
+#include "glu_act.h"
 #include "ops.h"
 
 namespace ffk {
@@ -77,6 +84,24 @@ struct Stage {
       }
     }
   }
+  // The B stage of the gated forward (K-contiguous, 128 rows): rows 0..63 are the gate rows n0 .. n0 + 63
+  // of W_e [2F][K], rows 64..127 its up rows F + n0 .. F + n0 + 63; a row whose column n0 + (row & 63) is at
+  // or beyond F is selected to zero, so an up tile never reads into the next expert and a gate tile never
+  // reads up rows.
+  __device__ __forceinline__ void load_glu(const bf16_t* __restrict__ g, int64_t ld, int n0, int k0, int F, int k_lim,
+                                           int tid) {
+    static_assert(KCONT && ROWS == 128, "the gated stage is the K-contiguous 128-row one");
+#pragma unroll
+    for (int i = 0; i < NL; ++i) {
+      const int id = tid + i * NT;
+      const int row = id >> 3, gn = n0 + (row & 63), gk = k0 + (id & 7) * 8;
+      if (gn < F && gk < k_lim) {
+        r[i] = *reinterpret_cast<const uint4*>(g + (int64_t)((row >> 6) * F + gn) * ld + gk);
+      } else {
+        r[i] = make_uint4(0, 0, 0, 0);
+      }
+    }
+  }
   __device__ __forceinline__ void store(char* lds, int tid) const {
 #pragma unroll
     for (int i = 0; i < NL; ++i) {
@@ -107,6 +132,76 @@ struct Stage {
   }
 };
 
+// Block id -> tile of expert e with `rows` live rows: the first tm_live * tn block ids take the live
+// tiles, in gemm_tile.h's order over the live rows only; the others take the empty tiles behind them.
+// Consecutive block ids go to consecutive XCDs, so the live tiles spread over all of them whatever
+// share of the capacity is filled (the tile order over all cap rows put them on the first XCDs only:
+// 2x the time at half load).
+template <int BM>
+__device__ __forceinline__ void deal_tile(int bid, int rows, int tn, int& tile_m, int& tile_n) {
+  const int tm_live = (rows + BM - 1) / BM, n_live = tm_live * tn;
+  if (bid < n_live) {
+    tile_coords(bid, tm_live, tn, tile_m, tile_n);
+  } else {
+    tile_m = tm_live + (bid - n_live) / tn;
+    tile_n = (bid - n_live) % tn;
+  }
+}
+
+// The K loop of the gated forward, experts_rows_kernel's with the gated B stage: acc += X_e[m0 .. m0 + BM)[K]
+// . (gate rows | up rows)^T over double-buffered LDS stages (A: BM x 64, rows at or beyond `rows` selected
+// to zero; B: 128 x 64), the loads of tile t + 1 issued before the MFMAs of tile t and written to LDS
+// after them, one barrier per K-tile. Wave (wm, wn) takes A rows wm * BM/2 + 16 i and, for accumulator
+// slot j, B rows wn * 32 + 16 j (gate, j < 2) or 64 + wn * 32 + 16 (j - 2) (up): slots j and j + 2 of a lane
+// hold the gate and the up value of the same output element. On return every wave has passed the last
+// barrier: the LDS is free. (Kept apart from experts_rows_kernel's loop: one template for both changed
+// that kernel's scalar registers and argument loads.)
+template <int BM>
+__device__ __forceinline__ void glu_mainloop(char* smem, const bf16_t* __restrict__ A, const bf16_t* __restrict__ W,
+                                             int K, int F, int m0, int n0, int rows, int tid, int lane, int wm, int wn,
+                                             f32x4 (&acc)[BM / 32][4]) {
+  constexpr int A_BYTES = BM * BK * 2, B_BYTES = BN * BK * 2, STAGE_BYTES = A_BYTES + B_BYTES;
+  constexpr int MI = BM / 32;
+  const int nk = (K + BK - 1) / BK;
+  Stage<true, BM> sa;
+  Stage<true, BN> sb;
+  sa.load(A, K, m0, 0, rows, K, tid);
+  sb.load_glu(W, K, n0, 0, F, K, tid);
+  sa.store(smem, tid);
+  sb.store(smem + A_BYTES, tid);
+  __syncthreads();
+  for (int t = 0; t < nk; ++t) {
+    char* cur = smem + (t & 1) * STAGE_BYTES;
+    char* nxt = smem + ((t + 1) & 1) * STAGE_BYTES;
+    const bool more = (t + 1) < nk;
+    if (more) {
+      sa.load(A, K, m0, (t + 1) * BK, rows, K, tid);
+      sb.load_glu(W, K, n0, (t + 1) * BK, F, K, tid);
+    }
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      bf16x8 af[MI], bfr[4];
+#pragma unroll
+      for (int i = 0; i < MI; ++i) af[i] = frag<true, BK, false>(cur, wm * (BM / 2) + i * 16, kk, lane);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        bfr[j] = frag<true, BK, false>(cur + A_BYTES, (j >> 1) * 64 + wn * 32 + (j & 1) * 16, kk, lane);
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int i = 0; i < MI; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);
+      __builtin_amdgcn_s_setprio(0);
+    }
+    if (more) {
+      sa.store(nxt, tid);
+      sb.store(nxt + A_BYTES, tid);
+    }
+    __syncthreads();
+  }
+}
+
 struct RowsArgs {
   ExpertPtrs a;       // X_e (forward) or dZ_e (input gradient): [cap][KR]
   const bf16_t* w;    // [n][N][K]; read [NO][KR] K-contiguous (forward) or [KR][NO] (input gradient)
@@ -129,18 +224,8 @@ __global__ void __launch_bounds__(NT, 2) experts_rows_kernel(RowsArgs p) {
   const int tn = (p.NO + BN - 1) / BN;
   const bf16_t* A = p.a.p[e];
   const int rows = A ? live_rows(p.load, e, p.cap) : 0;
-  // The first tm_live * tn block ids take the live tiles, in gemm_tile.h's order over the live rows
-  // only; the others take the empty tiles behind them. Consecutive block ids go to consecutive XCDs,
-  // so the live tiles spread over all of them whatever share of the capacity is filled (the tile
-  // order over all cap rows put them on the first XCDs only: 2x the time at half load).
-  const int tm_live = (rows + BM - 1) / BM, n_live = tm_live * tn;
   int tile_m, tile_n;
-  if ((int)blockIdx.x < n_live) {
-    tile_coords(blockIdx.x, tm_live, tn, tile_m, tile_n);
-  } else {
-    tile_m = tm_live + ((int)blockIdx.x - n_live) / tn;
-    tile_n = ((int)blockIdx.x - n_live) % tn;
-  }
+  deal_tile<BM>(blockIdx.x, rows, tn, tile_m, tile_n);
   const int m0 = tile_m * BM, n0 = tile_n * BN;
   bf16_t* Y = p.y + (int64_t)e * p.cap * p.NO;
   bf16_t* Z = p.z ? p.z + (int64_t)e * p.cap * p.NO : nullptr;
@@ -237,6 +322,129 @@ __global__ void __launch_bounds__(NT, 2) experts_rows_kernel(RowsArgs p) {
       const int64_t o = (int64_t)m * p.NO + n;
       *reinterpret_cast<ushort4*>(Y + o) = yo;
       if (Z) *reinterpret_cast<ushort4*>(Z + o) = zo;
+    }
+  }
+}
+
+struct GluRowsArgs {
+  ExpertPtrs a;       // X_e [cap][K]
+  const bf16_t* w;    // [n][2F][K]: F gate rows, then F up rows, per expert
+  const void* bias;   // optional [n][2F] in the same order, bf16 or fp32
+  bf16_t* h;          // [n][cap][F]
+  bf16_t* z;          // optional [n][cap][2F] = (zg | zu)
+  const int* load;
+  int cap, F, K, act, bias_bf16;
+};
+
+// Gated forward: one workgroup owns a BM x 64 tile of H_e. Its B stage holds the 64 gate rows and the 64
+// up rows of those output columns, so accumulator slots j and j + 2 of a lane are zg and zu of the same
+// element and act(zg) * zu is taken in registers from the fp32 sums. STAGED: the bf16 H tile and the two
+// Z half tiles go through the LDS the K loop has left free (row r at r * 128 B, its eight 16-B chunks
+// swizzled by r & 7: the lanes' 8-B writes and the 16-B reads both run without bank conflicts) and leave
+// as whole 16-B row chunks, eight consecutive lanes to a 128-B row segment; otherwise each lane stores
+// its 8-B quads straight from the accumulators.
+template <int BM, bool STAGED>
+__global__ void __launch_bounds__(NT, 2) experts_glu_rows_kernel(GluRowsArgs p) {
+  constexpr int A_BYTES = BM * BK * 2, B_BYTES = BN * BK * 2, STAGE_BYTES = A_BYTES + B_BYTES;
+  constexpr int MI = BM / 32, BNH = 64, OUT_BYTES = BM * BNH * 2;
+  static_assert(3 * OUT_BYTES <= 2 * STAGE_BYTES, "H and the two Z halves fit the K loop's LDS");
+  __shared__ __attribute__((aligned(16))) char smem[2 * STAGE_BYTES];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int e = blockIdx.y;
+  const int F = p.F, tn = (F + BNH - 1) / BNH;
+  const bf16_t* A = p.a.p[e];
+  const int rows = A ? live_rows(p.load, e, p.cap) : 0;
+  int tile_m, tile_n;
+  deal_tile<BM>(blockIdx.x, rows, tn, tile_m, tile_n);
+  const int m0 = tile_m * BM, n0 = tile_n * BNH;
+  bf16_t* H = p.h + (int64_t)e * p.cap * F;
+  bf16_t* Z = p.z ? p.z + (int64_t)e * p.cap * 2 * F : nullptr;
+
+  if (m0 >= rows) {  // nothing routed here: no operand load, no MFMA, the tile is zeros
+    for (int id = tid; id < BM * (BNH / 8); id += NT) {
+      const int m = m0 + (id >> 3), n = n0 + (id & 7) * 8;
+      if (m < p.cap && n < F) {
+        *reinterpret_cast<uint4*>(H + (int64_t)m * F + n) = make_uint4(0, 0, 0, 0);
+        if (Z) {
+          *reinterpret_cast<uint4*>(Z + (int64_t)m * 2 * F + n) = make_uint4(0, 0, 0, 0);
+          *reinterpret_cast<uint4*>(Z + (int64_t)m * 2 * F + F + n) = make_uint4(0, 0, 0, 0);
+        }
+      }
+    }
+    return;
+  }
+
+  const bf16_t* W = p.w + (int64_t)e * 2 * F * p.K;
+  f32x4 acc[MI][4];
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  glu_mainloop<BM>(smem, A, W, p.K, F, m0, n0, rows, tid, lane, wm, wn, acc);
+
+  // lane holds zg = acc[i][j], zu = acc[i][j + 2] of H[m][n .. n + 3], m = m0 + r, r = wm * BM/2 + 16 i +
+  // (lane & 15), n = n0 + c, c = wn * 32 + 16 j + 4 (lane >> 4); F % 8 == 0 keeps every quad whole. Rows
+  // in [rows, cap) of a partial tile: zeros. Columns at or beyond F have no bias and are not stored.
+  const int r0 = wm * (BM / 2) + (lane & 15);
+  const int c0 = wn * 32 + (lane >> 4) * 4;
+#pragma unroll
+  for (int i = 0; i < MI; ++i) {
+    const int r = r0 + i * 16, m = m0 + r;
+    if (!STAGED && m >= p.cap) continue;
+    const bool live = m < rows;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int c = c0 + j * 16, n = n0 + c;
+      if (n >= F) continue;
+      ushort4 ho = make_ushort4(0, 0, 0, 0), go = ho, uo = ho;
+      if (live) {
+        float g[4], u[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          g[q] = acc[i][j][q];
+          u[q] = acc[i][j + 2][q];
+          if (p.bias) {
+            const int64_t bi = (int64_t)e * 2 * F + n + q;
+            g[q] += p.bias_bf16 ? bf2f(((const bf16_t*)p.bias)[bi]) : ((const float*)p.bias)[bi];
+            u[q] += p.bias_bf16 ? bf2f(((const bf16_t*)p.bias)[bi + F]) : ((const float*)p.bias)[bi + F];
+          }
+        }
+        go = make_ushort4(f2bf(g[0]), f2bf(g[1]), f2bf(g[2]), f2bf(g[3]));
+        uo = make_ushort4(f2bf(u[0]), f2bf(u[1]), f2bf(u[2]), f2bf(u[3]));
+#pragma unroll
+        for (int q = 0; q < 4; ++q) g[q] = glu_act(p.act, g[q]) * u[q];
+        ho = make_ushort4(f2bf(g[0]), f2bf(g[1]), f2bf(g[2]), f2bf(g[3]));
+      }
+      if (STAGED) {
+        char* q = smem + r * (BNH * 2) + (((c >> 3) ^ (r & 7)) << 4) + (c & 7) * 2;
+        *reinterpret_cast<ushort4*>(q) = ho;
+        if (Z) {
+          *reinterpret_cast<ushort4*>(q + OUT_BYTES) = go;
+          *reinterpret_cast<ushort4*>(q + 2 * OUT_BYTES) = uo;
+        }
+      } else {
+        *reinterpret_cast<ushort4*>(H + (int64_t)m * F + n) = ho;
+        if (Z) {
+          *reinterpret_cast<ushort4*>(Z + (int64_t)m * 2 * F + n) = go;
+          *reinterpret_cast<ushort4*>(Z + (int64_t)m * 2 * F + F + n) = uo;
+        }
+      }
+    }
+  }
+  if (STAGED) {
+    __syncthreads();
+    for (int id = tid; id < BM * (BNH / 8); id += NT) {
+      const int r = id >> 3, c8 = id & 7;
+      const int m = m0 + r, n = n0 + c8 * 8;
+      if (m < p.cap && n < F) {
+        const char* q = smem + r * (BNH * 2) + ((c8 ^ (r & 7)) << 4);
+        *reinterpret_cast<uint4*>(H + (int64_t)m * F + n) = *reinterpret_cast<const uint4*>(q);
+        if (Z) {
+          *reinterpret_cast<uint4*>(Z + (int64_t)m * 2 * F + n) = *reinterpret_cast<const uint4*>(q + OUT_BYTES);
+          *reinterpret_cast<uint4*>(Z + (int64_t)m * 2 * F + F + n) = *reinterpret_cast<const uint4*>(q + 2 * OUT_BYTES);
+        }
+      }
     }
   }
 }
@@ -365,6 +573,38 @@ __global__ void __launch_bounds__(NT) experts_dact_kernel(ExpertPtrs dy, const b
   }
 }
 
+// Gate backward over the live rows of every expert, one 16-B chunk of dH (8 columns) per thread and step:
+// dZ_e[r, c] = dH_e[r, c] * Zu * act'(Zg), dZ_e[r, F + c] = dH_e[r, c] * act(Zg), act and act' from one
+// glu_act_grad. Rows >= r_e of the dZ slab are not written (no grouped kernel reads them).
+__global__ void __launch_bounds__(NT) experts_glu_bwd_kernel(ExpertPtrs dh, const bf16_t* __restrict__ z,
+                                                            bf16_t* __restrict__ dz, const int* __restrict__ load,
+                                                            int cap, int F, int act) {
+  const int e = blockIdx.y;
+  const bf16_t* g = dh.p[e];
+  if (!g) return;
+  const int f8 = F >> 3;
+  const int64_t live = (int64_t)live_rows(load, e, cap) * f8;
+  const int64_t base = (int64_t)e * cap * 2 * F;
+  for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < live; i += (int64_t)gridDim.x * NT) {
+    const int64_t r = i / f8;
+    const int c = (int)(i - r * f8) * 8;
+    const int64_t o = base + r * 2 * F + c;
+    float d[8], a[8], b[8];
+    load16(g + r * F + c, d);
+    load16(z + o, a);
+    load16(z + o + F, b);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float y, dy;
+      glu_act_grad(act, a[j], y, dy);
+      a[j] = d[j] * b[j] * dy;
+      b[j] = d[j] * y;
+    }
+    store16(dz + o, a);
+    store16(dz + o + F, b);
+  }
+}
+
 bool al16(const void* q) { return ((uintptr_t)q & 15) == 0; }
 
 // pointer table of n experts; false when one is misaligned (null = an expert without rows)
@@ -446,6 +686,49 @@ bool experts_act_bwd(const void* const* dys, int n, const void* z, void* dz, con
   const int gx = (int)std::max<int64_t>(1, std::min<int64_t>(chunks, 2048 / n));
   hipLaunchKernelGGL(experts_dact_kernel, dim3(gx, n), dim3(NT), 0, st, t, reinterpret_cast<const bf16_t*>(z),
                      reinterpret_cast<bf16_t*>(dz), load, cap, N, act);
+  return true;
+}
+
+namespace {
+
+// The default epilogue of the gated forward (docs/PERFORMANCE.md, 'Gated expert GEMMs')
+constexpr bool kGluStagedEpilogue = true;
+
+template <bool STAGED>
+void launch_glu_rows(const GluRowsArgs& p, int n, int tile_m, hipStream_t st) {
+  const bool small = tile_m == 64 || (tile_m == 0 && experts_tile_m(p.cap) == 64);
+  const int bm = small ? 64 : 128;
+  dim3 grid(((p.cap + bm - 1) / bm) * ((p.F + 63) / 64), n);
+  if (small) hipLaunchKernelGGL((experts_glu_rows_kernel<64, STAGED>), grid, dim3(NT), 0, st, p);
+  else hipLaunchKernelGGL((experts_glu_rows_kernel<128, STAGED>), grid, dim3(NT), 0, st, p);
+}
+
+}  // namespace
+
+bool experts_glu_fwd(const void* const* xs, int n, const void* w, const void* bias, int bias_bf16, const int* load,
+                     void* h, void* z, int cap, int F, int K, int act, int tile_m, int epilogue, hipStream_t st) {
+  GluRowsArgs p;
+  if (!shape_ok(n, cap, F, K) || !fill_table(p.a, xs, n) || !al16(w) || !al16(h) || !al16(z)) return false;
+  p.w = reinterpret_cast<const bf16_t*>(w);
+  p.bias = bias;
+  p.bias_bf16 = bias_bf16;
+  p.h = reinterpret_cast<bf16_t*>(h);
+  p.z = reinterpret_cast<bf16_t*>(z);
+  p.load = load;
+  p.cap = cap; p.F = F; p.K = K; p.act = act;
+  if (epilogue == 1 || (epilogue == 0 && kGluStagedEpilogue)) launch_glu_rows<true>(p, n, tile_m, st);
+  else launch_glu_rows<false>(p, n, tile_m, st);
+  return true;
+}
+
+bool experts_glu_bwd(const void* const* dhs, int n, const void* z, void* dz, const int* load, int cap, int F, int act,
+                     hipStream_t st) {
+  ExpertPtrs t;
+  if (!shape_ok(n, cap, F, 8) || !fill_table(t, dhs, n) || !al16(z) || !al16(dz)) return false;
+  const int64_t chunks = ((int64_t)cap * F / 8 + NT - 1) / NT;
+  const int gx = (int)std::max<int64_t>(1, std::min<int64_t>(chunks, 2048 / n));
+  hipLaunchKernelGGL(experts_glu_bwd_kernel, dim3(gx, n), dim3(NT), 0, st, t, reinterpret_cast<const bf16_t*>(z),
+                     reinterpret_cast<bf16_t*>(dz), load, cap, F, act);
   return true;
 }
 

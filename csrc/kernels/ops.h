@@ -197,6 +197,18 @@ bool experts_bwd_weight(const void* const* dzs, const void* const* xs, int n, co
 // dz_e[r] = dy_e[r] * act'(z_e[r]) for the live rows (the others are not written)
 bool experts_act_bwd(const void* const* dys, int n, const void* z, void* dz, const int* load, int cap, int N, int act,
                      hipStream_t st);
+// Gated experts: w [n][2F][K] with the F gate rows of an expert first and its F up rows behind them,
+// bias [n][2F] likewise. h_e[r] = act(x_e[r] . Wg_e^T + bg_e) * (x_e[r] . Wu_e^T + bu_e) for the live
+// rows, one rounding from the fp32 accumulators; h [n][cap][F], z (optional) [n][cap][2F] = (zg | zu)
+// in bf16; zeros at or beyond the load in both. act: a GluAct code (glu_act.h). epilogue: 0 = the
+// default, 1 = staged through LDS and written as 16-byte row chunks, 2 = 8-byte stores from the
+// accumulator lanes. Refuses as experts_fwd does, with F in the place of N.
+bool experts_glu_fwd(const void* const* xs, int n, const void* w, const void* bias, int bias_bf16, const int* load,
+                     void* h, void* z, int cap, int F, int K, int act, int tile_m, int epilogue, hipStream_t st);
+// dz [n][cap][2F]: dz[:, :F] = dh * zu * act'(zg), dz[:, F:] = dh * act(zg) for the live rows (the others are
+// not written); z is experts_glu_fwd's. experts_bwd_data / experts_bwd_weight then take dz with N = 2F.
+bool experts_glu_bwd(const void* const* dhs, int n, const void* z, void* dz, const int* load, int cap, int F, int act,
+                     hipStream_t st);
 
 // norm.hip
 void layernorm_fwd(int dt, const void* x, const void* res, void* sum_out, const void* gamma, const void* beta,

@@ -106,21 +106,26 @@ class PerExpertInitializer(Initializer):
     """Initializer of a stacked expert weight [n, out, in] (ops/misc.py ExpertsDense): slice e is filled
     as a dense layer's [out, in] weight would be (fan-in and fan-out per expert, not over the 3-D
     tensor) by `inner` (default Glorot uniform), each expert with a seed of its own. seed None: the
-    model-local seed of the weight (Executor.init_weights)."""
+    model-local seed of the weight (Executor.init_weights). halves = 2: a gated expert's [2 * out, in] slice
+    is two [out, in] weights (gate rows, then up rows), each filled with its own fans and seed."""
 
-    def __init__(self, inner=None):
+    def __init__(self, inner=None, halves=1):
         self.inner = inner
+        self.halves = int(halves)
         self.seed = None
 
     def fill_full(self, t, shape):
         import copy
+        rows = shape[1] // self.halves
+        part = (rows,) + tuple(shape[2:])
         for e in range(shape[0]):
-            init = copy.copy(self.inner) if self.inner is not None else GlorotUniformInitializer(None)
-            base = self.seed if getattr(init, "seed", 0) is None else getattr(init, "seed", 0)
-            init.seed = int(base or 0) + 7919 * e
-            blk = torch.empty(tuple(shape[1:]), dtype=t.dtype, device=t.device)
-            init.fill_full(blk, tuple(shape[1:]))
-            t[e].copy_(blk)
+            for h in range(self.halves):
+                init = copy.copy(self.inner) if self.inner is not None else GlorotUniformInitializer(None)
+                base = self.seed if getattr(init, "seed", 0) is None else getattr(init, "seed", 0)
+                init.seed = int(base or 0) + 7919 * e + 104729 * h
+                blk = torch.empty(part, dtype=t.dtype, device=t.device)
+                init.fill_full(blk, part)
+                t[e, h * rows:(h + 1) * rows].copy_(blk)
 
 
 class BlockInitializer(Initializer):

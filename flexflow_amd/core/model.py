@@ -545,21 +545,32 @@ class FFModel:
         return L.outputs[0]
 
     def experts_dense(self, inputs, assign, out_dim, activation=ActiMode.AC_MODE_NONE, use_bias=True,
-                      kernel_initializer=None, bias_initializer=None, name=None):
+                      kernel_initializer=None, bias_initializer=None, name=None, gate_activation=None):
         """The dense layer of every expert as one layer (extension; ops/misc.py ExpertsDense): inputs are the n
         tensors [cap, in_dim] of group_by (or of a previous experts_dense), assign the [B, k] top-k indices that
         routed them. Returns n tensors [cap, out_dim]: activation(x_e . W_e^T + b_e) on the rows the router
         filled, zeros after. Weights: kernel (n, out_dim, in_dim), each expert's slice initialised as dense
         would initialise an (out_dim, in_dim) weight, and bias (n * out_dim,). One grouped GEMM launch per
-        direction instead of one per expert, computing the routed rows only."""
+        direction instead of one per expert, computing the routed rows only.
+        gate_activation ("silu", "gelu", "gelu_tanh", "relu" or "sigmoid"): gated experts (SwiGLU / GeGLU), each
+        output gate_activation(x_e . Wg_e^T + bg_e) * (x_e . Wu_e^T + bu_e), still [cap, out_dim]. The kernel is
+        then (n, 2 * out_dim, in_dim), an expert's out_dim gate rows first and its up rows behind them, each half
+        initialised as an (out_dim, in_dim) weight, and the bias (n * 2 * out_dim,); the gate runs inside the
+        grouped forward GEMM. `activation` must stay AC_MODE_NONE with it."""
         inputs = list(inputs)
         if not inputs:
             raise ValueError("experts_dense: needs at least one expert input")
         if int(out_dim) < 1:
             raise ValueError(f"experts_dense: out_dim must be positive, got {out_dim}")
-        L = self._add(OperatorType.OP_EXPERTS_DENSE, inputs + [assign], name, out_dim=int(out_dim),
-                      activation=activation, use_bias=bool(use_bias), kernel_init=kernel_initializer,
-                      bias_init=bias_initializer)
+        attrs = dict(out_dim=int(out_dim), activation=activation, use_bias=bool(use_bias),
+                     kernel_init=kernel_initializer, bias_init=bias_initializer)
+        if gate_activation is not None:
+            from .. import kernels as K
+            K.glu_act_code("experts_dense", gate_activation)
+            if activation != ActiMode.AC_MODE_NONE:
+                raise ValueError("experts_dense: gate_activation replaces activation; pass only one of them")
+            attrs["gate_activation"] = gate_activation
+        L = self._add(OperatorType.OP_EXPERTS_DENSE, inputs + [assign], name, **attrs)
         return list(L.outputs)
 
     def moe(self, input, num_exp, num_select, expert_hidden_size, alpha, lambda_bal, fused_experts=False):
@@ -578,21 +589,30 @@ class FFModel:
         return self.aggregate(agg, num_exp, lambda_bal)
 
     def moe_ffn(self, input, num_exp, num_select, ffn_dim, alpha=2.0, lambda_bal=0.0,
-                activation=ActiMode.AC_MODE_GELU, name=None):
+                activation=ActiMode.AC_MODE_GELU, name=None, gate_activation=None, use_bias=True):
         """The mixture-of-experts FFN of current decoders (extension): a linear gate, top-k routing with
         softmax weights over the picks, and per expert down(activation(up(x))) with up [ffn_dim, D] and down
         [D, ffn_dim], summed with the routing weights. input [B, D] -> [B, D]. Built from dense (gate), top_k,
         group_by, two experts_dense and aggregate (layers {name}_gate, _topk, _group, _up, _down, _agg): two
-        grouped GEMM layers, no layer per expert."""
+        grouped GEMM layers, no layer per expert.
+        gate_activation (a name as for experts_dense): gated experts, down(gate_activation(gate(x)) * up(x)) as
+        in Mixtral, Qwen-MoE or DeepSeek-MoE: {name}_up is then the gated experts_dense with the stacked
+        [2 * ffn_dim, D] gate / up weight and `activation` is ignored for it (passing a non-default one too is an
+        error). use_bias goes to both expert layers (those decoders have none)."""
         if int(ffn_dim) < 1:
             raise ValueError(f"moe_ffn: ffn_dim must be positive, got {ffn_dim}")
+        if gate_activation is not None:
+            if activation != ActiMode.AC_MODE_GELU:
+                raise ValueError("moe_ffn: gate_activation replaces activation; pass only one of them")
+            activation = ActiMode.AC_MODE_NONE
         n = (lambda s: None) if name is None else (lambda s: f"{name}_{s}")
         D = input.dims[-1]
         gate = self.dense(input, num_exp, name=n("gate"))
         topk_v, topk_i = self.top_k(gate, num_select, False, name=n("topk"))
         exp_t = self.group_by(input, topk_i, num_exp, alpha, name=n("group"))
-        h = self.experts_dense(exp_t, topk_i, int(ffn_dim), activation, name=n("up"))
-        y = self.experts_dense(h, topk_i, D, name=n("down"))
+        h = self.experts_dense(exp_t, topk_i, int(ffn_dim), activation, use_bias, name=n("up"),
+                               gate_activation=gate_activation)
+        y = self.experts_dense(h, topk_i, D, use_bias=use_bias, name=n("down"))
         return self.aggregate([self.softmax(topk_v, name=n("weights")), topk_i, topk_i, gate] + y, num_exp,
                               lambda_bal, name=n("agg"))
 

@@ -3082,6 +3082,55 @@ def experts_act_bwd(dys, z, load, act):
     return torch.where(live, dy * act_grad_ref(z.float(), act), 0.0).to(z.dtype)
 
 
+def experts_glu_fwd(xs, w, b, load, act, save_z=False, tile_m=0, epilogue=0):
+    """Gated experts: w [n, 2F, K] with an expert's F gate rows first and its F up rows behind them (the
+    packing of glu's x[..., :F] / x[..., F:]), b [n * 2F] likewise or None; act a GLU_ACTS name.
+    h[e, r] = act(zg) * zu with (zg | zu) = xs[e][r] . w[e]^T + b[e] for r < load[e], zeros after: one grouped
+    GEMM whose epilogue takes the product from the fp32 sums (experts.hip). Returns (h [n, cap, F], z): z is
+    the bf16 slab [n, cap, 2F] of (zg | zu) when save_z, else None. epilogue: 0 the kernel's default, 1 staged
+    through LDS, 2 direct (for the benchmark and the tests)."""
+    code = glu_act_code("experts_glu_fwd", act)
+    n, N2, Kd = w.shape
+    if N2 % 2:
+        raise ValueError(f"experts_glu_fwd: w must be [n, 2F, K], got {list(w.shape)}")
+    F_ = N2 // 2
+    like = next(t for t in xs if t is not None)
+    cap, dev = like.shape[0], like.device
+    if _experts_dev(n, w, xs):
+        h = torch.empty(n, cap, F_, device=dev, dtype=torch.bfloat16)
+        z = torch.empty(n, cap, N2, device=dev, dtype=torch.bfloat16) if save_z else None
+        if ext().experts_glu_fwd(_experts_cont(xs), w, b, load, h, z, code, tile_m, epilogue):
+            return h, z
+    live = _experts_live(load, cap, dev)
+    x = torch.where(live, _experts_stack(xs, cap, Kd, dev), 0.0)
+    r = torch.einsum("erk,enk->ern", x, w.float())
+    if b is not None:
+        r = r + b.float().view(n, 1, N2)
+    h = torch.where(live, _glu_act_f32(r[..., :F_], act) * r[..., F_:], 0.0).to(w.dtype)
+    return h, (torch.where(live, r, 0.0).to(w.dtype) if save_z else None)
+
+
+def experts_glu_bwd(dhs, z, load, act):
+    """dz slab [n, cap, 2F] of the gated experts from experts_glu_fwd's z: dz[..., :F] = dh * zu * act'(zg),
+    dz[..., F:] = dh * act(zg) for r < load[e] (other rows: unspecified on the HIP path, zeros on the
+    fallback; no consumer reads them). experts_bwd_data / experts_bwd_weight take it with N = 2F."""
+    code = glu_act_code("experts_glu_bwd", act)
+    n, cap, N2 = z.shape
+    F_ = N2 // 2
+    if _experts_dev(n, z, dhs):
+        dz = torch.empty_like(z)
+        if ext().experts_glu_bwd(_experts_cont(dhs), z, dz, load, code):
+            return dz
+    live = _experts_live(load, cap, z.device)
+    dh = torch.where(live, _experts_stack(dhs, cap, F_, z.device), 0.0)
+    zf = torch.where(live, z.float(), 0.0)
+    g, u = zf[..., :F_].detach().requires_grad_(), zf[..., F_:]
+    with torch.enable_grad():
+        a = _glu_act_f32(g, act)
+    (da,) = torch.autograd.grad(a, g, dh * u)  # dh * zu * act'(zg)
+    return torch.where(live, torch.cat([da, dh * a.detach()], -1), 0.0).to(z.dtype)
+
+
 def experts_bwd_data(dz, w, load, tile_m=0):
     """slab[e, r] = dz[e][r] . w[e] for r < load[e], zeros after."""
     n, N, Kd = w.shape

@@ -325,7 +325,11 @@ class ExpertsDense(OpImpl):
     for the rows the router filled (row < load[e]), zeros after. Weights: kernel [n, out, in], bias
     [n * out] (1-D, so the optimizers keep treating it as a bias). One grouped MFMA GEMM per direction
     (csrc/kernels/experts.hip) whose row counts are the device-side load of K.moe_route: no launch per
-    expert, no work on the capacity's empty rows, no host synchronisation. Replicated, like GroupBy."""
+    expert, no work on the capacity's empty rows, no host synchronisation. Replicated, like GroupBy.
+    gate_activation (a K.GLU_ACTS name): gated experts, y_e = act(x_e . Wg_e^T + bg_e) * (x_e . Wu_e^T + bu_e),
+    kernel [n, 2 * out, in] with an expert's gate rows first and its up rows behind them, bias [n * 2 * out]
+    likewise. The product is the forward GEMM's epilogue and the gate backward one grouped launch
+    (K.experts_glu_fwd / K.experts_glu_bwd); the two gradient GEMMs are the ungated layer's with N = 2 * out."""
     op_type = OperatorType.OP_EXPERTS_DENSE
 
     @classmethod
@@ -338,9 +342,10 @@ class ExpertsDense(OpImpl):
         cap, din = exps[0]
         attrs["n"], attrs["cap"] = n, cap
         dt = in_dtypes[0]
-        ws = [WeightSpec("kernel", (n, out, din), dt, PerExpertInitializer(attrs.get("kernel_init")))]
+        halves = 2 if attrs.get("gate_activation") is not None else 1
+        ws = [WeightSpec("kernel", (n, halves * out, din), dt, PerExpertInitializer(attrs.get("kernel_init"), halves))]
         if attrs.get("use_bias", True):
-            ws.append(WeightSpec("bias", (n * out,), dt, attrs.get("bias_init")))
+            ws.append(WeightSpec("bias", (n * halves * out,), dt, attrs.get("bias_init")))
         return [(cap, out)] * n, [dt] * n, ws
 
     def axis_kinds(self):
@@ -356,6 +361,10 @@ class ExpertsDense(OpImpl):
     def act(self):
         return self.attrs.get("activation", ActiMode.AC_MODE_NONE).value
 
+    @property
+    def gate(self):
+        return self.attrs.get("gate_activation")
+
     def saves_output(self):
         return False  # backward reads the inputs and the saved pre-activation only
 
@@ -370,7 +379,10 @@ class ExpertsDense(OpImpl):
             flat = assign.reshape(-1).long().clamp(0, n - 1)
             load = torch.nn.functional.one_hot(flat, n).sum(0).to(torch.int32)
         exps = [x.to(w.dtype) for x in exps]
-        y, z = K.experts_fwd(exps, w, b, load, self.act, save_z=ctx.training)
+        if self.gate is not None:
+            y, z = K.experts_glu_fwd(exps, w, b, load, self.gate, save_z=ctx.training)
+        else:
+            y, z = K.experts_fwd(exps, w, b, load, self.act, save_z=ctx.training)
         if ctx.training:
             ctx.saved.update(xs=exps, w=w, z=z, load=load)
         return list(y.unbind(0))
@@ -383,7 +395,10 @@ class ExpertsDense(OpImpl):
         if all(d is None for d in douts):
             return [None] * (n + 1)
         dz = [None if d is None else d.to(w.dtype) for d in douts]
-        if self.act != K.ACT_NONE:
+        if self.gate is not None:
+            slab = K.experts_glu_bwd(dz, z, load, self.gate)
+            dz = [None if d is None else slab[e] for e, d in enumerate(dz)]
+        elif self.act != K.ACT_NONE:
             slab = K.experts_act_bwd(dz, z, load, self.act)
             dz = [None if d is None else slab[e] for e, d in enumerate(dz)]
         dx = K.experts_bwd_data(dz, w, load)
@@ -396,8 +411,10 @@ class ExpertsDense(OpImpl):
         return i < self.attrs["n"]
 
     def flops(self, in_shapes, out_shapes, w_shapes):
-        """2 * n * cap * in * out: the capacity, an upper bound (the kernels compute the load's rows only)."""
-        return 2.0 * self.attrs["n"] * self.attrs["cap"] * in_shapes[0][-1] * self.attrs["out_dim"]
+        """2 * n * cap * in * out (gated: 2 * out): the capacity, an upper bound (the kernels compute the load's
+        rows only)."""
+        out = self.attrs["out_dim"] * (2 if self.gate is not None else 1)
+        return 2.0 * self.attrs["n"] * self.attrs["cap"] * in_shapes[0][-1] * out
 
     def uses_mfma(self):
         return True

@@ -12,6 +12,15 @@ layers of an expert FFN (up: D -> ffn with GELU, down: ffn -> D), times per dire
 in one process, alternating the variants round by round, each round timed with device events around
 `--reps` back-to-back calls. Prints one JSON line per case; --out also writes them to a file.
 
+--gated times the gated (SwiGLU) up layer instead, D -> (ffn gate | ffn up) -> ffn, SiLU gate, per case:
+
+  forward  : one K.experts_glu_fwd (default epilogue, with and without save_z, and the LDS-staged and the
+             direct epilogue forced) against K.experts_fwd(N = 2 ffn, ACT_NONE) plus the n K.glu_fwd
+             launches on the packed halves of its slab
+  backward : one K.experts_glu_bwd against the n K.glu_bwd launches
+
+and prints the medians with the spread (min .. max) of the rounds.
+
 Routing: 'uniform' gives every expert B * k / n rows; 'overloaded' gives expert 0 four times that
 (clamped to the capacity) and spreads the rest evenly.
 """
@@ -38,8 +47,9 @@ def loads(n, cap, routing):
     return [min(big, cap)] + [min(rest, cap)] * (n - 1)
 
 
-def time_interleaved(variants, rounds, reps):
-    """{name: fn} -> {name: median ms per call}; the variants alternate inside every round."""
+def time_interleaved(variants, rounds, reps, spread=False):
+    """{name: fn} -> {name: median ms per call}; the variants alternate inside every round. spread: the
+    values are [median, min, max] over the rounds."""
     for fn in variants.values():
         fn()
     torch.cuda.synchronize()
@@ -53,6 +63,8 @@ def time_interleaved(variants, rounds, reps):
             b.record()
             b.synchronize()
             times[name].append(a.elapsed_time(b) / reps)
+    if spread:
+        return {k: [round(t, 4) for t in (sorted(v)[len(v) // 2], min(v), max(v))] for k, v in times.items()}
     return {k: sorted(v)[len(v) // 2] for k, v in times.items()}
 
 
@@ -112,6 +124,48 @@ def run_case(n, alpha, routing, layer, rounds, reps):
     return out
 
 
+def run_gated_case(n, alpha, routing, rounds, reps, act="silu"):
+    dev = "cuda"
+    cap = int(math.ceil(alpha * PAIRS / n))
+    ld = loads(n, cap, routing)
+    load = torch.tensor(ld, device=dev, dtype=torch.int32)
+    g = torch.Generator(device=dev).manual_seed(0)
+    rnd = lambda *s: torch.randn(*s, device=dev, generator=g).to(torch.bfloat16)
+    xs, dhs = [], []
+    for r in ld:
+        x, dh = rnd(cap, D), rnd(cap, FFN)
+        x[r:], dh[r:] = 0, 0
+        xs.append(x)
+        dhs.append(dh)
+    w = rnd(n, 2 * FFN, D) * 0.03
+    b = rnd(n * 2 * FFN)
+    h = torch.empty(n, cap, FFN, device=dev, dtype=torch.bfloat16)
+    _, z = K.experts_glu_fwd(xs, w, b, load, act, save_z=True)
+    dz = torch.empty_like(z)
+
+    def unfused_fwd():
+        y, _ = K.experts_fwd(xs, w, b, load, K.ACT_NONE)
+        for e in range(n):
+            K.glu_fwd(y[e, :, :FFN], y[e, :, FFN:], act, out=h[e])
+
+    def unfused_bwd():
+        for e in range(n):
+            K.glu_bwd(z[e, :, :FFN], z[e, :, FFN:], dhs[e], act, dg=dz[e, :, :FFN], du=dz[e, :, FFN:])
+
+    out = dict(gated=act, n=n, alpha=alpha, routing=routing, cap=cap, load_max=max(ld), load_min=min(ld),
+               rows_live=sum(ld), rows_capacity=n * cap, auto_tile_m=int(K.ext().experts_tile_m(cap)))
+    fused = lambda **kw: (lambda: K.experts_glu_fwd(xs, w, b, load, act, **kw))  # noqa: E731
+    out["fwd_ms"] = time_interleaved({"fused": fused(), "fused_save_z": fused(save_z=True),
+                                      "staged_save_z": fused(save_z=True, epilogue=1),
+                                      "direct_save_z": fused(save_z=True, epilogue=2),
+                                      "staged": fused(epilogue=1), "direct": fused(epilogue=2),
+                                      "unfused": unfused_fwd}, rounds, reps, spread=True)
+    out["gate_bwd_ms"] = time_interleaved({"fused": lambda: K.experts_glu_bwd(dhs, z, load, act),
+                                           "unfused": unfused_bwd}, rounds, reps, spread=True)
+    out["useful_tflops_fused"] = round(2.0 * sum(ld) * D * 2 * FFN / (out["fwd_ms"]["fused_save_z"][0] * 1e9), 1)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--experts", type=int, nargs="+", default=[8, 64])
@@ -120,6 +174,7 @@ def main():
     ap.add_argument("--layers", nargs="+", default=["up", "down"])
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--gated", action="store_true", help="the gated up layer against its unfused form")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -128,8 +183,10 @@ def main():
     for n in a.experts:
         for alpha in a.alpha:
             for routing in a.routing:
-                for layer in a.layers:
-                    line = json.dumps(run_case(n, alpha, routing, layer, a.rounds, a.reps))
+                for layer in (["gated"] if a.gated else a.layers):
+                    res = (run_gated_case(n, alpha, routing, a.rounds, a.reps) if a.gated
+                           else run_case(n, alpha, routing, layer, a.rounds, a.reps))
+                    line = json.dumps(res)
                     print(line, flush=True)
                     if sink:
                         sink.write(line + "\n")
